@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native correspondence hot path (driver contract: see README / DESIGN.md).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scope hotpath|netcorr] [--no-cpu-baseline]
-                    [--grad-payload path|netcorr|full] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scope hotpath|netcorr] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]] [--grad-payload path|netcorr|full]
 
 A "step" is ONE forward + backward pass of the hot path over one batch of synthetic ADE20k-shaped
 input (BASELINE.json configs[1]: 256x256 images, batch 8 per GPU, 64x64 feature grid, K = 256,
@@ -13,10 +13,13 @@ V = 3 exemplar colours + 151 one-hot labels), inputs already resident in HBM:
     down to the gradients of the theta/phi weights and of the incoming features
     -> (N > 1) RCCL all-reduce of the parameter gradients.
 
-`value` = images/s summed over all ranks (weak scaling: batch 8 per GPU whatever N).  The same JSON line also
-carries, measured in the same process after the headline window: the exact-fp32-MFMA flavour (`flavours.fp32`), a
->= 300-step stability window (`stability`), and the CPU baseline (the reference's torch op sequence on all host cores,
-plus the numpy port).  `--grad-payload` sizes the gradient exchange of N > 1 runs like BASELINE config 4 (netCorr's
+`value` = images/s summed over all ranks (weak scaling: batch 8 per GPU whatever N), `ms_per_step` = the time of one
+timed step.  A plain run does only that: set-up, W warm-up steps, K timed steps (no HIP events in them), the result
+line.  `--dump-outputs DIR` then writes what the last timed step computed (see dump_outputs).  With `--full` the same
+JSON line also carries, measured in the same process after the headline window: the per-kernel table and the roofline
+(HIP events around the dominant kernel in the timed window, the others in a window of their own), the exact-fp32-MFMA
+flavour (`flavours.fp32`), a >= 300-step stability window (`stability`), the context configurations, and the CPU
+baseline (the reference's torch op sequence on all host cores, plus the numpy port).  `--grad-payload` sizes the gradient exchange of N > 1 runs like BASELINE config 4 (netCorr's
 59 M or the full G+Corr 156 M fp32 parameters) — the hot path alone exchanges only theta/phi's 0.8 MB.
 `--scope netcorr` times the whole drop-in NoVGGCorrespondence module instead (feature producers on the K16 / K16b
 convolutions, K9 / K13 / K17 norms; `COCOS_CONV=f16x3|bf16|torch` picks the convolution flavour, named in
@@ -332,6 +335,32 @@ def make_step(scope, device, match_kernel=1):
     return model, fwd
 
 
+#: --dump-outputs writes at most this many fp32 elements in all (60 MiB); larger outputs are sampled
+DUMP_BUDGET_ELEMS = 15 << 20
+
+
+def dump_outputs(out_dir, outputs, model, d):
+    """--dump-outputs: what the timed step computed in its last step, each array as `<name>.npy` in float32 — the forward's
+    outputs (`warp_out`, `warp_mask`, ...) and the gradients a caller of the step receives: `grad_<parameter>` and
+    `grad_cont_features` / `grad_ref_features`.  The budget is shared out smallest array first; an array above its share
+    is written as a fixed sample (sorted flat indices from a seed-0 permutation, the same in every run), otherwise whole
+    and in its own shape."""
+    import numpy as np
+    arrays = {k: v for k, v in outputs.items()}
+    arrays.update({f"grad_{n}": p.grad for n, p in model.named_parameters() if p.grad is not None})
+    arrays.update({f"grad_{k}": d[k].grad for k in ("cont_features", "ref_features") if k in d and d[k].grad is not None})
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_ELEMS
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))):
+        a = t.detach().float()
+        share = left // (len(arrays) - i)
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        left -= a.numel()
+        np.save(os.path.join(out_dir, name.replace(".", "_") + ".npy"), a.cpu().numpy())
+
+
 def cpu_baseline_numpy(n_images, seed=0):
     """The numpy oracle (fp32, BLAS threads = host cores) on a bounded sample: forward + backward of the hot path
     from theta/phi on, batch 1 per call."""
@@ -589,9 +618,14 @@ def main():
                     help="N > 1: size of the per-step gradient all-reduce.  path = theta/phi only (0.8 MB, what the hot "
                          "path owns); netcorr / full add fp32 stand-in parameters so that the exchange is netCorr's 237 MB "
                          "or BASELINE config 4's 624 MB (their gradients are written every step, in backward order)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel table and roofline, other flavours, "
+                         "stability window, context configurations, CPU baseline, N > 1 exchange probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs and gradients to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the second flavour and the stability window (headline window + roofline only)")
+                    help="--full without the second flavour and the stability window (headline window + roofline only)")
     ap.add_argument("--stability-steps", type=int, default=300)
     ap.add_argument("--cpu-runs", type=int, default=10, help="timed runs of the torch CPU baseline (batch 2 each)")
     ap.add_argument("--cpu-images", type=int, default=10, help="images of the numpy CPU baseline (batch 1 each)")
@@ -610,6 +644,7 @@ def main():
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
 
+    torch.manual_seed(0)     # the parameters' initialisation: identical inputs and weights from run to run
     model, fwd = make_step(args.scope, device, args.match_kernel)
     # stand-ins for the rest of the replica's parameters (BASELINE config 4): fp32 tensors whose gradients are written
     # every step by autograd — first in backward order, like the generator's — and exchanged with the real ones
@@ -631,6 +666,7 @@ def main():
     d = build_inputs(device, args.scope)
     ones = [torch.ones((), device=device) for _ in extra]
     fwd_box = [fwd]          # the forward the step runs (the match_kernel-3 context window swaps it)
+    last = {}                # --dump-outputs: the latest step's outputs, detached (the autograd graph is not kept alive)
 
     def step():
         if buckets is not None:
@@ -649,6 +685,9 @@ def main():
         torch.autograd.backward(roots, [d["g_out"], d["g_mask"]] + ones)
         if buckets is not None:
             buckets.finish(world)
+        if args.dump_outputs:
+            last.clear()
+            last.update((k, v.detach()) for k, v in out.items() if torch.is_tensor(v))
 
     sync = lambda: (torch.distributed.barrier() if world > 1 else None, torch.cuda.synchronize())
 
@@ -679,30 +718,38 @@ def main():
     for _ in range(SETUP_STEPS):
         step()
     sync()
-    # Round 5: the timed window carries HIP events around the DOMINANT kernel only (the one `roofline` is about: ④ asks for
-    # its launch time measured live over the timed region) — every bracketed call costs two marker packets that serialise
-    # dispatch, and six per step were 2-3 % of `value`.  Which kernel that is comes from one fully-bracketed, untimed step;
-    # the other hot kernels' live averages come from a second window of the same length right after the headline one.
-    # the probe is a steady-state window of its own (30 steps after 5 unbracketed ones, all three MFMA kernels bracketed): on an idle
-    # queue an event pair also spans the host's launch latency, and a five-step probe right after a synchronisation ranked the forward
-    # above the query backward on some boxes
-    _, probe = window(30, 5, tags=HOT_TAGS)
-    # (round 6: ONE kernel stays bracketed in the timed window — since the forward's QK loop accumulates in one chain the query backward is
-    #  the longest by > 10 %; the second bracket cost another 1.4 % of `value`).  Ranked by the SHORTEST bracket: the kernel itself
-    dom_tags = tuple(sorted(probe, key=lambda t: -probe[t].get("min_ms", probe[t]["avg_ms"]))[:1])
-    dom_tag = dom_tags[0] if dom_tags else None
-    dt, kern = window(args.steps, args.warmup, tags=dom_tags if dom_tags else HOT_TAGS)
-    with ops.KernelTimer() as kt_all:
-        step()
-    kern_all = kt_all.summary()
-    _, kern_hot = window(args.steps, 0)              # all hot kernels bracketed: the `kernels` table (never part of `value`)
-    kern_timed = dict(kern)                          # what the timed window itself measured: `roofline` is computed from these
-    for tag, rec in kern_hot.items():
-        kern.setdefault(tag, rec)                    # (the bracketed kernels keep their figures from the headline window)
+    # A plain run times the steps with no HIP event in them: the per-kernel table and the roofline are --full's.
+    timed_tags = ()
+    if args.full:
+        # Round 5: the timed window carries HIP events around the DOMINANT kernel only (the one `roofline` is about: ④ asks for
+        # its launch time measured live over the timed region) — every bracketed call costs two marker packets that serialise
+        # dispatch, and six per step were 2-3 % of `value`.  Which kernel that is comes from one fully-bracketed, untimed step;
+        # the other hot kernels' live averages come from a second window of the same length right after the headline one.
+        # the probe is a steady-state window of its own (30 steps after 5 unbracketed ones, all three MFMA kernels bracketed): on an
+        # idle queue an event pair also spans the host's launch latency, and a five-step probe right after a synchronisation ranked
+        # the forward above the query backward on some boxes
+        _, probe = window(30, 5, tags=HOT_TAGS)
+        # (round 6: ONE kernel stays bracketed in the timed window — since the forward's QK loop accumulates in one chain the query
+        #  backward is the longest by > 10 %; the second bracket cost another 1.4 % of `value`).  Ranked by the SHORTEST bracket:
+        #  the kernel itself
+        dom_tags = tuple(sorted(probe, key=lambda t: -probe[t].get("min_ms", probe[t]["avg_ms"]))[:1])
+        timed_tags = dom_tags if dom_tags else HOT_TAGS
+    dt, kern = window(args.steps, args.warmup, tags=timed_tags)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model, d)
+    kern_all, kern_timed = {}, {}
+    if args.full:
+        with ops.KernelTimer() as kt_all:
+            step()
+        kern_all = kt_all.summary()
+        _, kern_hot = window(args.steps, 0)              # all hot kernels bracketed: the `kernels` table (never part of `value`)
+        kern_timed = dict(kern)                          # what the timed window itself measured: `roofline` is computed from these
+        for tag, rec in kern_hot.items():
+            kern.setdefault(tag, rec)                    # (the bracketed kernels keep their figures from the headline window)
 
     # ---- extras, same process / same box, after the headline window (N = 1 only) --------------------------------
     flavours, stability, context = {}, None, None
-    if world == 1 and not args.no_extras and args.scope == "hotpath":
+    if args.full and world == 1 and not args.no_extras and args.scope == "hotpath":
         sdt, _ = window(args.stability_steps, 0, tags=())
         stability = {"steps": args.stability_steps, "ms_per_step": round(sdt / args.stability_steps * 1e3, 4),
                      "images_per_s": round(BATCH_PER_GPU * args.stability_steps / sdt, 1),
@@ -768,7 +815,7 @@ def main():
     # N > 1: what BASELINE config 4's exchanges cost on this node — timed AFTER the contract window, never part of `value`:
     # one in-place all-reduce (RCCL) of a flat fp32 buffer of netCorr's 59 M and of netG+netCorr's 156 M gradients
     exchange_probe = None
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         try:
             exchange_probe = {}
             for name in ("netcorr", "full"):
@@ -790,12 +837,12 @@ def main():
 
     if rank == 0:
         split = headline_precision == "f16x3"
-        kernels = kernel_table(kern, headline_precision)
-        roofline = roofline_of(kernel_table(kern_timed, headline_precision) or kernels, headline_precision)
+        kernels = kernel_table(kern, headline_precision) if args.full else None
+        roofline = roofline_of(kernel_table(kern_timed, headline_precision) or kernels, headline_precision) if args.full else None
         # device time of EVERY C-ABI call per step (ms), so the part of the step outside the three big kernels is visible
-        per_step = {tag: round(rec["total_ms"], 4) for tag, rec in sorted(kern_all.items())}
+        per_step = {tag: round(rec["total_ms"], 4) for tag, rec in sorted(kern_all.items())} if args.full else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1:   # reported at N=1 only (bounded sample)
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N=1 only (bounded sample)
             cpu = cpu_baseline(args.cpu_runs)
             cpu["numpy_port"] = cpu_baseline_numpy(args.cpu_images)
         images = BATCH_PER_GPU * world * args.steps
@@ -813,8 +860,8 @@ def main():
                                       if args.scope == "hotpath" else
                                       "whole NoVGGCorrespondence module fwd+bwd (convolutions K16, norms K9/K13/K17, theta/phi K0); "
                                       f"convolutions={_conv_flavour()}"),
-                       "untimed_steps_before_window": SETUP_STEPS + 1 + args.warmup,
-                       "hip_events_in_timed_window": list(dom_tags) if dom_tags else list(HOT_TAGS),
+                       "untimed_steps_before_window": SETUP_STEPS + (1 if args.full else 0) + args.warmup,
+                       "hip_events_in_timed_window": list(timed_tags),
                        # hygiene: `value` is measured on ADE20k's one-hot label map, whose V_lo MFMA term is
                        # skipped; the same step with every term issued (what configs 3 and 5, with float label maps, get):
                        "value_with_general_v": (flavours.get("general_v") or {}).get("images_per_s"),
@@ -829,6 +876,7 @@ def main():
                                          "in place on flat fp32 gradient buffers" if world > 1 else None},
             "roofline": roofline, "kernels": kernels, "abi_calls_ms_per_step": per_step,
             "flavours": flavours, "stability": stability, "cpu_baseline": cpu, "exchange_probe": exchange_probe,
+            "full": args.full,
         }
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -184,3 +184,43 @@ def compare_with_golden(name: str, outputs: dict, golden) -> dict:
         if k not in keys:
             errs["unexpected:" + k] = float("inf")
     return errs
+
+
+def seeded_state_dict(template, seed: int) -> dict:
+    """Deterministic parameters for a module whose state_dict has the names / shapes / dtypes of `template` (a state_dict):
+    one torch CPU generator seeded with `seed`, entries drawn in sorted-name order, so the result does not depend on how
+    either implementation orders or initialises its layers.  Used to record the reference's outputs for given weights
+    (oracle/make_module_golden.py) and to load the very same weights into the drop-in in the tests.
+      weights (>= 2 dims)       N(0, 1 / fan_in)
+      spectral-norm u / v       the leading singular pair of the matching `weight_orig` (eval mode uses them as stored)
+      1-dim `weight` / `bias`   1 + N(0, 0.1) / N(0, 0.1);   `gamma` (attention) N(0, 0.1)
+      BatchNorm statistics      running_mean 0, running_var 1, num_batches_tracked 0"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k in sorted(template):
+        v = template[k]
+        leaf = k.rsplit(".", 1)[-1]
+        if not v.is_floating_point():
+            out[k] = torch.zeros_like(v)
+        elif leaf in ("running_mean", "weight_u", "weight_v"):
+            out[k] = torch.zeros_like(v)
+        elif leaf == "running_var":
+            out[k] = torch.ones_like(v)
+        elif v.dim() >= 2:
+            out[k] = torch.randn(v.shape, generator=g, dtype=torch.float64).div_(float(v[0].numel()) ** 0.5).to(v.dtype)
+        elif leaf == "weight":
+            out[k] = (1 + 0.1 * torch.randn(v.shape, generator=g, dtype=torch.float64)).to(v.dtype)
+        else:
+            out[k] = (0.1 * torch.randn(v.shape, generator=g, dtype=torch.float64)).to(v.dtype)
+    for k in out:
+        if k.endswith(".weight_orig"):
+            base = k[: -len("weight_orig")]
+            w = out[k].double().reshape(out[k].shape[0], -1)
+            vec = torch.ones(w.shape[1], dtype=torch.float64) / w.shape[1] ** 0.5
+            for _ in range(30):
+                u = torch.nn.functional.normalize(w @ vec, dim=0)
+                vec = torch.nn.functional.normalize(w.t() @ u, dim=0)
+            out[base + "weight_u"] = u.to(out[k].dtype)
+            out[base + "weight_v"] = vec.to(out[k].dtype)
+    return out

@@ -1,6 +1,6 @@
 """CPU checks of the drop-in NoVGGCorrespondence module: checkpoint compatibility (state_dict names
-and shapes equal the reference's), the feature producers against the reference's own code (only
-where /root/reference exists, i.e. in the build container), and injection into the reference's
+and shapes equal the reference's), the feature producers against the reference's recorded outputs
+(tests/golden/producers_*.npz), and, where the reference tree is present, injection into the reference's
 `networks.define_Corr`.  The hot path itself needs a GPU and is covered by test_gpu_parity.py."""
 import argparse
 import json
@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from cocosnet_amd import correspondence as cc
+from oracle import golden_cases as gc
+from oracle import make_module_golden as mg
 from oracle import ref_harness as rh
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "netcorr_state_dict_keys.json")
@@ -65,48 +67,39 @@ def test_hot_path_config_from_opt():
     assert HotPathConfig.from_opt(argparse.Namespace()).down == 4
 
 
-@needs_ref
-@pytest.mark.parametrize("flags", [
-    dict(semantic_nc=6, maskmix=True, PONO=True, PONO_C=True, match_kernel=1),
-    dict(semantic_nc=4, maskmix=False, PONO=True, PONO_C=True, adaptor_kernel=4, warp_bilinear=True),
-    dict(semantic_nc=5, maskmix=True, PONO=False, use_coordconv=True, adaptor_se=True,
-         adaptor_nonlocal=True, adaptor_res_deeper=True, dilation_conv=True, warp_stride=2),
-])
+@pytest.mark.parametrize("flags", list(mg.PRODUCER_CASES.values()))
 def test_producers_match_the_reference_code(flags):
-    """Load the reference's weights into the drop-in and compare theta_raw / phi_raw (the inputs of
-    the hot path) computed by both on CPU."""
-    ref = rh.build_reference_corr(rh.make_opt(**flags), seed=3).eval()
+    """Load the seeded weights the reference was run with (oracle/make_module_golden.py) into the drop-in and compare
+    theta_raw / phi_raw (the inputs of the hot path) with the reference's, recorded under tests/golden/, on CPU."""
+    import numpy as np
+    name = next(k for k, v in mg.PRODUCER_CASES.items() if v == flags)
+    want = np.load(os.path.join(os.path.dirname(GOLDEN), f"producers_{name}.npz"))
     mine = cc.NoVGGCorrespondence(_opt(flags)).eval()
-    mine.load_state_dict(ref.state_dict(), strict=True)
-    g = torch.Generator().manual_seed(0)
-    size = 32
-    img = torch.rand(2, 3, size, size, generator=g) * 2 - 1
-    lab = torch.randint(0, flags["semantic_nc"], (2, 1, size, size), generator=g)
-    seg = torch.zeros(2, flags["semantic_nc"], size, size).scatter_(1, lab, 1.0)
-    ref_seg = seg.flip(0)
-    got = {}
-    hooks = [ref.theta.register_forward_hook(lambda m, i, o: got.__setitem__("theta", o.detach())),
-             ref.phi.register_forward_hook(lambda m, i, o: got.__setitem__("phi", o.detach()))]
+    mine.load_state_dict(gc.seeded_state_dict(mine.state_dict(), mg.PRODUCER_SEED), strict=True)
+    img, seg, ref_seg = mg.producer_inputs(flags["semantic_nc"])
     with torch.no_grad():
-        ref(img, img, seg, ref_seg)
         th, ph = mine.project(img, img, seg, ref_seg)
-    for h in hooks:
-        h.remove()
+    got = {k: torch.from_numpy(want[k]) for k in ("theta", "phi")}
     for a, b in ((th, got["theta"]), (ph, got["phi"])):
         assert a.shape == b.shape
         assert float((a - b).abs().max() / b.abs().max()) < 1e-5
 
 
-@needs_ref
-def test_install_into_reference_define_corr():
-    """The unmodified reference factory builds OUR class once it is injected."""
-    networks = rh.load_reference()
-    ref_corr = __import__("importlib").import_module("models.networks.correspondence")
+def test_install_into_reference_define_corr(monkeypatch):
+    """Once injected, the class the reference's factory finds by name (`novggcorrespondence` in
+    `models.networks.correspondence`, networks/__init__.py:18-26,76-78) is OURS and subclasses the package's
+    `BaseNetwork`; checked on a stand-in package laid out like the reference's."""
+    base = type("BaseNetwork", (torch.nn.Module,), {})
+    reference_class = type("NoVGGCorrespondence", (base,), {})
+    networks = _stand_in_package(monkeypatch, correspondence=dict(NoVGGCorrespondence=reference_class))
+    networks.BaseNetwork = base
+    ref_corr = networks.correspondence
     original = ref_corr.NoVGGCorrespondence
     try:
         cls = cc.install_into_reference(networks)
-        net = rh.build_reference_corr(rh.make_opt(semantic_nc=5, match_kernel=1))
-        assert isinstance(net, cls) and isinstance(net, cc.NoVGGCorrespondence)
+        found = next(v for k, v in vars(ref_corr).items() if k.lower() == "novggcorrespondence")
+        net = found(cc.base_options(semantic_nc=5, match_kernel=1))
+        assert found is cls and isinstance(net, cls) and isinstance(net, cc.NoVGGCorrespondence)
         assert isinstance(net, networks.BaseNetwork)
     finally:
         ref_corr.NoVGGCorrespondence = original
@@ -178,25 +171,42 @@ def test_install_spade_into_reference(pono, monkeypatch):
     assert torch.allclose(y3.detach(), ref[0], atol=1e-6)
 
 
-@needs_ref
-def test_contextual_loss_module_equals_the_reference_class_on_cpu():
+def _stand_in_package(monkeypatch, **submodules):
+    """A package laid out like the reference's `models.networks` (the install helpers look their targets up by module
+    name): `<pkg>.<name>` for each keyword, holding the given attributes."""
+    import sys
+    import types
+    pkg = types.ModuleType("_cocos_stand_in_networks")
+    monkeypatch.setitem(sys.modules, pkg.__name__, pkg)
+    for name, attrs in submodules.items():
+        mod = types.ModuleType(f"{pkg.__name__}.{name}")
+        for k, v in attrs.items():
+            setattr(mod, k, v)
+        setattr(pkg, name, mod)
+        monkeypatch.setitem(sys.modules, mod.__name__, mod)
+    return pkg
+
+
+def test_contextual_loss_module_equals_the_reference_class_on_cpu(monkeypatch):
     """cocosnet_amd.contextual.ContextualLoss_forward restates ContextualLoss.py:93-137: on CPU tensors (where it runs
-    the same formulation in torch) it must agree with the reference class itself, PONO and non-PONO centring."""
-    import importlib
+    the same formulation in torch) it must agree with the reference class itself (its outputs recorded in
+    tests/golden/contextual_loss.npz by oracle/make_module_golden.py), PONO and non-PONO centring."""
+    import numpy as np
     from types import SimpleNamespace
     from cocosnet_amd.contextual import ContextualLoss_forward, install_contextual_loss_into_reference
-    rh.load_reference()
-    ref_mod = importlib.import_module("models.networks.ContextualLoss")
-    g = torch.Generator().manual_seed(0)
-    X, Y = torch.randn(2, 16, 6, 5, generator=g), torch.randn(2, 16, 6, 5, generator=g) + 0.2
+    want = np.load(os.path.join(os.path.dirname(GOLDEN), "contextual_loss.npz"))
+    X, Y = mg.contextual_inputs()
     for pono in (True, False):
         opt = SimpleNamespace(PONO=pono)
         a = ContextualLoss_forward(opt)(X, Y, h=0.1)
-        b = ref_mod.ContextualLoss_forward(opt)(X, Y, h=0.1)
-        assert torch.allclose(a, b, rtol=1e-5, atol=1e-6)
+        b = torch.from_numpy(want[f"pono_{int(pono)}"])
+        assert a.shape == b.shape and torch.allclose(a, b, rtol=1e-5, atol=1e-6)
+    reference_class = type("ContextualLoss_forward", (torch.nn.Module,), {})
+    networks = _stand_in_package(monkeypatch, ContextualLoss=dict(ContextualLoss_forward=reference_class))
+    ref_mod = networks.ContextualLoss
     original = ref_mod.ContextualLoss_forward
     try:
-        assert install_contextual_loss_into_reference(importlib.import_module("models.networks")) is ContextualLoss_forward
+        assert install_contextual_loss_into_reference(networks) is ContextualLoss_forward
         assert ref_mod.ContextualLoss_forward is ContextualLoss_forward
     finally:
         ref_mod.ContextualLoss_forward = original

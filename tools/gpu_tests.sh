@@ -7,7 +7,7 @@ timeout 2400 python -m pytest tests -q -m gpu -x --maxfail=${2:-400} > $O/pytest
 grep -E "^(FAILED|ERROR)" $O/pytest_gpu.log | sed 's/ - .*//' | head -60
 grep -E "^E  " $O/pytest_gpu.log | sort | uniq -c | sort -rn | head -25
 tail -3 $O/pytest_gpu.log
-timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 try:

@@ -18,7 +18,7 @@ for N in 1 2 4 8; do
     python bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --grad-payload $PAYLOAD --no-cpu-baseline --no-extras | tail -1 >> $OUT
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus $N --steps $STEPS --warmup $WARMUP --grad-payload $PAYLOAD --no-cpu-baseline | tail -1 >> $OUT
+      bench.py --gpus $N --full --steps $STEPS --warmup $WARMUP --grad-payload $PAYLOAD --no-cpu-baseline | tail -1 >> $OUT
   fi
 done
 python - "$OUT" <<'PY'
