@@ -21,13 +21,6 @@
 // mean over the 9*256 entries and 1 / (norm + eps).  kc = 2304.
 #include "box3_common.h"
 
-// Ablation builds (debug only, results are WRONG): -DBX_ABLATE=<bits>  1: no column sums (butterfly + LDS atomics),
-// 2: no G / P-plane stores, 4: only the centre T block is loaded (no y box), 8: no MFMAs, 16: key statistics not loaded,
-// 32: no exp — tools/box3_ablate.sh times them.
-#ifndef BX_ABLATE
-#define BX_ABLATE 0
-#endif
-
 namespace cocos {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -91,7 +84,6 @@ __device__ __forceinline__ void bx_fetch(BxTile& tl, const BxGeom& gm, int t, in
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         const int dy = d - 1;
-        if ((BX_ABLATE & 4) && d != 1) continue;
         const bool ok = (unsigned)(gm.py + dy) < (unsigned)gm.himg && (unsigned)(ky + dy) < (unsigned)gm.himg;
         const int kb = tc + dy * gm.tpr, qb = gm.qblk + dy * gm.tpr;
         const int blk = ok ? (gm.xt ? qb * gm.nqblk + kb : kb * gm.nqblk + qb) : 0;
@@ -137,7 +129,7 @@ __device__ __forceinline__ void bx_logits(const BxTile& tl, const BxGeom& gm, in
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            ts[4 * g + e] = (BX_ABLATE & 4) ? tl.s[1][g][e] : (tl.s[0][g][e] + tl.s[2][g][e]) + tl.s[1][g][e];
+            ts[4 * g + e] = (tl.s[0][g][e] + tl.s[2][g][e]) + tl.s[1][g][e];
     if (gm.xt) bx_transpose32(ts, gm.xt, h, lane_c);      // (workgroup-uniform: one branch per tile)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -277,7 +269,7 @@ __device__ __forceinline__ void box3_sw_fwd_body(
         const float nmb = kBxPBias - m_run;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            p[r] = (BX_ABLATE & 32) ? tt[r] * 1e-3f + 1.0f : fast_exp2(__builtin_fmaf(tt[r], a2, nmb));
+            p[r] = fast_exp2(__builtin_fmaf(tt[r], a2, nmb));
             psum += p[r];
         }
         l_run += psum;
@@ -310,11 +302,9 @@ __device__ __forceinline__ void box3_sw_fwd_body(
                         a_l[nxt] = *reinterpret_cast<const f16x8*>(vbase + VPLANE + c2 * 32 * BX_VROW + s2 * 16);
                     a_s[nxt] = *reinterpret_cast<const f16x8*>(vbase + 2 * VPLANE + c2 * 32 * BX_VROW + s2 * 16);
                 }
-                if (!(BX_ABLATE & 8)) {
-                    o[cb] = bx_mfma(a_h[cur], ph[s], o[cb]);
-                    o[cb] = bx_mfma(a_s[cur], pl[s], o[cb]);      // (2^-11 V_hi) . (2^11 P_lo)
-                    if (!VLO0 || cb == 0) o[cb] = bx_mfma(a_l[cur], ph[s], o[cb]);
-                }
+                o[cb] = bx_mfma(a_h[cur], ph[s], o[cb]);
+                o[cb] = bx_mfma(a_s[cur], pl[s], o[cb]);      // (2^-11 V_hi) . (2^11 P_lo)
+                if (!VLO0 || cb == 0) o[cb] = bx_mfma(a_l[cur], ph[s], o[cb]);
                 commit_v_piece(i, buf ^ 1);
                 fetch_v_piece(i, j0 + 64);
                 __builtin_amdgcn_sched_barrier(0);
@@ -519,7 +509,6 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
     // behind the barrier that ended tile t: register group `wave` of the four waves' images, summed -> column sums -> colpart
     float* const cp_b = colpart + ((size_t)b * nqb + wg) * 2 * Nk;
     auto reduce_cols = [&](int t) {
-        if (BX_ABLATE & 1) return;
         const float* a = colacc + (t & 1) * 4 * 2048 + wave * 256 + lane * 4;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -554,7 +543,7 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
         bx_fetch(tl, gm, t + 2, ntiles);
         float p[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) p[r] = (BX_ABLATE & 32) ? tt[r] * 1e-3f : fast_exp2(__builtin_fmaf(tt[r], a2, -lse2));
+        for (int r = 0; r < 16; ++r) p[r] = fast_exp2(__builtin_fmaf(tt[r], a2, -lse2));
 
         // ---- dP' = V(t) . dO' ---------------------------------------------------------------------------------------
         f32x16 dp0;          // ONE accumulator for the three terms (round 6, as corr_fused_fwd_f16x3.hip's QK1: the kernel is VALU-bound)
@@ -572,11 +561,9 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
                     ah[nxt] = *reinterpret_cast<const f16x8*>(vb0 + (u + 1) * 16);
                     if (!VLO0 || u + 1 < 2) al[nxt] = *reinterpret_cast<const f16x8*>(vb0 + VPLANE + (u + 1) * 16);
                 }
-                if (!(BX_ABLATE & 8)) {
-                    dp0 = bx_mfma(ah[cur], goh[u], dp0);
-                    dp0 = bx_mfma(ah[cur], gol[u], dp0);
-                    if (!VLO0 || u < 2) dp0 = bx_mfma(al[cur], goh[u], dp0);
-                }
+                dp0 = bx_mfma(ah[cur], goh[u], dp0);
+                dp0 = bx_mfma(ah[cur], gol[u], dp0);
+                if (!VLO0 || u < 2) dp0 = bx_mfma(al[cur], goh[u], dp0);
                 if (u < 2 * VPT) {
                     commit_v_piece(u, buf ^ 1);
                     fetch_v_piece(u, j0 + 64);
@@ -604,7 +591,7 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
         // has already written (one G for all passes over this T: one box adjoint + one pair of GEMMs)
         if (gm.xt) bx_transpose32(gv, gm.xt, h, c);
         const unsigned blk = (unsigned)((gm.xt ? gm.qblk * gm.nqblk + t : t * gm.nqblk + gm.qblk) * 4096);
-        if (accumulate && !(BX_ABLATE & 2)) {
+        if (accumulate) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 old = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(G_rs, (int)gm.lane_off,
@@ -618,16 +605,14 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
             gout[r >> 2][r & 3] = gv[r];
             gabs = fmaxf(gabs, fabsf(gv[r]));
         }
-        if (!(BX_ABLATE & 2)) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, gout[g]), G_rs, (int)gm.lane_off,
-                                                       (int)(blk + (unsigned)g * 1024u), 2);      // nt: a stream for K20
-            // (a 16-byte store whose soffset is a REGISTER: LLVM models no write-after-read hazard on its data registers,
-            //  gfx950 has one — corr_fused_fwd_f16x3.hip, round 4.  Keep the four quads untouched for a few cycles.)
-            asm volatile("s_nop 4" : : "v"(gout[0]), "v"(gout[1]), "v"(gout[2]), "v"(gout[3]));
-        }
-        if (STORE_P && !(BX_ABLATE & 2)) {
+        for (int g = 0; g < 4; ++g)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, gout[g]), G_rs, (int)gm.lane_off,
+                                                   (int)(blk + (unsigned)g * 1024u), 2);      // nt: a stream for K20
+        // (a 16-byte store whose soffset is a REGISTER: LLVM models no write-after-read hazard on its data registers,
+        //  gfx950 has one — corr_fused_fwd_f16x3.hip, round 4.  Keep the four quads untouched for a few cycles.)
+        asm volatile("s_nop 4" : : "v"(gout[0]), "v"(gout[1]), "v"(gout[2]), "v"(gout[3]));
+        if (STORE_P) {
             // planes of 2^14 P in the accumulator's own orientation: [Nq/32][Nk/32] blocks of 2 x [32 queries][16 keys]
             // (corr_fused_bwd_f16x3.hip, store_regs_blk; read by hgemm_f16x3 with b_blocked = 2)
             unsigned hw[8], lw[8];
@@ -651,14 +636,12 @@ __device__ __forceinline__ void box3_sw_bwd_body(COCOS_BXB_PARAMS) {
                 __builtin_amdgcn_raw_buffer_store_b128(xl, pl_rs, (int)off, 0, 2);
             }
         }
-        if (!(BX_ABLATE & 1)) {
-            // (slot of tile t - 2 was read by every wave before it passed the barrier of tile t - 1)
-            float* a = colacc + buf * 4 * 2048 + wave * 2048 + lane * 4;
+        // (slot of tile t - 2 was read by every wave before it passed the barrier of tile t - 1)
+        float* a = colacc + buf * 4 * 2048 + wave * 2048 + lane * 4;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                *reinterpret_cast<f32x4*>(a + g * 256) = f32x4{x1[4 * g], x1[4 * g + 1], x1[4 * g + 2], x1[4 * g + 3]};
-                *reinterpret_cast<f32x4*>(a + 1024 + g * 256) = f32x4{x2[4 * g], x2[4 * g + 1], x2[4 * g + 2], x2[4 * g + 3]};
-            }
+        for (int g = 0; g < 4; ++g) {
+            *reinterpret_cast<f32x4*>(a + g * 256) = f32x4{x1[4 * g], x1[4 * g + 1], x1[4 * g + 2], x1[4 * g + 3]};
+            *reinterpret_cast<f32x4*>(a + 1024 + g * 256) = f32x4{x2[4 * g], x2[4 * g + 1], x2[4 * g + 2], x2[4 * g + 3]};
         }
         __syncthreads();
     };

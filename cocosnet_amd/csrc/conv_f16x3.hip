@@ -34,27 +34,12 @@
 // sched_group_barrier pipeline; ~2*M*N*K useful FLOPs, x3 issued.  Compile-time knobs below = measured experiments
 // (DESIGN.md section 3.3), the defaults are what shipped.
 #include "common.h"
-#include <cstdlib>
 #include <type_traits>
 
-#ifndef COCOS_CONV_SCHED_N
-#define COCOS_CONV_SCHED_N 6    // non-MFMA instructions handed out per MFMA gap (4..8 measured equal; pinning the staging
-#endif                          // pieces after each group of 6 MFMAs instead: 0.491 vs 0.470 ms on the 407-channel block)
-#ifndef COCOS_CONV_WGRAD_PIPE
-#define COCOS_CONV_WGRAD_PIPE 0  // weight gradient: 1 = the forward kernel's step shape (mid barrier, fragments half a step ahead, one stage):
-                                // measured neutral (1.591 vs 1.582 ms fwd+bwd) and it spills, so 0 = barrier at the end, two stages
-#endif
-#ifndef COCOS_CONV_OCC2
-#define COCOS_CONV_OCC2 1       // 128-row tiles: two workgroups per CU (2 waves per SIMD, 80 KB of LDS each)
-#endif
-#ifndef COCOS_CONV_STAGES
-#define COCOS_CONV_STAGES 0     // 0: per tile shape (see conv_fwd_kernel); 1 | 2: forced (timing experiments)
-#endif
-#ifndef COCOS_CONV_ABLATE
-#define COCOS_CONV_ABLATE 0     // timing experiments only (tools/build_conv_ablations.sh): 1 no gather loads, 2 no weight
-#endif                          // loads, 4 no LDS commit, 8 no MFMA
-
 namespace cocos {
+
+constexpr int kConvSchedN = 6;  // non-MFMA instructions handed out per MFMA gap (4..8 measured equal; pinning the staging
+                                // pieces after each group of 6 MFMAs instead: 0.491 vs 0.470 ms on the 407-channel block)
 
 // Optional phase timing (build with COCOS_EXTRA_HIPFLAGS=-DCOCOS_DEBUG_TIMING): shader-clock cycles spent by thread 0 of
 // workgroup 0 in the two halves of a forward step and at its barrier — cocos_debug_read_timing_conv().
@@ -161,7 +146,7 @@ __device__ __forceinline__ f32x4 buf_load4s(__amdgpu_buffer_rsrc_t r, unsigned b
 // >= 0 (the step offset travels in the scalar offset, which the hardware does not range-check): nothing below X is ever
 // dereferenced — a lane whose window corner lies outside the image is masked to the out-of-range offset.
 template <int BM, int BN, bool FAST4, bool ONE = false>
-__global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void conv_fwd_kernel(const float* __restrict__ X, const _Float16* __restrict__ wh,
+__global__ __launch_bounds__(256, BM == 128 ? 2 : 1) void conv_fwd_kernel(const float* __restrict__ X, const _Float16* __restrict__ wh,
                                                           const _Float16* __restrict__ wl,
                                                           const float* __restrict__ w_scale, const float* __restrict__ x_amax,
                                                           const float* __restrict__ bias, float* __restrict__ Y, int M,
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
     constexpr int MI = BM / 64, NJ = BN / 64;          // 32 x 32 blocks of a wave's tile (waves as 2 x 2)
     // register stages: ONE (a tile fetched under the second half of step t is committed under the first half of step
     // t+1); two measured slower once the fragments were double-buffered (0.455 vs 0.442 ms: register spills)
-    constexpr int STAGES = COCOS_CONV_STAGES ? COCOS_CONV_STAGES : 1;
+    constexpr int STAGES = 1;
     constexpr int LPR = BN / 4;                        // lanes per k row of the gathered tile (4 positions each)
     constexpr int RPP = 256 / LPR;                     // k rows per pass of the 256 threads
     constexpr int NP = CV_BK / RPP;                    // gathered pieces per thread (4 | 8)
@@ -243,7 +228,6 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
     bool f_rowok[NC];
     auto fetch_begin = [&](Stage& S, int tt) {
         tt = min(tt, nkb - 1);                         // prefetches beyond the end re-read the last tile (never used)
-        if (COCOS_CONV_ABLATE & 16) tt = 0;            // timing experiment: every step re-reads tile 0 (cache-hot loads)
         f_cb = cv_div(tt, g.mT);                       // k-block tt = 32 channels f_cb*32.. at tap tt % T
         const int tap = tt - f_cb * (g.KH * g.KW);
         f_ky = cv_div(tap, g.mKW);
@@ -262,16 +246,10 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
         }
     };
     auto fetch_a = [&](Stage& S, int u) {
-        if (COCOS_CONV_ABLATE & 2) { S.a[0][u] = S.a[1][u] = u32x4{f_soffa, 0u, 0u, 0u}; return; }
         S.a[0][u] = __builtin_amdgcn_raw_buffer_load_b128(wh_rs, (int)voffa[u], (int)f_soffa, 0);
         if (!ONE) S.a[1][u] = __builtin_amdgcn_raw_buffer_load_b128(wl_rs, (int)voffa[u], (int)f_soffa, 0);
     };
     auto fetch_g = [&](Stage& S, int u, auto edge_tag) __attribute__((always_inline)) {
-        if (COCOS_CONV_ABLATE & 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) S.gv[u][e] = (float)(f_soff + u + e) * 1e-9f;
-            return;
-        }
         const bool chanok = rowlane[u] + f_cb * 32 < g.Cin;
         if (FAST4) {
             const bool ok = chanok && f_rowok[0];
@@ -297,14 +275,12 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
         }
     };
     auto commit_a = [&](const Stage& S, int buf, int u) {
-        if (COCOS_CONV_ABLATE & 4) return;
         _Float16* ab = at + buf * 2 * APLANE;
         const int idx = u * 256 + tid, row = idx >> 2, kc = idx & 3;
         *reinterpret_cast<u32x4*>(ab + row * CV_AROW + kc * 8) = S.a[0][u];
         if (!ONE) *reinterpret_cast<u32x4*>(ab + APLANE + row * CV_AROW + kc * 8) = S.a[1][u];
     };
     auto commit_g = [&](Stage& S, int buf, int u) {
-        if (COCOS_CONV_ABLATE & 4) return;
         _Float16* gb = gt + buf * 2 * GPLANE;
         if (FAST4) {
 #pragma unroll
@@ -383,29 +359,25 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             CPH_T(tsa);
-            if (!(COCOS_CONV_ABLATE & 8)) {
-                if (s == 0) read_frags(buf, 1); else read_frags(buf ^ 1, 0);
-            }
+            if (s == 0) read_frags(buf, 1); else read_frags(buf ^ 1, 0);
             if (s == 1) fetch_begin(S, t + 1 + STAGES);
             // program order: the fragment reads, then per row block its MFMAs followed by a slice of the staging work
             // (first half: commits, second half: fetches); the pipeline below then hands the non-MFMA instructions out in
             // that order, a few per MFMA.  (Measured: all loads first, then reads, then MFMAs: 0.499 instead of 0.442 ms.)
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                if (!(COCOS_CONV_ABLATE & 8)) {
-                    // term-major: two MFMAs on the same accumulator are never neighbours (an instruction issued between
-                    // two dependent MFMAs costs a ~43-cycle bubble on gfx950; between independent ones ~6)
-                    if (ONE) {
+                // term-major: two MFMAs on the same accumulator are never neighbours (an instruction issued between
+                // two dependent MFMAs costs a ~43-cycle bubble on gfx950; between independent ones ~6)
+                if (ONE) {
 #pragma unroll
-                        for (int j = 0; j < NJ; ++j) acc[i][j] = cv_mfma_bf16(fah[s][i], fbh[s][j], acc[i][j]);
-                    } else {
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = cv_mfma_bf16(fah[s][i], fbh[s][j], acc[i][j]);
+                } else {
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[s][i], fbh[s][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[s][i], fbh[s][j], acc[i][j], 0, 0, 0);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[s][i], fbl[s][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[s][i], fbl[s][j], acc[i][j], 0, 0, 0);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fal[s][i], fbh[s][j], acc[i][j], 0, 0, 0);
-                    }
+                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fal[s][i], fbh[s][j], acc[i][j], 0, 0, 0);
                 }
                 if (s == 0) {
                     commit_a(S, buf ^ 1, i);
@@ -417,14 +389,12 @@ __global__ __launch_bounds__(256, (BM == 128 && COCOS_CONV_OCC2) ? 2 : 1) void c
                     for (int q = 0; q < GPS; ++q) fetch_g(S, i * GPS + q, edge_tag);
                 }
             }
-            if (!(COCOS_CONV_ABLATE & 8)) {
-                // one MFMA, then up to COCOS_CONV_SCHED_N instructions of any other kind (a wave that owns its SIMD issues
-                // about one instruction per 4-5 cycles: ~7 fit beside a 32-cycle MFMA)
+            // one MFMA, then up to kConvSchedN instructions of any other kind (a wave that owns its SIMD issues
+            // about one instruction per 4-5 cycles: ~7 fit beside a 32-cycle MFMA)
 #pragma unroll
-                for (int q = 0; q < (ONE ? 1 : 3) * MI * NJ; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, ONE ? 3 * COCOS_CONV_SCHED_N : COCOS_CONV_SCHED_N, 0);
-                }
+            for (int q = 0; q < (ONE ? 1 : 3) * MI * NJ; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, ONE ? 3 * kConvSchedN : kConvSchedN, 0);
             }
             CPH_T(tsb);
             CPH_ADD(s, tsa, tsb);
@@ -540,7 +510,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(const float* __restr
     }
 
     struct Stage { float a[APT][4]; float gv[4][4]; int xs[4]; };
-    Stage st[COCOS_CONV_WGRAD_PIPE ? 1 : 2];
+    Stage st[2];
     constexpr int NC = FAST4 ? 1 : 4;
     Corner f_cr[NC];
     bool f_live[NC];
@@ -640,12 +610,12 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(const float* __restr
     };
 
     const int nsteps = (max(nend - nbeg, 0) + CV_BK - 1) / CV_BK;
-    constexpr int WSTAGES = COCOS_CONV_WGRAD_PIPE ? 1 : 2;
+    constexpr int WSTAGES = 2;
     // positions at or beyond nend are masked (f_live), so prefetches past the last step are harmless
     fetch_all(st[0], nbeg);
     commit_all(st[0], 0);
     fetch_all(st[0], nbeg + CV_BK);
-    if (WSTAGES == 2) fetch_all(st[1], nbeg + 2 * CV_BK);
+    fetch_all(st[1], nbeg + 2 * CV_BK);
     __syncthreads();
 
     f16x8 fah[2][MI], fal[2][MI], fbh[2][2], fbl[2][2];
@@ -663,17 +633,14 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(const float* __restr
             if (!ONE) fal[s][i] = *reinterpret_cast<const f16x8*>(ab + APLANE + i * 32 * CV_AROW + s * 16);
         }
     };
-    // same step shape as the forward kernel: one barrier in the middle, fragments read half a step ahead, the staged
-    // tile committed under the first half and the next one fetched under the second
+    // each half step reads its own fragments; the staged tile is committed under the first half and the next one fetched
+    // under the second; one barrier at the end of the step, two register stages.  (The forward kernel's step shape — a
+    // barrier in the middle, fragments half a step ahead, one stage — measured neutral, 1.591 vs 1.582 ms fwd+bwd, and spilled.)
     auto step = [&](int t, Stage& S, auto edge_tag) __attribute__((always_inline)) {
         const int buf = t & 1;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            if (COCOS_CONV_WGRAD_PIPE) {
-                if (s == 0) read_frags(buf, 1); else read_frags(buf ^ 1, 0);
-            } else {
-                read_frags(buf, s);
-            }
+            read_frags(buf, s);
             if (s == 1) fetch_begin(nbeg + (t + 1 + WSTAGES) * CV_BK);
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
@@ -703,13 +670,12 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(const float* __restr
 #pragma unroll
             for (int q = 0; q < (ONE ? 2 : 6) * MI; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, ONE ? 3 * COCOS_CONV_SCHED_N : COCOS_CONV_SCHED_N, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, ONE ? 3 * kConvSchedN : kConvSchedN, 0);
             }
-            if (COCOS_CONV_WGRAD_PIPE ? s == 0 : s == 1) __syncthreads();
+            if (s == 1) __syncthreads();
         }
     };
     auto run = [&](auto edge_tag) __attribute__((always_inline)) {
-        if (COCOS_CONV_WGRAD_PIPE) read_frags(0, 0);
         int t = 0;
         for (; t + 1 < nsteps; t += 2) {
             step(t, st[0], edge_tag);
@@ -785,31 +751,26 @@ static int conv_fwd_launch(const cocos::ConvGeom& g, const float* x, const void*
                   "conv2d_fwd_f16x3: weight planes must be 16-byte aligned");
     const bool one = w_lo == nullptr;            // single bf16 plane: the one-term flavour
     const bool fast4 = g.stride == 1;
-    // tile: BM = 256 rows for wide layers, BN = 128 positions.  The 256 x 256 tile (wave tile 128 x 128: each LDS operand
-    // is re-read half as often per MFMA, all 256 accumulator registers in use, one register stage) exists and is
-    // tested, but measured no faster on the 407-channel block (0.466 vs 0.470 ms) and slower on its input gradient
-    // (fewer, longer workgroups): COCOS_CONV_BN=256 selects it for experiments.
-    const char* force_bm = getenv("COCOS_CONV_BM");
-    const int bm = (force_bm && atoi(force_bm) == 128) ? 128 : (Cout > 128 ? 256 : 128);
+    // tile: BM = 256 rows for wide layers, BN = 128 positions.  A 256 x 256 tile (wave tile 128 x 128: each LDS operand
+    // re-read half as often per MFMA, all 256 accumulator registers in use, one register stage) measured no faster on the
+    // 407-channel block (0.466 vs 0.470 ms) and slower on its input gradient (fewer, longer workgroups).
+    const int bm = Cout > 128 ? 256 : 128;
     const long long mt = (Cout + bm - 1) / bm;
-    const char* force = getenv("COCOS_CONV_BN");
-    const int bn = (force && atoi(force) == 256 && bm == 256) ? 256 : 128;
-    const long long blocks = mt * ((g.Ntot + bn - 1) / bn);
+    const long long blocks = mt * ((g.Ntot + 127) / 128);
     COCOS_REQUIRE(blocks <= 0x7fffffffLL, COCOS_ERR_UNSUPPORTED, "conv2d_fwd_f16x3: grid too large");
     hipStream_t s = as_stream(stream);
-#define COCOS_GO(BMv, BNv, F4) do { if (one && BNv == 128) COCOS_GO1(BMv, 128, F4, true); else COCOS_GO1(BMv, BNv, F4, false); } while (0)
-#define COCOS_GO1(BMv, BNv, F4, ONEv)                                                                              \
+#define COCOS_GO(BMv, F4) do { if (one) COCOS_GO1(BMv, F4, true); else COCOS_GO1(BMv, F4, false); } while (0)
+#define COCOS_GO1(BMv, F4, ONEv)                                                                                   \
     do {                                                                                                           \
-        auto kern = conv_fwd_kernel<BMv, BNv, F4, ONEv>;                                                           \
-        const size_t smem = (size_t)2 * 2 * (BMv * CV_AROW + CV_BK * (BNv + 32)) * sizeof(_Float16);               \
+        auto kern = conv_fwd_kernel<BMv, 128, F4, ONEv>;                                                           \
+        const size_t smem = (size_t)2 * 2 * (BMv * CV_AROW + CV_BK * (128 + 32)) * sizeof(_Float16);               \
         COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                   \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));              \
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), smem, s, x, static_cast<const _Float16*>(w_hi), \
                            static_cast<const _Float16*>(w_lo), w_scale_dev, x_amax_dev, bias, y, Cout, g);         \
     } while (0)
-    if (bm == 256 && bn == 256 && !one) { if (fast4) COCOS_GO(256, 256, true); else COCOS_GO(256, 256, false); }
-    else if (bm == 256)         { if (fast4) COCOS_GO(256, 128, true); else COCOS_GO(256, 128, false); }
-    else                        { if (fast4) COCOS_GO(128, 128, true); else COCOS_GO(128, 128, false); }
+    if (bm == 256) { if (fast4) COCOS_GO(256, true); else COCOS_GO(256, false); }
+    else           { if (fast4) COCOS_GO(128, true); else COCOS_GO(128, false); }
 #undef COCOS_GO
 #undef COCOS_GO1
     COCOS_HIP_CHECK(hipGetLastError());

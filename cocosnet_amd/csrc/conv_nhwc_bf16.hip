@@ -791,12 +791,10 @@ static int cocos_nhwc_gemm_impl(const void* xp, const void* w_hi, const void* w_
     if (bm == 128) {
         if (bn == 256) COCOS_NHWC_GO(128, 256); else COCOS_NHWC_GO(128, 128);
     } else if (bn == 256) {
-        static const bool w8 = [] { const char* e = getenv("COCOS_CONV_NHWC_WAVES"); return !(e && e[0] == '4'); }();
         if (split && sk) COCOS_NHWC_GO_W(256, 256, true, 4, 3);
         else if (split) COCOS_NHWC_GO_W(256, 256, false, 4, 3);
         else if (sk) COCOS_NHWC_GO_W(256, 256, true, 4, 1);
-        else if (w8) COCOS_NHWC_GO_W(256, 256, false, 8, 1);
-        else COCOS_NHWC_GO_W(256, 256, false, 4, 1);
+        else COCOS_NHWC_GO_W(256, 256, false, 8, 1);
     } else {
         COCOS_NHWC_GO(256, 128);
     }

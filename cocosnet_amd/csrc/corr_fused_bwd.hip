@@ -19,18 +19,6 @@
 // resident-side gradients accumulate in registers with no atomics; two kernels, deterministic.
 #include "common.h"
 
-// sched_group_barrier pins (per loop, so they can be ablated at compile time)
-#ifndef COCOS_SGB_S
-#define COCOS_SGB_S 1
-#endif
-#ifndef COCOS_SGB_DP
-#define COCOS_SGB_DP 1
-#endif
-#ifndef COCOS_SGB_DX
-#define COCOS_SGB_DX 1
-#endif
-#define SGB(en, mask, n) do { if (en) __builtin_amdgcn_sched_group_barrier(mask, n, 0); } while (0)
-
 namespace cocos {
 
 constexpr int BWD_BR = 128;   // resident positions per workgroup
@@ -173,7 +161,7 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
             float a[2][NB];
 #pragma unroll
             for (int u = 0; u < NB; ++u) a[0][u] = xl[(2 * u) * BWD_LD];
-            SGB(COCOS_SGB_S, 0x100, NB / 2);
+            __builtin_amdgcn_sched_group_barrier(0x100, NB / 2, 0);
 #pragma unroll
             for (int bt = 0; bt < NBATCH; ++bt) {
                 if (bt + 1 < NBATCH) {
@@ -185,10 +173,10 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
                 for (int u = 0; u < NB; ++u) s = mfma32(a[bt & 1][u], xreg[bt * NB + u], s);
 #pragma unroll
                 for (int u = 0; u < NB / 2; ++u) {
-                    SGB(COCOS_SGB_S, 0x008, 2);
-                    SGB(COCOS_SGB_S, 0x100, 1);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
-                if (COCOS_SGB_S) __builtin_amdgcn_sched_barrier(0);   // one region per batch
+                __builtin_amdgcn_sched_barrier(0);   // one region per batch
             }
         }
 
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
                 a[0][u] = cl[(2 * u) * BWD_LD];
                 bb[0][u] = rl[(2 * u) * BWD_BR];
             }
-            SGB(COCOS_SGB_DP, 0x100, NB + NB / 2);
+            __builtin_amdgcn_sched_group_barrier(0x100, NB + NB / 2, 0);
 #pragma unroll
             for (int bt = 0; bt < NBATCH; ++bt) {
                 if (bt + 1 < NBATCH) {
@@ -220,10 +208,10 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
                 for (int u = 0; u < NB; ++u) dp = mfma32(a[bt & 1][u], bb[bt & 1][u], dp);
 #pragma unroll
                 for (int u = 0; u < NB / 2; ++u) {
-                    SGB(COCOS_SGB_DP, 0x008, 2);
-                    SGB(COCOS_SGB_DP, 0x100, 3);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 }
-                if (COCOS_SGB_DP) __builtin_amdgcn_sched_barrier(0);   // one region per batch
+                __builtin_amdgcn_sched_barrier(0);   // one region per batch
             }
         }
 
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
             for (int kb = 0; kb < KB; ++kb) xa[0][kb] = xl[kb * 32 * BWD_LD + acc_row_base(0)];
 #pragma unroll
             for (int cb = 0; cb < NC; ++cb) ca[0][cb] = cl[cb * 32 * BWD_LD + acc_row_base(0)];
-            if (COCOS_SGB_DX) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (r + 1 < 16) {
@@ -280,11 +268,11 @@ __global__ __launch_bounds__(256, 1) void corr_bwd_kernel(
                 // coarse pin (a 1:1 MFMA/read pattern over these 16 x (KB+NC) pairs sends hipcc's
                 // group solver into minutes of compile time): half of this step's MFMAs, then ALL
                 // reads of the next step, then the other half -> every read leads its use by >= 4 MFMAs
-                SGB(COCOS_SGB_DX, 0x008, (KB + NC) / 2);
-                SGB(COCOS_SGB_DX, 0x100, KB + NC);
-                SGB(COCOS_SGB_DX, 0x008, (KB + NC) - (KB + NC) / 2);
+                __builtin_amdgcn_sched_group_barrier(0x008, (KB + NC) / 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, KB + NC, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, (KB + NC) - (KB + NC) / 2, 0);
                 // one scheduling region per step keeps the group solver's work linear
-                if (COCOS_SGB_DX) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
     }

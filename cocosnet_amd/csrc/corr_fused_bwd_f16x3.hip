@@ -50,21 +50,9 @@ __device__ __forceinline__ u32x4 bq_load16s(__amdgpu_buffer_rsrc_t r, unsigned o
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, (int)soff, 0);
 }
 
-// Ablation builds (debug only, results are WRONG): -DCOCOS_ABLATE=<bits>  1: no tile staging, 2: no operand re-reads
-// from LDS, 4: no exp/split arithmetic, 8: no dS'' transposition + plane stores, 16: no logits loads
-// Projection of a FUSED key side ("accumulate dkn in the same kernel"; round 3): 1024: the 48 extra MFMAs
-// per wave tile that dkn_tile[256 x 32 keys] += Q_wave . dS''^T would issue (on the dqn accumulators: no registers are left
-// for a second 128-register accumulator set, which is the first obstacle); 2048: its output traffic — the wave's 256 x 32
-// fp32 partial tile leaving as 128 atomic adds per lane and tile (32 KB per wave tile; with 8 + 2048 the dS'' stores it
-// would replace are removed).  Not modelled and still owed by a real variant: the transposition of dS'' through LDS that
-// the product needs (the contraction runs over QUERIES, which sit in the lanes of this kernel's tiles — an MFMA never
-// contracts over the lane index), measured at +4.4 % of the kernel when the planes still left through it.
-#ifndef COCOS_ABLATE
-#define COCOS_ABLATE 0
-#endif
 // cache policy of the HWxHW streams (saved logits, dS'' / P planes): written once, read once by another kernel — `nt`
 // (aux bit 1) keeps them from evicting the key/value tiles that the 32 workgroups of a sample share in their XCD's L2
-#define COCOS_STREAM_AUX ((COCOS_ABLATE & 256) ? 0 : 2)
+constexpr int kStreamAux = 2;
 #ifdef COCOS_DEBUG_TIMING
 __device__ long long g_phase_bq_h[8];
 #define BPH_T(var) const long long var = __builtin_readcyclecounter()
@@ -321,23 +309,21 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
         dm = (th - m_raw) + (tl - m_raw_lo);              // both maxima are fp32 numbers a few ulps apart: exact differences
     };
     auto load_s = [&](f32x4& dst, int tt, int k) {
-        if ((COCOS_ABLATE & 16) && tt > 1) return;
-        const int tc = (COCOS_ABLATE & 128) ? (tt & 1) : min(tt, ntiles - 1);
+        const int tc = min(tt, ntiles - 1);
         dst = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            lg_rs, (int)lg_lane_off, (int)((unsigned)(tc * nqblk) * 4096u + (unsigned)k * 1024u), COCOS_STREAM_AUX));
+            lg_rs, (int)lg_lane_off, (int)((unsigned)(tc * nqblk) * 4096u + (unsigned)k * 1024u), kStreamAux));
     };
 
     // one staged piece of the V tile (i < 2*VPT) or of the K tile (2*VPT <= i < 2*VPT + 8) to LDS, and the reload of
     // its register with the tile after: V(tv) -> vt[bufv], then V(tv + 1) requested; K(tk) -> kt[bufk], then K(tk + 1)
     auto stage_piece = [&](int i, int tv, int tk, auto piece_tag) __attribute__((always_inline)) {
-        constexpr bool PLO0 = decltype(piece_tag)::value || (COCOS_ABLATE & 512);   // lo plane of value channels >= 32 is zero: not fetched
-        if (COCOS_ABLATE & 1) return;
+        constexpr bool PLO0 = decltype(piece_tag)::value;   // lo plane of value channels >= 32 is zero: not fetched
         _Float16* const vw = vt + (tv & 1) * 2 * VPLANE;
         _Float16* const kw = kt + (tk & 1) * 2 * KPLANE;
         if (i < 2 * VPT) {
             const int pl_ = i & 1, u = i >> 1;
             if (!RAGGED) {
-                const int jn = (COCOS_ABLATE & 64) ? 32 : min((tv + 1) * 32, Nk - 32);
+                const int jn = min((tv + 1) * 32, Nk - 32);
                 if (u * 256 + 255 < VCH || u * 256 + tid < VCH)
                     *reinterpret_cast<u32x4*>(vw + pl_ * VPLANE + v_lds[u]) = vst[pl_][u];
                 vst[pl_][u] = bq_load16s(pl_ ? vl_rs : vh_rs,
@@ -353,7 +339,7 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
         } else if (i - 2 * VPT < 8) {
             const int pl_ = (i - 2 * VPT) & 1, u = (i - 2 * VPT) >> 1;
             if (!RAGGED) {
-                const int jn = (COCOS_ABLATE & 64) ? 32 : min((tk + 1) * 32, Nk - 32);
+                const int jn = min((tk + 1) * 32, Nk - 32);
                 _Float16* d = kw + pl_ * KPLANE + k_lds[u];
                 *reinterpret_cast<u32x2*>(d) = u32x2{kst[pl_][u].x, kst[pl_][u].y};
                 *reinterpret_cast<u32x2*>(d + 8) = u32x2{kst[pl_][u].z, kst[pl_][u].w};
@@ -384,7 +370,6 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
     // VLO0 (uniform, see the forward kernel): only value block 0 has a non-zero lo plane — the V_lo * dO_hi term, its
     // fragment reads and the fetch of those lo channels are skipped for the other blocks (8 of 30 MFMAs, same result)
     auto phase_dp = [&](f32x16& dp0, int t) __attribute__((always_inline)) {
-        constexpr bool SKIPLO = VLO0 || (COCOS_ABLATE & 512);
         // (round 6: the accumulator STARTS at -D' — the subtraction of dS'' = P (dP' - D') rides in the initialisation the chain needs
         //  anyway: 16 VALU instructions per tile fewer in a kernel that is bound by them)
 #pragma unroll
@@ -398,13 +383,13 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
 #pragma unroll
         for (int u = 0; u < CVS; ++u) {
             const int cur = u & 1, nxt = cur ^ 1;
-            if (!(COCOS_ABLATE & 2) && u + 1 < CVS) {
+            if (u + 1 < CVS) {
                 ah[nxt] = *reinterpret_cast<const f16x8*>(vb0 + (u + 1) * 16);
-                if (!SKIPLO || u + 1 < 2) al[nxt] = *reinterpret_cast<const f16x8*>(vb0 + VPLANE + (u + 1) * 16);
+                if (!VLO0 || u + 1 < 2) al[nxt] = *reinterpret_cast<const f16x8*>(vb0 + VPLANE + (u + 1) * 16);
             }
             dp0 = bq_mfma(ah[cur], goh[u], dp0);
             dp0 = bq_mfma(ah[cur], gol[u], dp0);
-            if (!SKIPLO || u < 2) dp0 = bq_mfma(al[cur], goh[u], dp0);
+            if (!VLO0 || u < 2) dp0 = bq_mfma(al[cur], goh[u], dp0);
 #pragma unroll
             for (int q = 0; q < PER; ++q)
                 if (u * PER + q < NP) stage_piece(u * PER + q, t + 1, t, vlo0_tag);
@@ -431,8 +416,7 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
     // ---- VALU slice r of tile t: dS''[r] from logit register r; pairs are split to f16 hi/lo at odd r ----------
     auto valu_slice = [&](int r, int t, const f32x4 (&s)[4], float dm, const f32x16& dp0, float (&dsv)[2], float (&pv)[2],
                           DsRegs& out, DsRegs& pout) {
-        float pc = (COCOS_ABLATE & 4) ? s[r >> 2][r & 3] * 1e-9f
-                                      : fast_exp2(__builtin_fmaf(RAWM ? s[r >> 2][r & 3] + dm : s[r >> 2][r & 3], scale_log2, nlse2c));
+        float pc = fast_exp2(__builtin_fmaf(RAWM ? s[r >> 2][r & 3] + dm : s[r >> 2][r & 3], scale_log2, nlse2c));
         if (RAGGED && (t * 32 + acc_row_base(r) + 4 * h >= Nk)) pc = 0.f;
         dsv[r & 1] = pc * dp0[r];
         if (STORE_P) pv[r & 1] = pc * p_from_pc;
@@ -440,7 +424,7 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
             split_pair_rtz(dsv[0], dsv[1], out.hw[r >> 1], out.lw[r >> 1]);
             if (STORE_P) split_pair_rtz(pv[0], pv[1], pout.hw[r >> 1], pout.lw[r >> 1]);
         }
-        if (!BLK && STORE_DS && (r & 1) && !(COCOS_ABLATE & 8)) stage_transpose(r >> 1, out.hw[r >> 1], out.lw[r >> 1]);
+        if (!BLK && STORE_DS && (r & 1)) stage_transpose(r >> 1, out.hw[r >> 1], out.lw[r >> 1]);
     };
     // BLK: the planes are stored in the accumulator's own orientation, [query][key], as [Nq/32][Nk/32] blocks of
     // 2 x [32 queries][16 keys] halfs (2 KB; halves = keys 0..15 | 16..31 of the tile): lane (c, h) holds keys 8m + 4h .. +3 of query c in regs (2m, 2m+1); ONE
@@ -450,7 +434,6 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
     // fragments from this layout with ds_read_b64_tr_b16 (hgemm_f16x3.hip, b_blocked = 2).
     auto store_regs_blk = [&](int t, const DsRegs& d, __amdgpu_buffer_rsrc_t h_rs, __amdgpu_buffer_rsrc_t l_rs, int pp_lo = 0,
                               int pp_hi = 2) {
-        if (COCOS_ABLATE & 8) return;
         const unsigned blk = (unsigned)((((q0 >> 5) + wave) * (Nk >> 5) + t) * 2048);     // bytes: block (q-block, key tile t)
 #pragma unroll
         for (int pp = pp_lo; pp < pp_hi; ++pp) {         // group pairs (0,1) and (2,3)
@@ -464,16 +447,14 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
                 xl[i] = sl[0]; xl[2 + i] = sl[1];
             }
             // block = two 1 KB halves [pp][32 queries][16 keys]: each store instruction writes one half, contiguous
-            unsigned off = blk + (unsigned)(pp * 1024 + c * 32 + h * 16);
-            if (COCOS_ABLATE & 32) off = (unsigned)(lane * 16 + wave * 1024 + pp * 4096);
-            __builtin_amdgcn_raw_buffer_store_b128(xh, h_rs, (int)off, 0, COCOS_STREAM_AUX);
-            __builtin_amdgcn_raw_buffer_store_b128(xl, l_rs, (int)off, 0, COCOS_STREAM_AUX);
+            const unsigned off = blk + (unsigned)(pp * 1024 + c * 32 + h * 16);
+            __builtin_amdgcn_raw_buffer_store_b128(xh, h_rs, (int)off, 0, kStreamAux);
+            __builtin_amdgcn_raw_buffer_store_b128(xl, l_rs, (int)off, 0, kStreamAux);
         }
     };
     // !BLK: the wave's transposed 32x32 tile: LDS -> 16-byte row pieces of the row-major [Nk][Nq] planes
     auto store_planes = [&](int t, const DsRegs& d, __amdgpu_buffer_rsrc_t h_rs, __amdgpu_buffer_rsrc_t l_rs) {
         if (BLK) { store_regs_blk(t, d, h_rs, l_rs); return; }
-        if (COCOS_ABLATE & 8) return;
         // (LDS instructions of one wave execute in order: the 2-byte writes above are visible here)
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
@@ -481,10 +462,9 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
             const u32x4 xh = *reinterpret_cast<const u32x4*>(dstile + key * DSROW + qc);
             const u32x4 xl = *reinterpret_cast<const u32x4*>(dstile + DSPLANE + key * DSROW + qc);
             const int row = t * 32 + key, col = q0 + wave * 32 + qc;        // Nq % 8 == 0: whole pieces
-            unsigned off = (row < Nk && col < Nq) ? (unsigned)(row * Nq + col) * 2u : kBufOob;
-            if (COCOS_ABLATE & 32) off = (unsigned)(lane * 16 + wave * 1024 + pass * 4096);
-            __builtin_amdgcn_raw_buffer_store_b128(xh, h_rs, (int)off, 0, COCOS_STREAM_AUX);
-            __builtin_amdgcn_raw_buffer_store_b128(xl, l_rs, (int)off, 0, COCOS_STREAM_AUX);
+            const unsigned off = (row < Nk && col < Nq) ? (unsigned)(row * Nq + col) * 2u : kBufOob;
+            __builtin_amdgcn_raw_buffer_store_b128(xh, h_rs, (int)off, 0, kStreamAux);
+            __builtin_amdgcn_raw_buffer_store_b128(xl, l_rs, (int)off, 0, kStreamAux);
         }
     };
     auto store_p_tile = [&](int t, const DsRegs& pr) {
@@ -504,10 +484,8 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
     //      logit registers are consumed, the loads of tile t + 2's logits ride in the MFMA gaps.  STAGE_K: the key-tile
     //      pieces of tile t go to LDS (read from the next iteration on), one every other step ----------------------------
     constexpr int LEAD = 3;
-#ifndef BQ_STORE_I0
-#define BQ_STORE_I0 7        // dqn steps at which the two halves of the tile's planes are stored: slices 0..7 are done by step 4,
-#define BQ_STORE_I1 15       // slices 8..15 by step 12 (tuned: see DESIGN 5.0)
-#endif
+    constexpr int kBqStoreI0 = 7;       // dqn steps at which the two halves of the tile's planes are stored: slices 0..7 are done by step 4,
+    constexpr int kBqStoreI1 = 15;      // slices 8..15 by step 12 (tuned: see DESIGN 5.0)
     auto phase_dqn = [&](int t, const DsRegs& prev, auto with_valu, auto stage_k, f32x4 (&s)[4], float& dm, const f32x16& dp0,
                          DsRegs& cur, DsRegs& pcur) {
         constexpr bool WITH_VALU = decltype(with_valu)::value;
@@ -537,7 +515,7 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
 #pragma unroll
         for (int i = 0; i < 2 * KB; ++i) {                // i = tt * KB + kb
             const int tt = i / KB, kb = i % KB, cur_ = i & 1, nxt = cur_ ^ 1;
-            if (!(COCOS_ABLATE & 2) && i + 1 < 2 * KB) {
+            if (i + 1 < 2 * KB) {
                 const int t2 = (i + 1) / KB, k2 = (i + 1) % KB;
                 a_h[nxt] = *reinterpret_cast<const f16x8*>(kb0 + k2 * 32 * BQH_KROW + t2 * 16);
                 a_l[nxt] = *reinterpret_cast<const f16x8*>(kb0 + KPLANE + k2 * 32 * BQH_KROW + t2 * 16);
@@ -553,30 +531,17 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
             // with an L2-resident target (round-4 ablation), i.e. their issue, not HBM
             // (only when dS'' is the one plane set: with the P planes as well — cycle terms, the Attention block — four stores per
             //  position measured 1-2 % SLOWER than all eight at the end, same box, tools/bq_ab.py)
-            if (WITH_VALU && BLK && !STORE_P && (i == BQ_STORE_I0 || i == BQ_STORE_I1)) {
-                const int pp = i == BQ_STORE_I1 ? 1 : 0;
+            if (WITH_VALU && BLK && !STORE_P && (i == kBqStoreI0 || i == kBqStoreI1)) {
+                const int pp = i == kBqStoreI1 ? 1 : 0;
                 if (STORE_DS) store_regs_blk(t, cur, dh_rs, dl_rs, pp, pp + 1);
             }
             if (STAGE_K && (i & 1) == 0) stage_piece(2 * VPT + (i >> 1), t + 1, t, false_type{});
             if (WITH_VALU && i == 2 * KB - 1) prefetch_v(t + 1);         // first fragments of the next iteration's dP'
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (COCOS_ABLATE & 1024) {
-#pragma unroll
-            for (int i = 0; i < 2 * KB; ++i) {
-                dx[i % KB] = bq_mfma(a_h[i & 1], sh[i / KB], dx[i % KB]);
-                dx[i % KB] = bq_mfma(a_h[i & 1], sl[i / KB], dx[i % KB]);
-                dx[i % KB] = bq_mfma(a_l[i & 1], sh[i / KB], dx[i % KB]);
-            }
-        }
-        if ((COCOS_ABLATE & 2048) && live) {
-            float* base = dqn + (size_t)b * BQH_KD * Nq + (size_t)((t & 127) * 32) + c;      // a 256 x 32 tile somewhere in dqn[b]
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    atomicAdd(base + (size_t)(kb * 32 + acc_row_base(r) + 4 * h) * Nq, dx[kb][r]);
-        }
+        // (naming `live` here keeps this closure's layout — and with it hipcc's register allocation of the whole kernel: without
+        //  it the CVS = 5 instantiations spill 8 bytes.  No instruction comes of it.)
+        (void)live;
         // the dqn accumulators live in the accumulator file for the whole kernel (without the pins hipcc
         // rotates them through other AGPR ranges: 64 v_accvgpr_mov per tile)
 #pragma unroll
@@ -636,7 +601,7 @@ __device__ __forceinline__ void corr_bwd_query_f16x3_body(
         BPH_T(tp2);
         phase_dqn(t, prev, true_type{}, true_type{}, s, dm, dp0, cur, pcur);
         BPH_T(tp3);
-        if (!BLK || STORE_P || BQ_STORE_I0 > 15) {      // (else: the blocked dS'' planes were stored inside phase_dqn)
+        if (!BLK || STORE_P || kBqStoreI0 > 15) {      // (else: the blocked dS'' planes were stored inside phase_dqn)
             if (STORE_DS) store_planes(t, cur, dh_rs, dl_rs);
             if (STORE_P) store_p_tile(t, pcur);
         }

@@ -48,14 +48,11 @@ constexpr int SP_VROW = 40;              // halfs per channel row of the V tile:
 // sits at the TOP of f16's range, so that the truncation floor of the hi/lo split (2^-24 absolute, one-sided)
 // is 2^-33 relative to a row maximum — thousands of tail keys cannot bias a row sum by more than ~1e-7.
 // Numerator (O) and denominator (l) carry the same factor, which cancels in out = O / l.
-// Round 6 measured the trade behind these two (thr + bias = 15 is f16's range; -DCOCOS_RESCALE_THR=<t>): threshold 8 / 9 / 10 / 12 make
+// Round 6 measured the trade behind these two (thr + bias = 15 is f16's range): threshold 8 / 9 / 10 / 12 make
 // the forward 1.3 / 2.0 / 2.0 / 2.2 % faster (fewer 200-instruction rescales of O) and move the elementwise-relative floor of the soft
 // label map up by 2^(t - 6): at 9 the entries at 1e-8 leave the 1e-3 band (tests/test_gpu_mk3_sizes.py).  Kept at 6 / 9.
-#ifndef COCOS_RESCALE_THR
-#define COCOS_RESCALE_THR 6.0f
-#endif
-constexpr float kSplitRescaleThr = COCOS_RESCALE_THR;
-constexpr float kPBias = 15.0f - COCOS_RESCALE_THR;
+constexpr float kSplitRescaleThr = 6.0f;
+constexpr float kPBias = 15.0f - kSplitRescaleThr;
 
 __device__ __forceinline__ f32x16 mfma16h(f16x8 a, f16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
@@ -86,17 +83,11 @@ __device__ __forceinline__ void split_pair(float a, float b, f16x2& hi, f16x2& l
     lo = __builtin_bit_cast(f16x2, l);
 }
 
-// Optional phase timing (build with COCOS_EXTRA_HIPFLAGS=-DCOCOS_DEBUG_TIMING): shader-clock ticks spent by
-// wave 0 of workgroup 0 in each phase of the tile loop, read back with cocos_debug_read_timing_fwd_f16x3().
-// Ablation builds (debug only, results are WRONG): -DCOCOS_ABLATE=<bits>  1: no tile staging in the QK loop,
-// 2: no operand re-reads from LDS, 4: no softmax arithmetic, 8: no logits store, 512: V lo plane skipped for channel
-// blocks >= 1 (what exactly-representable label channels could save) — tools/ablate_ms.sh times them.
-#ifndef COCOS_ABLATE
-#define COCOS_ABLATE 0
-#endif
 // cache policy of the HWxHW streams (saved logits, dS'' / P planes): written once, read once by another kernel — `nt`
 // (aux bit 1) keeps them from evicting the key/value tiles that the 32 workgroups of a sample share in their XCD's L2
-#define COCOS_STREAM_AUX ((COCOS_ABLATE & 256) ? 0 : 2)
+constexpr int kStreamAux = 2;
+// Optional phase timing (build with COCOS_EXTRA_HIPFLAGS=-DCOCOS_DEBUG_TIMING): shader-clock ticks spent by
+// wave 0 of workgroup 0 in each phase of the tile loop, read back with cocos_debug_read_timing_fwd_f16x3().
 #ifdef COCOS_DEBUG_TIMING
 __device__ long long g_phase_fwd_h[8];
 #define FPH_T(var) const long long var = __builtin_readcyclecounter()
@@ -286,7 +277,7 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
     // ds_read_b128 takes several hundred cycles to come back, far more than the 96 cycles of one step's MFMAs.
     // The rings live ACROSS the tile loop: the first fragments of tile t+1's key tile are requested at the end of
     // tile t's P.V loop, so the QK loop never starts cold (round 1 / step 1 read them right after the barrier:
-    // ~450 cycles of every tile's QK phase were that bubble — tools/ablate_fwd.sh, profiles/r02_ablation_fwd.txt).
+    // ~450 cycles of every tile's QK phase were that bubble — profiles/r02_ablation_fwd.txt).
     constexpr int RA = 4, NS = SP_KD / 16;
     f16x8 ah[RA], al[RA];
     auto prefetch_k = [&](int buf) {
@@ -319,16 +310,15 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
         // issued in the QK loop; 8 <= i < 8 + 2*CVB: value-tile pieces, issued in the P.V loop.
         auto piece = [&](int i, auto vlo0_piece_tag) __attribute__((always_inline)) {
             constexpr bool PLO0 = decltype(vlo0_piece_tag)::value;     // value blocks >= 1 have an all-zero lo plane: not staged
-            if (COCOS_ABLATE & 1) return;
             if (!RAGGED) {
-                const int jc = (COCOS_ABLATE & 64) ? SP_BK : min(jn, Nk - SP_BK);       // look-ahead past the end re-reads the last tile
+                const int jc = min(jn, Nk - SP_BK);       // look-ahead past the end re-reads the last tile
                 if (i < 8) {
                     const int pl_ = i & 1, u = i >> 1;
                     *reinterpret_cast<u32x4*>(kw + pl_ * KPLANE + k_lds[u]) = kst[pl_][u];
                     kst[pl_][u] = buf_load_u4s(pl_ ? kl_rs : kh_rs, k_voff[u], (unsigned)jc * (unsigned)(SP_KD * 2));
                 } else if (i - 8 < 2 * CVB) {
                     const int pl_ = (i - 8) & 1, u = (i - 8) >> 1;
-                    if ((PLO0 || (COCOS_ABLATE & 512)) && pl_ == 1 && u >= 1) return;
+                    if (PLO0 && pl_ == 1 && u >= 1) return;
                     const bool ones = pl_ == 0 && u == CVB - 1 && ones_thread;
                     *reinterpret_cast<u32x2*>(vw + pl_ * VPLANE + v_lds[u]) = ones ? kOnes2 : vst[pl_][u];
                     if (pl_ == 0) *reinterpret_cast<u32x2*>(vw + 2 * VPLANE + v_lds[u]) = ones ? kOnesS2 : unshift2(vst[0][u]);
@@ -362,12 +352,8 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
         // QK1 (round 6): the three product terms accumulate into ONE register set — a dependent chain of v_mfma_f32_32x32x16_f16 issues at
         // the full rate on gfx950 (tools/probes/mfma_operand_rate.hip), and the kernel is bound by its VALU instructions, not by MFMA
         // dependencies: 32 accumulator reads and 16 packed adds fewer per tile, forward 0.311 -> 0.293 ms same box (tools/ab_libs.sh;
-        // -DCOCOS_QK_THREE_ACC restores the round-2 form).  The magnitude-free flavour keeps its two chains (they START at -m_hi / -m_lo).
-#ifdef COCOS_QK_THREE_ACC
-        constexpr bool QK1 = false;
-#else
+        // the round-2 form is in git history).  The magnitude-free flavour keeps its two chains (they START at -m_hi / -m_lo).
         constexpr bool QK1 = !RAWM;
-#endif
         f32x16 sa, sb, sc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sa[r] = RAWM ? -m_run : 0.f; sb[r] = RAWM ? -m_lo : 0.f; sc[r] = 0.f; }
@@ -378,10 +364,10 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
                 const int cur = s % RA;
                 const bool live = s < KST;      // (a compile-time fact after unrolling)
                 if (live) sa = mfma16h(ah[cur], qhr[s], sa);
-                if (!(COCOS_ABLATE & 2) && s + RA - 1 < KST) ah[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + (s + RA - 1) * 16);
+                if (s + RA - 1 < KST) ah[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + (s + RA - 1) * 16);
                 __builtin_amdgcn_sched_barrier(0);
                 if (live) { if (QK1) sa = mfma16h(ah[cur], qlr[s], sa); else sb = mfma16h(ah[cur], qlr[s], sb); }
-                if (!(COCOS_ABLATE & 2) && s + RA - 1 < KST) al[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + KPLANE + (s + RA - 1) * 16);
+                if (s + RA - 1 < KST) al[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + KPLANE + (s + RA - 1) * 16);
                 __builtin_amdgcn_sched_barrier(0);
                 if (live) { if (QK1) sa = mfma16h(al[cur], qhr[s], sa); else sc = mfma16h(al[cur], qhr[s], sc); }
                 if ((s & 1) == 0) piece(s >> 1, std::false_type{});   // the 8 key-tile pieces, every other step
@@ -452,9 +438,9 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
 #pragma unroll
             for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
         }
-        if (STORE_S && !(COCOS_ABLATE & 8)) {
+        if (STORE_S) {
             // the wave's 32x32 tile of raw logits: four contiguous 1 KB stores (registers 4k..4k+3 of every lane)
-            const unsigned soff = (COCOS_ABLATE & 32) ? 0u : (unsigned)(t * nqblk) * 4096u;
+            const unsigned soff = (unsigned)(t * nqblk) * 4096u;
             // RAWM: the saved logits are RELATIVE raw accumulators, s - m_tile, with m_tile (the row's running maximum when the
             // tile was stored, hi and lo part) in mtile[b][t][0..1][query]: the backward forms s_rel + (m_tile - m_final) — exact differences.  (Absolute
             // logits s_rel + m would be rounded at |m|: one ulp of 2^27 raw units is ~70 in the exponent at |logit| ~ 1e9, and
@@ -467,12 +453,12 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
             for (int k = 0; k < 4; ++k)
                 __builtin_amdgcn_raw_buffer_store_b128(
                     __builtin_bit_cast(u32x4, f32x4{s0[4 * k], s0[4 * k + 1], s0[4 * k + 2], s0[4 * k + 3]}), lg_rs,
-                    (int)lg_lane_off, (int)(soff + (unsigned)k * 1024u), COCOS_STREAM_AUX);
+                    (int)lg_lane_off, (int)(soff + (unsigned)k * 1024u), kStreamAux);
         }
         float p[16];
         const float nmb = RAWM ? kPBias : kPBias - m_run;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) p[r] = (COCOS_ABLATE & 4) ? s0[r] * 1e-3f + 1.0f : fast_exp2(__builtin_fmaf(s0[r], scale_log2, nmb));
+        for (int r = 0; r < 16; ++r) p[r] = fast_exp2(__builtin_fmaf(s0[r], scale_log2, nmb));
 
         FPH_T(tp3);
         // P -> f16 hi/lo: registers 8t..8t+7 are the k-slots of P.V step t
@@ -491,19 +477,18 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
         // ---- O^T += V . P : A = V tile rows (channels) with permuted keys, B = P.  Riding in the gaps: the value-tile
         //      pieces of tile t+1 (one per step) and, in the last steps, the first key fragments of tile t+1 ----------------
         {
-            constexpr bool SKIPLO = VLO0 || (COCOS_ABLATE & 512);
 #pragma unroll
             for (int i = 0; i < NSV; ++i) {
                 const int tt = i / CVB, cb = i % CVB, cur = i % RA, n = i + RA - 1;
-                if (!(COCOS_ABLATE & 2) && n < NSV) {
+                if (n < NSV) {
                     a_h[n % RA] = *reinterpret_cast<const f16x8*>(vbase + (n % CVB) * 32 * SP_VROW + (n / CVB) * 16);
                     a_s[n % RA] = *reinterpret_cast<const f16x8*>(vbase + 2 * VPLANE + (n % CVB) * 32 * SP_VROW + (n / CVB) * 16);
-                    if (!SKIPLO || (n % CVB) == 0)
+                    if (!VLO0 || (n % CVB) == 0)
                         a_l[n % RA] = *reinterpret_cast<const f16x8*>(vbase + VPLANE + (n % CVB) * 32 * SP_VROW + (n / CVB) * 16);
                 }
                 o[cb] = mfma16h(a_h[cur], ph[tt], o[cb]);
                 o[cb] = mfma16h(a_s[cur], pl[tt], o[cb]);      // (2^-11 V_hi) . (2^11 P_lo)
-                if (!SKIPLO || cb == 0) o[cb] = mfma16h(a_l[cur], ph[tt], o[cb]);
+                if (!VLO0 || cb == 0) o[cb] = mfma16h(a_l[cur], ph[tt], o[cb]);
                 piece(8 + i, vlo0_tag);
                 if (i == NSV - 1) prefetch_k(buf ^ 1);      // (NSV = 2: both in the same step)
                 __builtin_amdgcn_sched_barrier(0);

@@ -22,23 +22,15 @@ namespace cocos {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef HG_ABLATE
-#define HG_ABLATE 0    // debug builds only (tools/xbox_ablate.sh): 1 no T stores, 2 no x box, 4 no MFMAs, 8 no loads inside the k loop, 16 row-major tile order
-#endif
 constexpr int HG_BM = 256, HG_BN = 128, HG_BK = 32;
 constexpr int HG_ROW = HG_BK + 8;   // halfs per LDS row
 // A tile (round 6): 64-byte rows, the 16-byte chunk of a row XOR-swizzled by (row >> 2) & 3.  With the padded 80-byte rows the staging
 // writes (four lanes per row: 16 lanes = rows r .. r + 3) put rows r and r + 3 onto 12 common banks — PMC: 8.4 M LDS conflict cycles per
 // launch, 9 % of its time; here a 16-lane group writes 256 contiguous bytes and the fragment reads of 16 consecutive rows still fall
 // into 16 distinct 4-bank groups.  (Re-mapping the lanes instead — one chunk of 16 rows per 16 lanes — made the GLOBAL loads of the tile
-// 16-byte pieces of 16 different rows: 0.175 -> 0.200 ms.)  -DHG_A_PADDED keeps the old rows.  The tile's LDS region keeps its size.
-#ifdef HG_A_PADDED
-constexpr int HG_AROW = HG_ROW;
-__device__ __forceinline__ int hg_a_chunk(int row, int kc) { return kc; }
-#else
+// 16-byte pieces of 16 different rows: 0.175 -> 0.200 ms.)  The tile's LDS region keeps its size.
 constexpr int HG_AROW = HG_BK;
 __device__ __forceinline__ int hg_a_chunk(int row, int kc) { return kc ^ ((row >> 2) & 3); }
-#endif
 
 // EXACT: M % 256 == 0, N % 128 == 0, K % 32 == 0 — no bounds tests at all.  With them hipcc wraps every staged load in
 // an exec-mask region (s_and_saveexec / s_or per load: ~120 scalar instructions per k-step of 96 MFMAs).
@@ -90,11 +82,11 @@ __global__ __launch_bounds__(256, DUO ? 2 : 1) void hgemm_f16x3_kernel(const _Fl
     const int vb = xcd_remap(blockIdx.x, gridDim.x);
     const int b = vb / (ntn * ntm), rem = vb % (ntn * ntm);
     int mi = rem / ntn, ni = rem % ntn;
-    if (EPI != 0 && !(HG_ABLATE & 16) && (ntm & 7) == 0 && (ntn & 7) == 0) {
+    if (EPI != 0 && (ntm & 7) == 0 && (ntn & 7) == 0) {
         // x-box GEMM (both operands are re-read: 16 x 32 tiles per sample at cfg2'): the ~64 tiles an XCD works on at a time
         // form an 8 x 8 block of the tile grid instead of two full rows — 3 MB of operand planes (8 key tiles + 8 query tiles)
         // instead of 4.5 MB, inside the XCD's 4 MB of L2 — and the blocks walk along n inside an m block, so the key planes of
-        // an m block are fetched once (round 4; same-box A/B, -DHG_ABLATE=16: neutral at cfg2' — the 256 MB memory-side cache
+        // an m block are fetched once (round 4; same-box A/B against row-major order: neutral at cfg2' — the 256 MB memory-side cache
         // was already serving the re-reads — and 1.23 -> 1.19 ms on the 64 x 128 tile grid of cfg5)
         const int blk = rem >> 6, w = rem & 63, nb = ntn >> 3;
         mi = (blk / nb) * 8 + (w >> 3);
@@ -241,7 +233,7 @@ __global__ __launch_bounds__(256, DUO ? 2 : 1) void hgemm_f16x3_kernel(const _Fl
                 const f16x8 avl = *reinterpret_cast<const f16x8*>(ab + APLANE + i * 32 * HG_AROW + ach);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    if (!(HG_ABLATE & 4) && (EXACT || i < rows_live)) {     // (ragged M: a wave-uniform branch around the MFMAs of all-padding row tiles)
+                    if (EXACT || i < rows_live) {     // (ragged M: a wave-uniform branch around the MFMAs of all-padding row tiles)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh, bvh[j], acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avh, bvl[j], acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(avl, bvh[j], acc[i][j], 0, 0, 0);
@@ -259,7 +251,7 @@ __global__ __launch_bounds__(256, DUO ? 2 : 1) void hgemm_f16x3_kernel(const _Fl
     if (DUO) {
         for (int t = 0; t < nsteps; ++t) {
             commit(st0, 0);                                   // (every wave passed the barrier that ended step t - 1)
-            if (!(HG_ABLATE & 8) && t + 1 < nsteps) fetch(st0, (t + 1) * HG_BK);  // in flight while this k-block multiplies
+            if (t + 1 < nsteps) fetch(st0, (t + 1) * HG_BK);  // in flight while this k-block multiplies
             __syncthreads();
             step(t, st0);                                     // (ends with a barrier)
         }
@@ -286,8 +278,7 @@ __global__ __launch_bounds__(256, DUO ? 2 : 1) void hgemm_f16x3_kernel(const _Fl
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
             f32x16 (&t)[2][2] = *reinterpret_cast<f32x16 (*)[2][2]>(&acc[2 * hh]);
-            if (HG_ABLATE & 2) {
-            } else if (EPI == 1) {
+            if (EPI == 1) {
                 xbox_64x64(t, img, lane);
             } else {
                 // 128-wide grid (box3_common.h): the wave's 128 keys are ONE image row (two chunks hh = 0, 1, handled one after
@@ -320,7 +311,6 @@ __global__ __launch_bounds__(256, DUO ? 2 : 1) void hgemm_f16x3_kernel(const _Fl
                     const unsigned blk = (unsigned)((((m0 + wm * 128 + (2 * hh + kt) * 32) >> 5) * nqblk + ((n0 + wn * 64 + qt * 32) >> 5)) * 4096);
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        if (!(HG_ABLATE & 1) || t[kt][qt][4 * g] == 1234.5f)
                         __builtin_amdgcn_raw_buffer_store_b128(
                             __builtin_bit_cast(u32x4, f32x4{t[kt][qt][4 * g] * scale, t[kt][qt][4 * g + 1] * scale,
                                                             t[kt][qt][4 * g + 2] * scale, t[kt][qt][4 * g + 3] * scale}),

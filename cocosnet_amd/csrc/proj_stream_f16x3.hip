@@ -27,7 +27,7 @@
 //     compiled out when K = Kpad / M % (128 RB) = 0; threads beyond the last patch re-stage the first ones instead of
 //     carrying a test.  33.4 -> 29.4 us (fwd), 34.0 -> 30.9 us (dx).  What is left is not the order of the
 //     instructions (every arrangement of the same work lands within 2 %) but their sum: ablation builds
-//     (tools/build_k0_ablations.sh) show the parts adding up — prologue 5 us, f16 split + LDS commit 6-8, stores 5-9,
+//     (profiles/r02_ablation_k0.txt) show the parts adding up — prologue 5 us, f16 split + LDS commit 6-8, stores 5-9,
 //     loads 2, MFMAs 7-10.  A second wave per SIMD does not change that either: a 512-thread variant (8 waves, each with
 //     HALF of k in 104 AGPRs, partial sums exchanged through LDS at the tile-end barrier) was bit-identical in the tests
 //     and took 30.3 us (fwd) — the reason is in tools/probes/valu_overlap.hip: on gfx950 VALU instructions do not run
@@ -44,12 +44,7 @@ namespace cocos {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef PS_ABLATE
-#define PS_ABLATE 0    // debug builds only (tools/build_k0_ablations.sh): 1 no x loads in the loop, 2 no y stores, 4 no f16 split / LDS commit, 8 no MFMAs
-#endif
-#ifndef PS_SCHED_N
-#define PS_SCHED_N 5   // instructions of any other kind dealt out per MFMA (4 / 5 / 6 / 8 measured: 29.9 / 29.4 / 30.0 / 30.0 us)
-#endif
+constexpr int kPsSchedN = 5;   // instructions of any other kind dealt out per MFMA (4 / 5 / 6 / 8 measured: 29.9 / 29.4 / 30.0 / 30.0 us)
 
 __device__ __forceinline__ float ps_scale_from_amax(const float* amax) {
     if (!amax) return 1.0f;
@@ -131,7 +126,6 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
     //  descriptor — a scalar select instead of a per-lane one in front of every load -> zeros)
     auto fetch_piece = [&](int i, int q) __attribute__((always_inline)) {   // i = u * 8 + kk; tile slot q
         const int u = i >> 3, kk = i & 7;
-        if ((PS_ABLATE & 1) && q == 3) return;
         st[u][kk] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
             make_rsrc(x + (size_t)tl_b[q] * K * N, tl_ok[q] ? (size_t)K * N * 4 : 0),
             (int)((KFULL || kk < k_left[u]) ? x_voff[u] : kBufOob), (kk * N + tl_n[q]) * 4, 0));
@@ -141,7 +135,6 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
     unsigned c_hw[2], c_lw[2];
     auto commit_half = [&](int i2, int buf) __attribute__((always_inline)) {   // i2 = (u * 4 + j) * 2 + half
         const int u = i2 >> 3, j = (i2 >> 1) & 3, half = i2 & 1;
-        if (PS_ABLATE & 4) return;
         unsigned hw[2], lw[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -232,7 +225,6 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
     const int m_lane = m_wave + 4 * h;
     auto store_one = [&](const f32x16 (&reg)[RB], int i, int q, int cb) __attribute__((always_inline)) {   // i = rb * 16 + r; tile slot q
         const int rb = i >> 4, r = i & 15;
-        if (PS_ABLATE & 2) return;
         const bool live = MFULL || (m_lane + rb * 32 + acc_row_base(r) < M);
         buf_store1s(make_rsrc(y + (size_t)tl_b[q] * M * N, tl_ok[q] ? (size_t)M * N * 4 : 0), reg[rb][r],
                     live ? y_voff : kBufOob, (unsigned)((rb * 32 + acc_row_base(r)) * N + tl_n[q] + cb * 32) * 4u);
@@ -243,7 +235,7 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
     // so that two MFMAs on the same accumulator are never neighbours: an instruction issued between two DEPENDENT
     // MFMAs costs a ~43-cycle bubble on gfx950, between independent ones it is free, and the wave (alone on its
     // SIMD) has ~500 other instructions per tile to issue in the shadow of the MFMAs.  A group = 6 MFMAs = 2 slots;
-    // `hook(slot)` supplies the other work, the sched_group_barrier pipeline deals it out one MFMA : PS_SCHED_N.
+    // `hook(slot)` supplies the other work, the sched_group_barrier pipeline deals it out one MFMA : kPsSchedN.
     constexpr int KPG = RB == 2 ? 1 : 2;             // k steps per group
     constexpr int NGR = KS / KPG;                    // groups per block
     constexpr int RAG = RB == 2 ? 2 : 1;             // operand read-ahead in groups
@@ -278,7 +270,6 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int ks = RB == 2 ? g : 2 * g + j, rb = RB == 2 ? j : 0, fb = ks % NFB;
-                    if (!(PS_ABLATE & 8))
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 2 ? al[rb][ks] : ah[rb][ks],
                                                                     term == 1 ? bl[fb] : bh[fb], acc[j], 0, 0, 0);
                 }
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void proj_stream_f16x3_kernel(
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, PS_SCHED_N, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002 | 0x004 | 0x010 | 0x080, kPsSchedN, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }

@@ -1,6 +1,6 @@
 """Debug: per-phase shader-clock ticks of the K2 split kernels in the magnitude-free (Attention) flavour at the netG shape
-(library built with -DCOCOS_DEBUG_TIMING: COCOS_ABL_EXTRA=-DCOCOS_DEBUG_TIMING tools/build_ablations.sh 0;
-COCOS_LIB_PATH=cocosnet_amd/lib/libcocos_hip_abl0.so python tools/phase_timing_attention.py)"""
+(library built with COCOS_LIB_NAME=libcocos_hip_dbg.so COCOS_EXTRA_HIPFLAGS=-DCOCOS_DEBUG_TIMING python -m cocosnet_amd.build).
+Usage: COCOS_LIB_PATH=.../libcocos_hip_dbg.so python tools/phase_timing_attention.py [Nq [B]]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 """Times K23 / K24 / the weight-gradient pair of the two projections at the bench shape (B = 8, Cin = 407, 64 x 64), one library
-per run (COCOS_LIB_PATH selects ablation builds).  Usage (GPU box): python tools/proj_pair_bench.py [B Cin h w]"""
+per run (COCOS_LIB_PATH selects an alternate build).  Usage (GPU box): python tools/proj_pair_bench.py [B Cin h w]"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
