@@ -56,6 +56,7 @@ HIP_SOURCES = [
     "conv_f16x3.hip",
     "conv_nhwc_bf16.hip",
     "spade_modulate.hip",
+    "norm_spade.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
 ]

@@ -2512,6 +2512,201 @@ def spade_modulate(xh, gamma, beta, slope: float = 1.0):
 
 
 # ------------------------------------------------------------------------------------------
+# K26 parameter-free batch / sync-batch / instance norm + SPADE modulation + LeakyReLU   (normalization.py:93-101, :148;
+#     architecture.py:88-95) — the non-PONO counterpart of K9, four passes: stats, apply | bwd_stats, bwd_apply
+# ------------------------------------------------------------------------------------------
+NORM_SPADE_KINDS = ("batch", "syncbatch", "instance")
+
+
+def _ns_dims(x: torch.Tensor):
+    if x.dim() < 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"norm_spade: expected x [B, C, ...], got {tuple(x.shape)}")
+    B, C = x.shape[:2]
+    return B, C, x.numel() // (B * C)
+
+
+def _ns_workspace(x: torch.Tensor) -> torch.Tensor:
+    B, C, N = _ns_dims(x)
+    return torch.empty(max(_lib.load().cocos_norm_spade_workspace_floats(B, C, N), 4), device=x.device, dtype=torch.float32)
+
+
+def _ns_same_shape(x, *ts):
+    for t in ts:
+        if t.shape != x.shape:
+            raise ValueError(f"norm_spade: x{tuple(x.shape)} and an operand of shape {tuple(t.shape)}")
+
+
+def norm_spade_stats(x, per_sample: bool, eps: float = 1e-5) -> torch.Tensor:
+    """One pass over x [B, C, ...]: [4, G] = (count, mean, M2, 1/sqrt(M2/count + eps)) per statistics group — the channel over
+    (B, H, W) for the batch norms (G = C), the plane (b, c) for per_sample (G = B*C).  Bitwise reproducible."""
+    x = _chk(x, "norm_spade_stats: x")
+    B, C, N = _ns_dims(x)
+    stats = torch.empty((4, B * C if per_sample else C), device=x.device, dtype=torch.float32)
+    _call("norm_spade_fwd", "cocos_norm_spade_stats", x.data_ptr(), stats.data_ptr(), _ns_workspace(x).data_ptr(), B, C, N,
+          int(bool(per_sample)), float(eps), _stream())
+    return stats
+
+
+def merge_norm_stats(stats: torch.Tensor, eps: float = 1e-5):
+    """Combine the [R, 4, G] (count, mean, M2, .) of R parts of a batch (ranks) into the whole batch's (count, mean, M2, invstd),
+    each [G]: in fp64, M2 = sum_r M2_r + n_r (mean_r - mean)^2 (exact, no sum x^2 - n mean^2 cancellation)."""
+    s = stats.double()
+    n_r, m_r, M_r = s[:, 0], s[:, 1], s[:, 2]
+    n = n_r.sum(0)
+    mean = (n_r * m_r).sum(0) / n
+    M2 = (M_r + n_r * (m_r - mean) ** 2).sum(0)
+    invstd = torch.rsqrt(M2 / n + eps)
+    return torch.stack([n, mean, M2, invstd]).float()
+
+
+def norm_spade_apply(x, gamma, beta, mean, invstd, per_sample: bool, slope: float = 1.0, amax_cell=None) -> torch.Tensor:
+    """y = leaky_relu((x - mean_g) * invstd_g * (1 + gamma) + beta, slope) with per-group mean / invstd [G] (batch statistics or
+    running buffers).  amax_cell (optional 1-element tensor): max(cell, max|y|) from the same pass."""
+    x, gamma, beta = (_chk(t, f"norm_spade_apply: {n}") for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta")))
+    mean, invstd = _chk(mean, "norm_spade_apply: mean"), _chk(invstd, "norm_spade_apply: invstd")
+    _ns_same_shape(x, gamma, beta)
+    B, C, N = _ns_dims(x)
+    y = torch.empty_like(x)
+    ws = _ns_workspace(x) if amax_cell is not None else None
+    _call("norm_spade_fwd", "cocos_norm_spade_apply", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+          invstd.data_ptr(), y.data_ptr(), _ptr(amax_cell), _ptr(ws), B, C, N, int(bool(per_sample)), float(slope), _stream())
+    return y
+
+
+def norm_spade_bwd_stats(x, gamma, beta, dy, mean, invstd, per_sample: bool, slope: float = 1.0) -> torch.Tensor:
+    """One pass over x, gamma, beta, dy: [2, G] = (sum dxhat, sum dxhat * xhat) per group, dxhat = dy * act'(z) * (1 + gamma)."""
+    x, gamma, beta, dy = (_chk(t, f"norm_spade_bwd_stats: {n}") for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (dy, "dy")))
+    mean, invstd = _chk(mean, "norm_spade_bwd_stats: mean"), _chk(invstd, "norm_spade_bwd_stats: invstd")
+    _ns_same_shape(x, gamma, beta, dy)
+    B, C, N = _ns_dims(x)
+    sums = torch.empty((2, B * C if per_sample else C), device=x.device, dtype=torch.float32)
+    _call("norm_spade_bwd", "cocos_norm_spade_bwd_stats", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(),
+          mean.data_ptr(), invstd.data_ptr(), sums.data_ptr(), _ns_workspace(x).data_ptr(), B, C, N, int(bool(per_sample)), float(slope),
+          _stream())
+    return sums
+
+
+def norm_spade_bwd_apply(x, gamma, beta, dy, mean, invstd, sums, inv_count: float, per_sample: bool, slope: float = 1.0,
+                         need=(True, True, True), amax_cells=None):
+    """(dx, dgamma, dbeta), each None where `need` says so.  sums: norm_spade_bwd_stats of the whole group (all ranks), scaled
+    by inv_count = 1 / group size; None = constant statistics (running buffers): dx = invstd * dxhat.  amax_cells (optional
+    2-element tensor): max(cell, max|dgamma|), max(cell, max|dbeta|) from the same pass."""
+    x, gamma, beta, dy = (_chk(t, f"norm_spade_bwd_apply: {n}") for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (dy, "dy")))
+    mean, invstd = _chk(mean, "norm_spade_bwd_apply: mean"), _chk(invstd, "norm_spade_bwd_apply: invstd")
+    sums = None if sums is None else _chk(sums, "norm_spade_bwd_apply: sums")
+    _ns_same_shape(x, gamma, beta, dy)
+    B, C, N = _ns_dims(x)
+    outs = [torch.empty_like(x) if w else None for w in need]
+    ws = _ns_workspace(x) if amax_cells is not None else None
+    _call("norm_spade_bwd", "cocos_norm_spade_bwd_apply", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(),
+          mean.data_ptr(), invstd.data_ptr(), _ptr(sums), float(inv_count), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+          _ptr(amax_cells), _ptr(ws), B, C, N, int(bool(per_sample)), float(slope), _stream())
+    return tuple(outs)
+
+
+class _NormSpade(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, per_sample: bool, use_batch: bool, run_mean, run_var, eps: float, slope: float, sync: bool, group,
+                holder: dict):
+        x, gamma, beta = _chk(x, "norm_spade: x"), _chk(gamma, "norm_spade: gamma"), _chk(beta, "norm_spade: beta")
+        _ns_same_shape(x, gamma, beta)
+        B, C, N = _ns_dims(x)
+        count = None
+        if use_batch:
+            stats = norm_spade_stats(x, per_sample, eps)
+            if sync:            # every rank's (count, mean, M2): one small all-gather, merged in fp64
+                import torch.distributed as dist
+                parts = [torch.empty_like(stats) for _ in range(dist.get_world_size(group))]
+                dist.all_gather(parts, stats.contiguous(), group=group)
+                stats = merge_norm_stats(torch.stack(parts), eps)
+                count = stats[0, :1]                   # (same for every channel; stays on the device)
+            else:
+                count = float(B * N if not per_sample else N)
+            mean, invstd = stats[1].contiguous(), stats[3].contiguous()
+            holder.update(mean=mean, m2=stats[2], count=count)
+        else:
+            mean = run_mean.detach().float().contiguous()
+            invstd = torch.rsqrt(run_var.detach().float() + eps).contiguous()
+        cell = _zero_cell(x.device) if CONV_PRECISION == "f16x3" else None   # y is the input of the block's next convolution
+        y = norm_spade_apply(x, gamma, beta, mean, invstd, per_sample, slope, cell)
+        if cell is not None:
+            _remember_amax(y, cell, weak=True)
+        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        ctx.cfg = (bool(per_sample), bool(use_batch), float(slope), bool(sync), group, count)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, mean, invstd = ctx.saved_tensors
+        per_sample, use_batch, slope, sync, group, count = ctx.cfg
+        dy = _chk(dy, "norm_spade: dy")
+        need = tuple(ctx.needs_input_grad[:3])
+        sums, inv_count = None, 1.0
+        if use_batch and need[0]:
+            sums = norm_spade_bwd_stats(x, gamma, beta, dy, mean, invstd, per_sample, slope)
+            if sync:
+                import torch.distributed as dist
+                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+                sums = (sums / count).contiguous()
+            else:
+                inv_count = 1.0 / count
+        cells = _zero_cells(x.device, 2) if (need[1] or need[2]) and CONV_PRECISION == "f16x3" else None
+        dx, dg, db = norm_spade_bwd_apply(x, gamma, beta, dy, mean, invstd, sums, inv_count, per_sample, slope, need, cells)
+        if cells is not None:       # the output gradients of SPADE's mlp_gamma / mlp_beta convolutions
+            if dg is not None:
+                _remember_amax(dg, cells[0:1], weak=True)
+            if db is not None:
+                _remember_amax(db, cells[1:2], weak=True)
+        return dx, dg, db, None, None, None, None, None, None, None, None, None
+
+
+def norm_spade(x, gamma, beta, kind: str, running_mean=None, running_var=None, num_batches_tracked=None, training: bool = True,
+               momentum=0.1, eps: float = 1e-5, slope: float = 1.0, group=None):
+    """leaky_relu(norm(x) * (1 + gamma) + beta, slope) for x, gamma, beta [B, C, H, W], norm one of NORM_SPADE_KINDS without
+    affine parameters: "batch" = nn.BatchNorm2d, "syncbatch" = dist.SyncBatchNorm2d (statistics over every rank of `group` when a
+    process group is live), "instance" = nn.InstanceNorm2d (no running statistics).  The running buffers follow nn.BatchNorm2d:
+    batch statistics when `training` or no buffers are given, updated with `momentum` (None: cumulative average), unbiased
+    running_var, num_batches_tracked counted."""
+    if kind not in NORM_SPADE_KINDS:
+        raise ValueError(f"norm_spade: kind {kind!r} is not one of {NORM_SPADE_KINDS}")
+    per_sample = kind == "instance"
+    track = running_mean is not None and running_var is not None
+    if per_sample and track:
+        raise ValueError("norm_spade: instance norm with running statistics is not supported")
+    use_batch = training or not track
+    size = x.size()
+    if use_batch:
+        spatial = 1
+        for d in size[2:]:
+            spatial *= d
+        if per_sample and spatial == 1:
+            raise ValueError(f"Expected more than 1 spatial element when training, got input size {size}")
+        if kind == "batch" and size[0] * spatial == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {size}")
+    sync = False
+    if kind == "syncbatch" and use_batch:
+        from .dist import _live_world
+        sync = _live_world(group) > 1
+    holder = {}
+    y = _NormSpade.apply(x, gamma, beta, per_sample, use_batch, running_mean, running_var, float(eps), float(slope), sync, group, holder)
+    if training and track:
+        with torch.no_grad():
+            m = 0.0 if momentum is None else momentum
+            if num_batches_tracked is not None:
+                num_batches_tracked.add_(1)
+                if momentum is None:
+                    m = 1.0 / float(num_batches_tracked)
+            n = holder["count"]
+            if isinstance(n, torch.Tensor):
+                unbiased = holder["m2"] / (n - 1).clamp_min(1.0)
+            else:
+                unbiased = holder["m2"] / max(n - 1.0, 1.0)
+            running_mean.mul_(1 - m).add_(holder["mean"], alpha=m)
+            running_var.mul_(1 - m).add_(unbiased, alpha=m)
+    return y
+
+
+# ------------------------------------------------------------------------------------------
 # K11 nearest-neighbour up-sampling of the warped image   (correspondence.py:188, :327)
 # ------------------------------------------------------------------------------------------
 class _UpsampleNearest(torch.autograd.Function):

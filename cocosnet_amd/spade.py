@@ -9,29 +9,62 @@ after (architecture.py:88-95, `actvn` :107-108) are one HBM pass in K9 (`ops.pon
 `install_spade_into_reference(networks)` rebinds the two `forward` methods of the reference's own classes, so every
 SPADE of an already-written training script (netG and netCorr alike) takes the fused path on the GPU; parameters,
 sub-modules and `state_dict` are untouched (checkpoints load unchanged).  CPU tensors, non-fp32 tensors, the
-`similarity_map` argument and non-PONO norms keep the reference's arithmetic (instance / batch / sync-batch statistics
-are computed by their own modules, only the modulation + activation are fused where that helps).
+`similarity_map` argument and norms of other classes keep the reference's arithmetic (their statistics are computed by
+their own modules, only the modulation + activation are fused).  Without `--PONO`, nn.BatchNorm2d, nn.InstanceNorm2d and
+dist.SyncBatchNorm2d (all parameter-free) are fused with the modulation and the activation in K26 (`ops.norm_spade`).
 """
 from __future__ import annotations
 
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
 
 LEAKY_SLOPE = 2e-1      # SPADEResnetBlock.actvn (architecture.py:107-108)
+#: non-PONO SPADE: batch / sync-batch / instance norm + modulation + activation as ONE fused operator (K26, ops.norm_spade) instead
+#: of the norm module followed by K17.  Test / A-B hook (tools/norm_spade_bench.py): plain module attribute, read at call time.
+NORM_FUSED = True
 
 
 def _hip_ok(*ts) -> bool:
     return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
 
 
+def _device_fp32(*ts) -> bool:
+    """The tensors themselves (not the `_hip_ok` dispatch hook) are CUDA fp32: K26 also reads and updates the module's running
+    buffers in place, so they have to live on the device next to x."""
+    return all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def _norm_spade_kind(m):
+    """The kind of ops.norm_spade that computes exactly what the parameter-free norm module `m` does, or None.  Exact classes
+    only: a subclass (or the reference's own SynchronizedBatchNorm2d) may do anything, so it keeps its own forward."""
+    from .dist import SyncBatchNorm2d
+    t = type(m)
+    if t is nn.BatchNorm2d and not m.affine:
+        return "batch"
+    if t is nn.InstanceNorm2d and not m.affine and not m.track_running_stats:
+        return "instance"
+    if t is SyncBatchNorm2d and not m.affine:
+        return "syncbatch"
+    return None
+
+
 def modulate(x, gamma, beta, pono: bool, param_free_norm=None, slope: float = 1.0):
     """leaky_relu(norm(x) * (1 + gamma) + beta, slope): the tail of SPADE.forward (+ the block's activation).
-    pono: PositionalNorm2d — fused with the modulation and the activation in K9 when x is CUDA fp32; otherwise the
-    norm stays the module's own and the modulation + activation are K17."""
-    if pono and _hip_ok(x, gamma, beta) and gamma.shape == x.shape and beta.shape == x.shape:
+    pono: PositionalNorm2d — fused with the modulation and the activation in K9 when x is CUDA fp32.  Otherwise a batch /
+    sync-batch / instance norm module of the exact classes of _norm_spade_kind is fused the same way (K26, reading and updating
+    the module's running buffers); any other norm stays the module's own and the modulation + activation are K17."""
+    fusible = _hip_ok(x, gamma, beta) and gamma.shape == x.shape and beta.shape == x.shape
+    if pono and fusible:
         return ops.pono_spade(x, gamma, beta, slope)
+    if not pono and NORM_FUSED and fusible and x.dim() == 4:
+        kind = _norm_spade_kind(param_free_norm)
+        m = param_free_norm
+        if kind is not None and _device_fp32(x, gamma, beta, *(b for b in (m.running_mean, m.running_var) if b is not None)):
+            return ops.norm_spade(x, gamma, beta, kind, m.running_mean, m.running_var, m.num_batches_tracked, m.training, m.momentum,
+                                  m.eps, slope, getattr(m, "group", None))
     if pono:
         mu = x.mean(dim=1, keepdim=True)                              # normalization.py:63-68
         normalized = (x - mu) / x.var(dim=1, keepdim=True).add(1e-5).sqrt()

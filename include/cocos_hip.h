@@ -666,6 +666,37 @@ int cocos_spade_modulate_bwd(const float* xh, const float* gamma, const float* b
                              float* dgamma, float* dbeta, long long n, float slope, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K26 parameter-free batch / sync-batch / instance norm + SPADE modulation + LeakyReLU, fused (the non-PONO branch of SPADE,
+ *     normalization.py:93-101 and :148, architecture.py:88-95) — K9's counterpart for the norms whose statistics span the batch:
+ *   x, gamma, beta, y, dy and the gradients [B,C,N] fp32 (N = H*W).  Statistics group g: channel c over (B, N) for
+ *   per_sample = 0 (batch / sync-batch), plane (b, c) over N for per_sample = 1 (instance); G = C resp. B*C.
+ *   xhat = (x - mean_g) * invstd_g;  z = xhat*(1+gamma) + beta;  y = z > 0 ? z : slope*z   (slope = 1: no activation)
+ *   workspace: cocos_norm_spade_workspace_floats(B, C, N) floats, 16-byte aligned (partials of the passes below).
+ *   stats:     one pass over x -> stats [4][G] = count, mean, M2 (sum of squared deviations), 1/sqrt(M2/count + eps).
+ *              Per-workgroup partials merged (Chan) by a finishing kernel of the same call: bitwise reproducible, no atomics.
+ *   apply:     y from x, gamma, beta and per-group mean / invstd (batch statistics, or the running buffers in eval mode);
+ *              y_amax_inout_dev (nullable) = max(*cell, max|y|), the workspace then holds the per-workgroup maxima.
+ *   bwd_stats: one pass over x, gamma, beta, dy (z recomputed) -> sums [2][G] = sum dxhat, sum dxhat * xhat,
+ *              dxhat = dy * act'(z) * (1 + gamma).
+ *   bwd_apply: any of dx, dgamma, dbeta (NULL = not wanted):  dgamma = dz * xhat, dbeta = dz = dy * act'(z),
+ *              dx = invstd * (dxhat - sums[0]*inv_count - xhat * sums[1]*inv_count);  sums NULL = constant statistics (eval):
+ *              dx = invstd * dxhat.  amax2_inout_dev (nullable) = [max|dgamma|, max|dbeta|] as for cocos_pono_spade_bwd_amax.
+ * ------------------------------------------------------------------------------------- */
+int cocos_norm_spade_workspace_floats(int B, int C, int N);
+int cocos_norm_spade_stats(const float* x, float* stats, float* workspace, int B, int C, int N, int per_sample, float eps,
+                           cocos_stream_t stream);
+int cocos_norm_spade_apply(const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd, float* y,
+                           float* y_amax_inout_dev, float* workspace, int B, int C, int N, int per_sample, float slope,
+                           cocos_stream_t stream);
+int cocos_norm_spade_bwd_stats(const float* x, const float* gamma, const float* beta, const float* dy, const float* mean,
+                               const float* invstd, float* sums, float* workspace, int B, int C, int N, int per_sample, float slope,
+                               cocos_stream_t stream);
+int cocos_norm_spade_bwd_apply(const float* x, const float* gamma, const float* beta, const float* dy, const float* mean,
+                               const float* invstd, const float* sums, float inv_count, float* dx, float* dgamma, float* dbeta,
+                               float* amax2_inout_dev, float* workspace, int B, int C, int N, int per_sample, float slope,
+                               cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K16 2-D convolution (cross-correlation, zero padding, like torch.nn.functional.conv2d with groups = 1, one stride /
  *     padding / dilation for both axes)
  *     as an implicit GEMM on the f16 MFMA with split operands (conv_f16x3.hip).  Replaces the nn.Conv2d calls of the
