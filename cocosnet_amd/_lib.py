@@ -251,6 +251,12 @@ _SIGNATURES = {
     "cocos_norm_spade_bwd_stats": (ctypes.c_int, [_c_float_p] * 8 + [ctypes.c_int] * 4 + [ctypes.c_float, _stream_t]),
     "cocos_norm_spade_bwd_apply": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_float] + [_c_float_p] * 5 + [ctypes.c_int] * 4
                                    + [ctypes.c_float, _stream_t]),
+    "cocos_vgg_preprocess_fwd": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_stream_t]),
+    "cocos_vgg_preprocess_bwd": (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 4 + [_stream_t]),
+    "cocos_relu_fwd": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_longlong, _stream_t]),
+    "cocos_relu_bwd": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_longlong, _stream_t]),
+    "cocos_relu_pool2_fwd": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_stream_t]),
+    "cocos_relu_pool2_bwd": (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 4 + [_stream_t]),
     "cocos_conv2d_out_size": (ctypes.c_int, [ctypes.c_int] * 5),
     "cocos_conv2d_kdim": (ctypes.c_int, [ctypes.c_int] * 3),
     "cocos_conv2d_fwd_f16x3": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,

@@ -57,6 +57,7 @@ HIP_SOURCES = [
     "conv_nhwc_bf16.hip",
     "spade_modulate.hip",
     "norm_spade.hip",
+    "vgg_glue.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
 ]

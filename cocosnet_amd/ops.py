@@ -3085,6 +3085,122 @@ def contextual_cx(xn, yn, h: float = 0.1, eps: float = 1e-3):
     return _ContextualCx.apply(xn, yn, float(h), float(eps))
 
 
+# ------------------------------------------------------------------------------------------
+# K27  the glue of the fixed VGG19: preprocess, ReLU, ReLU + 2x2 pool   (correspondence.py:79-146, util/util.py:45-54)
+# ------------------------------------------------------------------------------------------
+def _glue_cell(device):
+    """A max|.| cell for a K27 output that a K16 layer splits next, or None where nothing reads it (COCOS_CONV=bf16 splits nothing,
+    'torch' runs the framework's convolutions)."""
+    return _zero_cell(device) if CONV_PRECISION == "f16x3" else None
+
+
+def _glue_remember(t, cell):
+    if cell is not None:
+        _remember_amax(t, cell, weak=True)
+
+
+class _VggPreprocess(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, normal_correct: bool):
+        x = _chk(x, "vgg_preprocess: x")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"vgg_preprocess: expected an RGB batch [B, 3, H, W], got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        y = torch.empty_like(x)
+        cell = _glue_cell(x.device)
+        _call("vgg_preprocess", "cocos_vgg_preprocess_fwd", x.data_ptr(), y.data_ptr(), _ptr(cell), B, H, W, int(normal_correct), _stream())
+        _glue_remember(y, cell)
+        ctx.cfg = (B, H, W, int(normal_correct))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _chk(dy, "vgg_preprocess: dy")
+        dx = torch.empty_like(dy)
+        _call("vgg_preprocess", "cocos_vgg_preprocess_bwd", dy.data_ptr(), dx.data_ptr(), *ctx.cfg, _stream())
+        return dx, None
+
+
+def vgg_preprocess(x: torch.Tensor, normal_correct: bool = False) -> torch.Tensor:
+    """util.vgg_preprocess (util/util.py:45-54) in one pass, bitwise: ((x + 1) / 2 when normal_correct), RGB -> BGR, minus the
+    reference's mean, x 255.  Leaves max|y| for the first convolution."""
+    return _VggPreprocess.apply(x, bool(normal_correct))
+
+
+class _Relu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y):
+        y = _chk(y, "relu: y")
+        r = torch.empty_like(y)
+        cell = _glue_cell(y.device)
+        _call("relu", "cocos_relu_fwd", y.data_ptr(), r.data_ptr(), _ptr(cell), y.numel(), _stream())
+        _glue_remember(r, cell)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(r)
+        return r
+
+    @staticmethod
+    def backward(ctx, dr):
+        r, = ctx.saved_tensors
+        dr = _chk(dr, "relu: dr")
+        dy = torch.empty_like(r)
+        cell = _glue_cell(r.device)
+        _call("relu", "cocos_relu_bwd", dr.data_ptr(), r.data_ptr(), dy.data_ptr(), _ptr(cell), r.numel(), _stream())
+        _glue_remember(dy, cell)
+        return dy
+
+
+def relu(y: torch.Tensor) -> torch.Tensor:
+    """F.relu(y), bitwise (NaN kept), out of place; leaves max|r| for the next convolution and, backward, max|dy| for its own."""
+    return _Relu.apply(y)
+
+
+class _ReluPool2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, mode: int, keep_r: bool):
+        y = _chk(y, "relu_pool2: y")
+        if y.dim() != 4:
+            raise ValueError(f"relu_pool2: expected [B, C, H, W], got {tuple(y.shape)}")
+        B, C, H, W = y.shape
+        p = y.new_empty((B, C, H // 2, W // 2))
+        r = torch.empty_like(y) if keep_r else None
+        cell = _glue_cell(y.device)
+        _call("relu_pool2", "cocos_relu_pool2_fwd", y.data_ptr(), _ptr(r), p.data_ptr(), _ptr(cell), B * C, H, W, mode, _stream())
+        _glue_remember(p, cell)
+        if ctx.needs_input_grad[0]:
+            # the backward recomputes the mask and the arg-max from relu(src): r where it exists, else the pre-activation y
+            ctx.save_for_backward(r if keep_r else y)
+        ctx.cfg = (mode, keep_r)
+        ctx.set_materialize_grads(False)     # an output the loss does not reach costs no zero-filled gradient
+        return (r, p) if keep_r else p
+
+    @staticmethod
+    def backward(ctx, *grads):
+        src, = ctx.saved_tensors
+        mode, keep_r = ctx.cfg
+        dr, dp = grads if keep_r else (None, grads[0])
+        if dr is None and dp is None:
+            return None, None, None
+        dr = None if dr is None else _chk(dr, "relu_pool2: dr")
+        dp = None if dp is None else _chk(dp, "relu_pool2: dp")
+        B, C, H, W = src.shape
+        dy = torch.empty_like(src)
+        cell = _glue_cell(src.device)
+        _call("relu_pool2", "cocos_relu_pool2_bwd", src.data_ptr(), _ptr(dr), _ptr(dp), dy.data_ptr(), _ptr(cell), B * C, H, W, mode,
+              _stream())
+        _glue_remember(dy, cell)
+        return dy, None, None
+
+
+def relu_pool2(y: torch.Tensor, mode: str = "max", keep_r: bool = False):
+    """p = F.max_pool2d(F.relu(y), 2, 2) (mode "max") or F.avg_pool2d(F.relu(y), 2, 2) ("avg"), bitwise, from one read of y;
+    returns (r, p) with r = F.relu(y) when keep_r, else p alone.  No index tensor: the backward recomputes the window's arg-max.
+    Leaves max|p| for the next convolution and, backward, max|dy| for the one that produced y."""
+    if mode not in ("max", "avg"):
+        raise ValueError(f"relu_pool2: mode {mode!r}: expected 'max' or 'avg'")
+    return _ReluPool2.apply(y, 0 if mode == "max" else 1, bool(keep_r))
+
+
 def mfma_probe() -> torch.Tensor:
     """Debug: the 64x16 accumulator image of one v_mfma_f32_32x32x2_f32 (see api_common.hip)."""
     out = torch.empty((64, 16), device="cuda", dtype=torch.float32)

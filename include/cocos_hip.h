@@ -697,6 +697,36 @@ int cocos_norm_spade_bwd_apply(const float* x, const float* gamma, const float* 
                                cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K27 the glue between the convolutions of the fixed VGG19 feature extractor (VGG19_feature_color_torchversion,
+ *     correspondence.py:79-146; vgg_preprocess, util/util.py:45-54) — every result BITWISE equal to the framework's fp32 ops on
+ *     the same input (same operations in the same order, no contraction).  Out-of-place: no output may alias an input.
+ *   amax_inout_dev (nullable, every entry that has it): *cell = max(*cell, max|out|) for the tensor named below, as uint bits
+ *   (the cell must hold a finite value >= 0, e.g. 0; a NaN in the output leaves a NaN) — the scale of the next K16 layer's split.
+ *   preprocess_fwd: x, y [B,3,H,W]: y[:, c] = (x'[:, 2-c] - mean_bgr[c]) * 255, x' = (x + 1) / 2 if normal_correct else x,
+ *                   mean_bgr = (0.40760392, 0.45795686, 0.48501961).  Cell: max|y|.
+ *   preprocess_bwd: dx[:, c] = dy[:, 2-c] * 255 (then / 2 if normal_correct).
+ *   relu_fwd:       r = relu(y) over n elements, a NaN kept (torch.relu).  Cell: max|r|.
+ *   relu_bwd:       dy = src <= 0 ? 0 : dr (threshold_backward: a select, NaN passes; src = r or the pre-activation y).
+ *                   Cell: max|dy|.
+ *   relu_pool2_fwd: y [BC,H,W] -> p [BC,H/2,W/2] = pool2x2(relu(y)) (floor), and r [BC,H,W] = relu(y) when r is non-NULL, from
+ *                   one read of y.  mode 0 = max (first maximum in scan order, NaN wins: max_pool2d), 1 = avg (sum in scan order,
+ *                   / 4: avg_pool2d).  Cell: max|p|.
+ *   relu_pool2_bwd: dy [BC,H,W] = (dr + route(dp)) where !(src <= 0), else 0; route = dp to the window's arg-max (recomputed from
+ *                   relu(src): no index tensor) or dp / 4 to each of its four elements (avg); rows / columns cut by the floor get
+ *                   dr only.  dr [BC,H,W] and dp [BC,H/2,W/2] are each nullable (= zero).  src = r or y.  Cell: max|dy|.
+ *   H < 2 or W < 2 (no 2x2 window) -> COCOS_ERR_UNSUPPORTED.  Element indices are 64-bit.
+ * ------------------------------------------------------------------------------------- */
+int cocos_vgg_preprocess_fwd(const float* x, float* y, float* amax_inout_dev, int B, int H, int W, int normal_correct,
+                             cocos_stream_t stream);
+int cocos_vgg_preprocess_bwd(const float* dy, float* dx, int B, int H, int W, int normal_correct, cocos_stream_t stream);
+int cocos_relu_fwd(const float* y, float* r, float* amax_inout_dev, long long n, cocos_stream_t stream);
+int cocos_relu_bwd(const float* dr, const float* src, float* dy, float* amax_inout_dev, long long n, cocos_stream_t stream);
+int cocos_relu_pool2_fwd(const float* y, float* r /* nullable */, float* p, float* amax_inout_dev, int BC, int H, int W, int mode,
+                         cocos_stream_t stream);
+int cocos_relu_pool2_bwd(const float* src, const float* dr /* nullable */, const float* dp /* nullable */, float* dy,
+                         float* amax_inout_dev, int BC, int H, int W, int mode, cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K16 2-D convolution (cross-correlation, zero padding, like torch.nn.functional.conv2d with groups = 1, one stride /
  *     padding / dilation for both axes)
  *     as an implicit GEMM on the f16 MFMA with split operands (conv_f16x3.hip).  Replaces the nn.Conv2d calls of the
