@@ -257,6 +257,19 @@ _SIGNATURES = {
     "cocos_relu_bwd": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_longlong, _stream_t]),
     "cocos_relu_pool2_fwd": (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_stream_t]),
     "cocos_relu_pool2_bwd": (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 4 + [_stream_t]),
+    # K28: the tables are host arrays (ctypes arrays of nseg entries), every other pointer is device memory
+    "cocos_loss_partials": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),
+    "cocos_pair_loss_fwd": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_void_p, _c_float_p, _stream_t]),
+    "cocos_pair_loss_bwd": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 8 + [_c_float_p, _stream_t]),
+    "cocos_gan_loss_fwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
+                                          ctypes.c_void_p, _c_float_p, _stream_t]),
+    "cocos_gan_loss_bwd": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_float, _c_float_p,
+                                                                                   _stream_t]),
+    "cocos_mask_nll_partials": (ctypes.c_int, [ctypes.c_int] * 3),
+    "cocos_mask_nll_fwd": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 6
+                           + [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _stream_t]),
+    "cocos_mask_nll_bwd": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p]
+                           + [ctypes.c_int] * 4 + [_stream_t]),
     "cocos_conv2d_out_size": (ctypes.c_int, [ctypes.c_int] * 5),
     "cocos_conv2d_kdim": (ctypes.c_int, [ctypes.c_int] * 3),
     "cocos_conv2d_fwd_f16x3": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,

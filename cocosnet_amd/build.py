@@ -58,6 +58,7 @@ HIP_SOURCES = [
     "spade_modulate.hip",
     "norm_spade.hip",
     "vgg_glue.hip",
+    "loss_reduce.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
 ]

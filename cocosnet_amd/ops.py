@@ -7,6 +7,7 @@ the reference (models/networks/correspondence.py:274,284).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import sys
 import threading
@@ -3199,6 +3200,190 @@ def relu_pool2(y: torch.Tensor, mode: str = "max", keep_r: bool = False):
     if mode not in ("max", "avg"):
         raise ValueError(f"relu_pool2: mode {mode!r}: expected 'max' or 'avg'")
     return _ReluPool2.apply(y, 0 if mode == "max" else 1, bool(keep_r))
+
+
+# ------------------------------------------------------------------------------------------
+# K28  the loss block: pair (L1 / MSE) groups, GANLoss over a prediction list, the warp-mask NLL
+#      (pix2pix_model.py:205-296, util/util.py:36-43, networks/loss.py:15-97)
+# ------------------------------------------------------------------------------------------
+#: widest group one launch takes (COCOS_PAIR_LOSS_MAX_SEGMENTS / COCOS_GAN_LOSS_MAX_TENSORS of include/cocos_hip.h)
+PAIR_LOSS_MAX_SEGMENTS = 16
+GAN_LOSS_MAX_TENSORS = 8
+#: GANLoss.loss's cases -> the kernel's mode (COCOS_GAN_* of include/cocos_hip.h)
+GAN_MODES = {"hinge_d_real": 0, "hinge_d_fake": 1, "neg_mean": 2, "mean": 3, "ls": 4, "bce": 5}
+
+
+def _loss_chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype:
+        what = f"{t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise _lib.CocosHipError(f"{name}: expected a {dtype} CUDA/HIP tensor, got {what}; the loss kernels have no CPU fallback")
+    return t.contiguous()
+
+
+def _table(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+def _pair_parse(spec, tensors, name="pair_loss"):
+    """(a, b, w) lists of the contiguous tensors of a flat argument list; every one of them is referenced by the returned lists
+    until the caller drops them — after the launch is queued."""
+    A, Bs, Ws, it = [], [], [], 0
+    for has_b, has_w, _, _ in spec:
+        A.append(_loss_chk(tensors[it], f"{name}: a"))
+        it += 1
+        Bs.append(_loss_chk(tensors[it], f"{name}: b") if has_b else None)
+        it += int(has_b)
+        Ws.append(_loss_chk(tensors[it], f"{name}: w") if has_w else None)
+        it += int(has_w)
+    return A, Bs, Ws
+
+
+class _PairLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, *tensors):
+        A, Bs, Ws = _pair_parse(spec, tensors)
+        nseg = len(spec)
+        n = [a.numel() for a in A]
+        inner = []
+        for a, b, w in zip(A, Bs, Ws):
+            if b is not None and b.shape != a.shape:
+                raise ValueError(f"pair_loss: a {tuple(a.shape)} and b {tuple(b.shape)} differ")
+            if w is not None and (a.dim() < 1 or a.shape[0] == 0 or w.numel() != a.shape[0]):
+                raise ValueError(f"pair_loss: {w.numel()} sample weights for a {tuple(a.shape)}")
+            inner.append(a.numel() // a.shape[0] if w is not None and a.numel() else a.numel())
+        n_t, in_t = _table(ctypes.c_longlong, n), _table(ctypes.c_longlong, inner)
+        c1_t, c2_t = _table(ctypes.c_float, [sp[2] for sp in spec]), _table(ctypes.c_float, [sp[3] for sp in spec])
+        slots = _lib.load().cocos_loss_partials(nseg, n_t)
+        dev = A[0].device
+        partials = torch.empty(max(2 * slots, 2), device=dev, dtype=torch.float64)
+        out = torch.empty((nseg + 1, 2), device=dev, dtype=torch.float32)
+        _call("pair_loss", "cocos_pair_loss_fwd", nseg, _table(ctypes.c_void_p, [a.data_ptr() for a in A]),
+              _table(ctypes.c_void_p, [_ptr(b) for b in Bs]), _table(ctypes.c_void_p, [_ptr(w) for w in Ws]), n_t, in_t, c1_t, c2_t,
+              partials.data_ptr(), out.data_ptr(), _stream())
+        ctx.save_for_backward(*A, *[b for b in Bs if b is not None], *[w for w in Ws if w is not None])
+        ctx.spec = spec
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        spec, nseg = ctx.spec, len(ctx.spec)
+        saved = list(ctx.saved_tensors)
+        A, rest = saved[:nseg], saved[nseg:]
+        Bs = [rest.pop(0) if sp[0] else None for sp in spec]
+        Ws = [rest.pop(0) if sp[1] else None for sp in spec]
+        gout = _loss_chk(gout, "pair_loss: gout")
+        pos, it = [], 1                                   # position of every a among forward's arguments
+        for has_b, has_w, _, _ in spec:
+            pos.append(it)
+            it += 1 + int(has_b) + int(has_w)
+        dA = [torch.empty_like(a) if ctx.needs_input_grad[p] else None for a, p in zip(A, pos)]
+        n = [a.numel() for a in A]
+        inner = [a.numel() // a.shape[0] if w is not None else a.numel() for a, w in zip(A, Ws)]
+        _call("pair_loss", "cocos_pair_loss_bwd", nseg, _table(ctypes.c_void_p, [a.data_ptr() for a in A]),
+              _table(ctypes.c_void_p, [_ptr(b) for b in Bs]), _table(ctypes.c_void_p, [_ptr(w) for w in Ws]),
+              _table(ctypes.c_void_p, [_ptr(d) for d in dA]), _table(ctypes.c_longlong, n), _table(ctypes.c_longlong, inner),
+              _table(ctypes.c_float, [sp[2] for sp in spec]), _table(ctypes.c_float, [sp[3] for sp in spec]), gout.data_ptr(), _stream())
+        grads = [None] * it
+        for p, d in zip(pos, dA):
+            grads[p] = d
+        return tuple(grads)
+
+
+def pair_loss(segments) -> torch.Tensor:
+    """One launch over up to 16 segments `(a, b, w, c_l1, c_mse)`: segment s contributes c_l1 * mean(w[sample] * |a - b|) and
+    c_mse * mean((a - b)^2); b None = 0, w None = 1 (w: one weight per sample of a's leading dimension).  Returns out
+    [nseg + 1, 2] fp32: (L1 term, MSE term) per segment and their sums over the segments in the last row.  fp64 sums,
+    bitwise reproducible, nothing tensor-sized saved; only the a's receive gradients (K28)."""
+    segments = list(segments)
+    if not 1 <= len(segments) <= PAIR_LOSS_MAX_SEGMENTS:
+        raise ValueError(f"pair_loss: {len(segments)} segments (1 ... {PAIR_LOSS_MAX_SEGMENTS})")
+    spec, flat = [], []
+    for a, b, w, c1, c2 in segments:
+        spec.append((b is not None, w is not None, float(c1), float(c2)))
+        flat += [t.detach() if i else t for i, t in enumerate((a, b, w)) if t is not None]
+    return _PairLoss.apply(tuple(spec), *flat)
+
+
+class _GanLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mode, label, *xs):
+        X = [_loss_chk(x, "gan_loss: x") for x in xs]
+        n_t = _table(ctypes.c_longlong, [x.numel() for x in X])
+        slots = _lib.load().cocos_loss_partials(len(X), n_t)
+        partials = torch.empty(max(slots, 1), device=X[0].device, dtype=torch.float64)
+        out = torch.empty(1, device=X[0].device, dtype=torch.float32)
+        _call("gan_loss", "cocos_gan_loss_fwd", len(X), _table(ctypes.c_void_p, [x.data_ptr() for x in X]), n_t, mode, label,
+              partials.data_ptr(), out.data_ptr(), _stream())
+        ctx.save_for_backward(*X)
+        ctx.cfg = (mode, label)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X = list(ctx.saved_tensors)
+        mode, label = ctx.cfg
+        g = _loss_chk(g, "gan_loss: g")
+        dX = [torch.empty_like(x) if ctx.needs_input_grad[2 + i] else None for i, x in enumerate(X)]
+        _call("gan_loss", "cocos_gan_loss_bwd", len(X), _table(ctypes.c_void_p, [x.data_ptr() for x in X]),
+              _table(ctypes.c_void_p, [_ptr(d) for d in dX]), _table(ctypes.c_longlong, [x.numel() for x in X]), mode, label,
+              g.data_ptr(), _stream())
+        return (None, None, *dX)
+
+
+def gan_loss(xs, mode: str, label: float = 0.0) -> torch.Tensor:
+    """GANLoss over a list of up to 8 prediction tensors in one launch: [1] = (sum_t m_t) / len(xs) with m_t the per-tensor mean
+    of the mode's term — "hinge_d_real" -mean(min(x - 1, 0)), "hinge_d_fake" -mean(min(-x - 1, 0)), "neg_mean" -mean(x),
+    "mean" mean(x), "ls" mean((x - label)^2), "bce" binary_cross_entropy_with_logits against the constant label (K28)."""
+    xs = list(xs)
+    if mode not in GAN_MODES:
+        raise ValueError(f"gan_loss: mode {mode!r}: expected one of {sorted(GAN_MODES)}")
+    if not 1 <= len(xs) <= GAN_LOSS_MAX_TENSORS:
+        raise ValueError(f"gan_loss: {len(xs)} tensors (1 ... {GAN_LOSS_MAX_TENSORS})")
+    return _GanLoss.apply(GAN_MODES[mode], float(label), *xs)
+
+
+class _MaskNll(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, gt, ref):
+        p = _loss_chk(p, "mask_nll_loss: p")
+        gt = _loss_chk(gt, "mask_nll_loss: gt", torch.int64)
+        ref = _loss_chk(ref, "mask_nll_loss: ref", torch.int64)
+        if p.dim() != 4 or gt.numel() != p.shape[0] * gt.shape[-2] * gt.shape[-1] or ref.numel() != p.shape[0] * ref.shape[-2] * ref.shape[-1]:
+            raise ValueError(f"mask_nll_loss: p {tuple(p.shape)}, gt {tuple(gt.shape)}, ref {tuple(ref.shape)}: expected [B, nc, h, w] and "
+                             "one label per pixel")
+        B, nc, h, w = p.shape
+        H, W, Hr, Wr = gt.shape[-2], gt.shape[-1], ref.shape[-2], ref.shape[-1]
+        if (h, w) != (H // 4, W // 4):
+            raise ValueError(f"mask_nll_loss: p is {h}x{w}, the {H}x{W} label map gives {H // 4}x{W // 4} at scale 0.25")
+        slots = _lib.load().cocos_mask_nll_partials(B, H, W)
+        partials = torch.empty(max(2 * slots, 2), device=p.device, dtype=torch.float64)
+        present = torch.empty((B, 8), device=p.device, dtype=torch.int32)
+        out = torch.empty(2, device=p.device, dtype=torch.float32)
+        _call("mask_nll", "cocos_mask_nll_fwd", p.data_ptr(), gt.data_ptr(), ref.data_ptr(), B, nc, H, W, Hr, Wr, partials.data_ptr(),
+              present.data_ptr(), out.data_ptr(), _stream())
+        ctx.save_for_backward(p, gt, present, out)
+        ctx.cfg = (B, nc, H, W)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        p, gt, present, out = ctx.saved_tensors
+        g = _loss_chk(g, "mask_nll_loss: g")
+        dp = torch.empty_like(p)
+        _call("mask_nll", "cocos_mask_nll_bwd", p.data_ptr(), gt.data_ptr(), present.data_ptr(), out.data_ptr() + 4, g.data_ptr(),
+              dp.data_ptr(), *ctx.cfg, _stream())
+        return dp, None, None
+
+
+def mask_nll_loss(p: torch.Tensor, gt_label: torch.Tensor, ref_label: torch.Tensor) -> torch.Tensor:
+    """The warp-mask loss of pix2pix_model.py:262-276 before `* weight_mask`, without a host read: p [B, nc, H // 4, W // 4] the
+    warped mask, gt_label [B, (1,) H, W] and ref_label [B, (1,) Hr, Wr] int64, both sampled as F.interpolate(scale_factor=0.25,
+    mode='nearest') samples them; weight 1 where the ground-truth class is not 0 and occurs in the sample's reference map;
+    sum(weight * -log(p[gt] + 1e-10)) / (sum(weight) + 1e-5) as a 0-dim tensor.  The backward writes the dense gradient of p
+    in one pass; nothing but the class sets (32 bytes per sample) and sum(weight) is saved (K28)."""
+    return _MaskNll.apply(p, gt_label, ref_label)
 
 
 def mfma_probe() -> torch.Tensor:

@@ -727,6 +727,67 @@ int cocos_relu_pool2_bwd(const float* src, const float* dr /* nullable */, const
                          float* amax_inout_dev, int BC, int H, int W, int mode, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K28 the loss block of Pix2PixModel.compute_generator_loss / compute_discriminator_loss (pix2pix_model.py:205-296,
+ *     util/util.py:36-43, networks/loss.py:15-97) as reductions: one launch per GROUP of tensors + a one-workgroup finishing
+ *     kernel in the same call.  Per-element arithmetic fp32 in the framework's order, sums fp64 (lane -> wave -> workgroup ->
+ *     one partial per workgroup, added in a fixed order: bitwise reproducible, no atomics on a value), one rounding at the end.
+ *     Nothing tensor-sized is saved: the backward entries recompute and write each gradient once; the upstream gradient is
+ *     read from device memory.  The tables (a, b, w, da, n, inner, c_l1, c_mse, x, dx) are HOST arrays of nseg entries, copied
+ *     into the kernel arguments; the tensors they name are device memory.
+ *   loss_partials(nseg, n): workgroups (= fp64 partial slots; pair_loss needs 2 doubles per slot, gan_loss 1) of a launch over
+ *                   segments of n[s] elements; 0 for invalid arguments.
+ *   pair_loss_fwd:  segment s contributes L1_s = c_l1[s] * mean(w[s][i / inner[s]] * |a - b|) and
+ *                   L2_s = c_mse[s] * mean((a - b)^2) over its n[s] elements; w (table or entry) nullable = 1, b (table or
+ *                   entry) nullable = 0, inner (table) nullable = n; inner[s] must divide n[s].  A coefficient of 0 switches
+ *                   its term off.  out [nseg + 1][2]: (L1_s, L2_s) per segment, then (sum_s L1_s, sum_s L2_s).
+ *                   1 <= nseg <= COCOS_PAIR_LOSS_MAX_SEGMENTS.  16-byte loads when a, b are 16-byte aligned (and inner % 4 == 0
+ *                   where there are weights), a scalar route otherwise.
+ *   pair_loss_bwd:  da[s] = g1 * c_l1 * w * sign(a - b) / n + g2 * c_mse * 2 (a - b) / n (sign(0) = 0), with
+ *                   g1 = gout[s][0] + gout[nseg][0], g2 = gout[s][1] + gout[nseg][1]; gout [nseg + 1][2] on the device.  A NULL
+ *                   da[s] skips the segment.  b and w get no gradient.
+ *   gan_loss_fwd:   out[0] = (sum_t m_t) / nt over nt <= COCOS_GAN_LOSS_MAX_TENSORS tensors x[t] of n[t] elements, m_t by mode:
+ *                   HINGE_D_REAL -mean(min(x - 1, 0)), HINGE_D_FAKE -mean(min(-x - 1, 0)), NEG_MEAN -mean(x), MEAN mean(x),
+ *                   LS mean((x - label)^2), BCE mean((1 - label) x - log_sigmoid(x)) (binary_cross_entropy_with_logits against
+ *                   the constant label).
+ *   gan_loss_bwd:   dx[t] = g[0] * d m_t / d x / nt; a hinge argument exactly at the kink gets half (torch.min's rule).
+ *   mask_nll_fwd:   p [B,nc,h,w] (h = H / 4, w = W / 4, floor), gt [B,H,W] and ref [B,Hr,Wr] int64 label maps, both sampled as
+ *                   F.interpolate(scale_factor = 0.25, mode = 'nearest') samples them (source index min(4 * dst, size - 1)).
+ *                   weight = 1 where the ground-truth class is not 0 and occurs in the sample's downsampled reference map;
+ *                   out[0] = sum(weight * -log(p[gt] + 1e-10)) / (sum(weight) + 1e-5), out[1] = sum(weight);
+ *                   present [B][COCOS_MASK_NLL_MAX_CLASSES / 32]: the reference's class sets, kept for the backward.  A label
+ *                   outside [0, nc) has weight 0 and is never used as an index.  partials: 2 doubles per slot of
+ *                   mask_nll_partials(B, H, W).  nc > COCOS_MASK_NLL_MAX_CLASSES or a label map (either one) smaller than 4x4 ->
+ *                   COCOS_ERR_UNSUPPORTED.
+ *   mask_nll_bwd:   dp (dense, every element written) = -g[0] / (sum_w[0] + 1e-5) / (p + 1e-10) on the ground-truth channel of
+ *                   a weighted pixel, else 0.
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_PAIR_LOSS_MAX_SEGMENTS 16
+#define COCOS_GAN_LOSS_MAX_TENSORS 8
+#define COCOS_MASK_NLL_MAX_CLASSES 256
+#define COCOS_GAN_HINGE_D_REAL 0
+#define COCOS_GAN_HINGE_D_FAKE 1
+#define COCOS_GAN_NEG_MEAN 2
+#define COCOS_GAN_MEAN 3
+#define COCOS_GAN_LS 4
+#define COCOS_GAN_BCE 5
+int cocos_loss_partials(int nseg, const long long* n);
+int cocos_pair_loss_fwd(int nseg, const float* const* a, const float* const* b /* nullable */, const float* const* w /* nullable */,
+                        const long long* n, const long long* inner /* nullable */, const float* c_l1, const float* c_mse,
+                        double* partials, float* out, cocos_stream_t stream);
+int cocos_pair_loss_bwd(int nseg, const float* const* a, const float* const* b /* nullable */, const float* const* w /* nullable */,
+                        float* const* da, const long long* n, const long long* inner /* nullable */, const float* c_l1,
+                        const float* c_mse, const float* gout, cocos_stream_t stream);
+int cocos_gan_loss_fwd(int nt, const float* const* x, const long long* n, int mode, float label, double* partials, float* out,
+                       cocos_stream_t stream);
+int cocos_gan_loss_bwd(int nt, const float* const* x, float* const* dx, const long long* n, int mode, float label, const float* g,
+                       cocos_stream_t stream);
+int cocos_mask_nll_partials(int B, int H, int W);
+int cocos_mask_nll_fwd(const float* p, const long long* gt, const long long* ref, int B, int nc, int H, int W, int Hr, int Wr,
+                       double* partials, unsigned* present, float* out, cocos_stream_t stream);
+int cocos_mask_nll_bwd(const float* p, const long long* gt, const unsigned* present, const float* sum_w, const float* g, float* dp,
+                       int B, int nc, int H, int W, cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K16 2-D convolution (cross-correlation, zero padding, like torch.nn.functional.conv2d with groups = 1, one stride /
  *     padding / dilation for both axes)
  *     as an implicit GEMM on the f16 MFMA with split operands (conv_f16x3.hip).  Replaces the nn.Conv2d calls of the
