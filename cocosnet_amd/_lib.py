@@ -270,6 +270,11 @@ _SIGNATURES = {
                            + [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _stream_t]),
     "cocos_mask_nll_bwd": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p]
                            + [ctypes.c_int] * 4 + [_stream_t]),
+    # K29: `entries` / `groups` / `n` are host arrays (cocos_adam_entry = 6, cocos_ema_entry = 3 eight-byte words per entry)
+    # (launches_out: a host int the call fills with the number of kernel launches it made)
+    "cocos_optim_constant": (ctypes.c_int, [ctypes.c_int]),
+    "cocos_adam_multi_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _stream_t]),
+    "cocos_ema_multi_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _stream_t]),
     "cocos_conv2d_out_size": (ctypes.c_int, [ctypes.c_int] * 5),
     "cocos_conv2d_kdim": (ctypes.c_int, [ctypes.c_int] * 3),
     "cocos_conv2d_fwd_f16x3": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,

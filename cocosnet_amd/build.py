@@ -59,6 +59,7 @@ HIP_SOURCES = [
     "norm_spade.hip",
     "vgg_glue.hip",
     "loss_reduce.hip",
+    "optim_step.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
 ]

@@ -88,7 +88,13 @@ class GradBuckets:
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], bucket_bytes: int = DEFAULT_BUCKET_BYTES,
-                 overlap: bool = True, group=None):
+                 overlap: bool = True, group=None, align_elems: int = 1):
+        """`align_elems`: every parameter's offset inside its flat bucket is a multiple of it (the padding elements stay zero and
+        are all-reduced along).  1 = no padding; 4 = every gradient view starts 16-byte aligned, which puts it on the 16-byte
+        route of the multi-tensor optimiser step (cocosnet_amd.optim)."""
+        if int(align_elems) < 1:
+            raise ValueError(f"GradBuckets: align_elems={align_elems}")
+        self.align_elems = int(align_elems)
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
         self.group = group
         self.overlap = bool(overlap)
@@ -99,7 +105,7 @@ class GradBuckets:
         for p in order:
             if p.dtype != torch.float32:
                 raise TypeError("GradBuckets: fp32 parameters expected (the reference trains in fp32)")
-            nbytes = p.numel() * 4
+            nbytes = self._padded(p.numel()) * 4
             if cur and cur_bytes + nbytes > bucket_bytes:
                 self.buckets.append(cur)
                 cur, cur_bytes = [], 0
@@ -111,13 +117,15 @@ class GradBuckets:
         self._flat: List[torch.Tensor] = []
         self._bucket_of, self._offset_of = {}, {}
         for i, bucket in enumerate(self.buckets):
-            flat = torch.zeros(sum(p.numel() for p in bucket), dtype=torch.float32, device=bucket[0].device)
+            # the last parameter of a bucket needs no padding behind it
+            size = sum(self._padded(p.numel()) for p in bucket[:-1]) + bucket[-1].numel()
+            flat = torch.zeros(size, dtype=torch.float32, device=bucket[0].device)
             off = 0
             for p in bucket:
                 n = p.numel()
                 p.grad = flat[off:off + n].view_as(p)
                 self._bucket_of[p], self._offset_of[p] = i, off
-                off += n
+                off += self._padded(n)
             self._flat.append(flat)
         self._pending = [len(b) for b in self.buckets]
         self._works: List = [None] * len(self.buckets)
@@ -128,6 +136,10 @@ class GradBuckets:
         if self.overlap:
             for p in self.params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad_ready))
+
+    def _padded(self, n: int) -> int:
+        a = self.align_elems
+        return -(-n // a) * a
 
     def nbytes(self) -> int:
         return sum(p.numel() * 4 for p in self.params)
@@ -144,12 +156,10 @@ class GradBuckets:
         for i, bucket in enumerate(self.buckets):
             flat = self._flat[i]
             flat.zero_()
-            off = 0
             for p in bucket:
-                n = p.numel()
+                off, n = self._offset_of[p], p.numel()
                 if p.grad is None or p.grad.data_ptr() != flat.data_ptr() + off * 4:
                     p.grad = flat[off:off + n].view_as(p)
-                off += n
         self._pending = [len(b) for b in self.buckets]
         self._works = [None] * len(self.buckets)
         self._launched = [False] * len(self.buckets)

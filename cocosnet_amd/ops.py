@@ -3386,6 +3386,79 @@ def mask_nll_loss(p: torch.Tensor, gt_label: torch.Tensor, ref_label: torch.Tens
     return _MaskNll.apply(p, gt_label, ref_label)
 
 
+# ------------------------------------------------------------------------------------------
+# K29  the tail of the step: multi-tensor Adam and EMA (pix2pix_trainer.py:57,61-62,73; generator.py:268-274)
+# ------------------------------------------------------------------------------------------
+def optim_constants() -> dict:
+    """COCOS_OPTIM_* as the loaded library was built with them: TABLE_ENTRIES (table entries per launch), TABLE_GROUPS (Adam group
+    rows per launch), CHUNK_ELEMS (elements per workgroup), ENTRY_ELEMS (elements per table entry)."""
+    f = _lib.load().cocos_optim_constant
+    return {name: f(k) for k, name in enumerate(("TABLE_ENTRIES", "TABLE_GROUPS", "CHUNK_ELEMS", "ENTRY_ELEMS"))}
+
+
+def _optim_chk(t, name: str) -> None:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.layout == torch.strided and t.is_contiguous()
+            and t.numel() > 0):
+        what = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise _lib.CocosHipError(f"{name}: expected a dense contiguous non-empty float32 CUDA/HIP tensor, got {what}; the optimiser "
+                                 "kernels have no CPU fallback")
+
+
+def adam_multi_step(params, grads, exp_avgs, exp_avg_sqs, group_rows, group_index, validate: bool = True) -> int:
+    """torch.optim.Adam's update (no amsgrad, no maximize) of every listed parameter, one launch per 64 table entries, in place:
+    one read of p, g, m, v and one write of p, m, v per element.  `group_rows`: one (step_size, bc2_sqrt, beta1, 1 - beta1, beta2,
+    1 - beta2, eps, weight_decay) per row — lr / (1 - beta1^t), sqrt(1 - beta2^t) formed in double by the caller;
+    `group_index[i]`: the row of tensor i.  The tables are host arrays: no copy to the device, no allocation, no host
+    synchronisation.  Bumps `_version` of every p, m, v.  `validate=False`: the caller has already checked that every tensor is a
+    dense contiguous fp32 tensor of its parameter's size on one device.  Returns the number of kernel launches the call made,
+    as counted by the library (K29)."""
+    params, grads, exp_avgs, exp_avg_sqs = list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)
+    n = len(params)
+    if not (n and n == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(group_index)) or not len(group_rows):
+        raise ValueError(f"adam_multi_step: {n} parameters, {len(grads)} gradients, {len(exp_avgs)} / {len(exp_avg_sqs)} moments, "
+                         f"{len(group_index)} group indices, {len(group_rows)} group rows")
+    words = []
+    for p, g, m, v, k in zip(params, grads, exp_avgs, exp_avg_sqs, group_index):
+        cnt = p.numel()
+        if validate:
+            for t, what in ((p, "p"), (g, "g"), (m, "exp_avg"), (v, "exp_avg_sq")):
+                _optim_chk(t, "adam_multi_step: " + what)
+        if validate and not (g.numel() == m.numel() == v.numel() == cnt and g.device == m.device == v.device == p.device):
+            raise ValueError(f"adam_multi_step: p {tuple(p.shape)}, g {tuple(g.shape)}, exp_avg {tuple(m.shape)}, exp_avg_sq {tuple(v.shape)}")
+        # cocos_adam_entry as six 8-byte words (little endian: group in the low half of the last one)
+        words += (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), cnt, int(k) & 0xffffffff)
+    entries = _table(ctypes.c_uint64, words)
+    rows = _table(ctypes.c_float, [float(x) for row in group_rows for x in row])
+    if len(rows) != 8 * len(group_rows):
+        raise ValueError("adam_multi_step: a group row has 8 numbers")
+    launches = ctypes.c_int(0)
+    _call("adam_multi", "cocos_adam_multi_step", ctypes.addressof(entries), n, ctypes.addressof(rows), len(group_rows),
+          ctypes.addressof(launches), _stream())
+    torch.autograd.graph.increment_version(params + exp_avgs + exp_avg_sqs)
+    return launches.value
+
+
+def ema_multi_update(shadows, params, mu: float) -> int:
+    """shadow = (1 - mu) * p + mu * shadow for every pair, in place, bitwise what the expression gives in torch ops (two rounded
+    products, one rounded sum), one launch per 64 table entries.  Bumps `_version` of every shadow.  Returns the number of kernel
+    launches the call made, as counted by the library (K29)."""
+    shadows, params = list(shadows), list(params)
+    if not shadows or len(shadows) != len(params):
+        raise ValueError(f"ema_multi_update: {len(shadows)} shadows, {len(params)} parameters")
+    words = []
+    for s, p in zip(shadows, params):
+        _optim_chk(s, "ema_multi_update: shadow")
+        _optim_chk(p, "ema_multi_update: p")
+        if s.numel() != p.numel() or s.device != p.device:
+            raise ValueError(f"ema_multi_update: shadow {tuple(s.shape)} on {s.device}, p {tuple(p.shape)} on {p.device}")
+        words += (s.data_ptr(), p.data_ptr(), s.numel())
+    entries = _table(ctypes.c_uint64, words)
+    launches = ctypes.c_int(0)
+    _call("ema_multi", "cocos_ema_multi_update", ctypes.addressof(entries), len(shadows), float(mu), ctypes.addressof(launches), _stream())
+    torch.autograd.graph.increment_version(shadows)
+    return launches.value
+
+
 def mfma_probe() -> torch.Tensor:
     """Debug: the 64x16 accumulator image of one v_mfma_f32_32x32x2_f32 (see api_common.hip)."""
     out = torch.empty((64, 16), device="cuda", dtype=torch.float32)

@@ -10,6 +10,7 @@ backend "nccl"), attached to the two optimisers so that the step functions need 
     optimizer.zero_grad()  ->  one fill per flat gradient bucket (p.grad stays a view into its bucket)
     loss.backward()        ->  every full bucket leaves for the all-reduce from autograd's hooks, during backward
     optimizer.step()       ->  first waits for the buckets and turns sums into means, then the reference's Adam step
+                               (or, after cocosnet_amd.optim.fuse_adam / fuse_trainer, the multi-tensor kernel step)
 
 Sync-BN layers (the reference without --PONO) exchange their statistics through `cocosnet_amd.dist.SyncBatchNorm2d`.
 
@@ -41,11 +42,14 @@ def broadcast_parameters(module_or_params, src: int = 0, group=None) -> None:
 
 
 def attach_gradient_exchange(optimizer: torch.optim.Optimizer, bucket_bytes: int = DEFAULT_BUCKET_BYTES,
-                             overlap: bool = True, group=None) -> GradBuckets:
+                             overlap: bool = True, group=None, align_elems: int = 1) -> GradBuckets:
     """Make `optimizer` data-parallel in place: its `zero_grad()` re-arms the gradient buckets and its `step()` first
-    completes the all-reduce (mean over ranks).  Returns the GradBuckets (also kept as `optimizer.grad_buckets`)."""
+    completes the all-reduce (mean over ranks).  Returns the GradBuckets (also kept as `optimizer.grad_buckets`).
+    `align_elems`: GradBuckets' (4 = 16-byte aligned gradient views for cocosnet_amd.optim's fused step).  Wraps whatever
+    `optimizer.step` is at the time, a step fused by `cocosnet_amd.optim.fuse_adam` included; the wrapper carries the buckets as
+    `step.cocos_grad_buckets` so that `fuse_adam` applied AFTERWARDS knows what it wraps."""
     params = [p for g in optimizer.param_groups for p in g["params"]]
-    buckets = GradBuckets(params, bucket_bytes=bucket_bytes, overlap=overlap, group=group)
+    buckets = GradBuckets(params, bucket_bytes=bucket_bytes, overlap=overlap, group=group, align_elems=align_elems)
     inner_step = optimizer.step
 
     def zero_grad(set_to_none: bool = True):
@@ -55,6 +59,7 @@ def attach_gradient_exchange(optimizer: torch.optim.Optimizer, bucket_bytes: int
         buckets.finish()
         return inner_step(closure) if closure is not None else inner_step()
 
+    step.cocos_grad_buckets = buckets
     optimizer.zero_grad = zero_grad
     optimizer.step = step
     optimizer.grad_buckets = buckets

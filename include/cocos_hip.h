@@ -788,6 +788,64 @@ int cocos_mask_nll_bwd(const float* p, const long long* gt, const unsigned* pres
                        int B, int nc, int H, int W, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K29 the tail of the training step (trainers/pix2pix_trainer.py:57,61-62,73): torch.optim.Adam over a parameter list and the
+ *     reference's EMA update (models/networks/generator.py:268-274) as multi-tensor launches (csrc/optim_step.hip).  `entries` and
+ *     `groups` are HOST arrays; the function copies them, COCOS_OPTIM_TABLE_ENTRIES at a time, into the kernel arguments of one
+ *     launch each — no copy to the device, no allocation, no synchronisation.  A tensor of more than COCOS_OPTIM_ENTRY_ELEMS
+ *     elements takes ceil(n / COCOS_OPTIM_ENTRY_ELEMS) table entries; launches = ceil(table entries / COCOS_OPTIM_TABLE_ENTRIES)
+ *     (an Adam launch also ends when its entries name more than COCOS_OPTIM_TABLE_GROUPS different groups); both calls leave
+ *     the number of kernel launches they made in *launches_out (host, nullable).  cocos_optim_constant(which) returns the
+ *     COCOS_OPTIM_* macro selected by COCOS_OPTIM_CONST_* as the library was built with it (0 for an unknown selector).  A workgroup owns COCOS_OPTIM_CHUNK_ELEMS contiguous elements; 16-byte loads and stores when the
+ *     entry's pointers are 16-byte aligned (a gradient that is only 4-byte aligned is read dword by dword, the rest stays
+ *     16-byte), dword accesses otherwise.  Every tensor fp32, dense, contiguous.
+ *   adam_multi_step:  per element, fp32, each operation rounded on its own, correctly rounded sqrt and division (Adam without
+ *                   amsgrad / maximize, torch's single-tensor operation order):
+ *                     g' = g + weight_decay * p                              (only if weight_decay != 0)
+ *                     m  = m + one_minus_beta1 * (g' - m)                    (beta1 == 0: m = g', m is not read)
+ *                     v  = beta2 * v + (one_minus_beta2 * g') * g'
+ *                     p  = p - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ *                   p, m, v are updated in place, g is only read.  beta outside [0, 1), eps < 0 or bc2_sqrt <= 0 (a step
+ *                   count of 0) -> COCOS_ERR_UNSUPPORTED.
+ *   ema_multi_update: shadow = fl(fl((float)(1.0 - mu) * p) + fl((float)mu * shadow)) in place: bitwise what
+ *                   `(1.0 - mu) * p + mu * shadow` gives in torch for a Python float mu (hence the double).
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_OPTIM_TABLE_ENTRIES 64          /* table entries (tensors or pieces of one) per launch */
+#define COCOS_OPTIM_TABLE_GROUPS 8            /* different cocos_adam_group rows per launch */
+#define COCOS_OPTIM_CHUNK_ELEMS 4096          /* elements per workgroup */
+#define COCOS_OPTIM_ENTRY_ELEMS (1 << 24)     /* elements per table entry (a multiple of the chunk) */
+typedef struct cocos_adam_entry {
+    float* p;          /* parameter (device), updated in place */
+    const float* g;    /* gradient (device), read only; may be 4-byte aligned */
+    float* m;          /* exp_avg (device), updated in place */
+    float* v;          /* exp_avg_sq (device), updated in place */
+    long long n;       /* elements, >= 1 */
+    int group;         /* index into groups */
+    int reserved;      /* pads the entry to 48 bytes; ignored */
+} cocos_adam_entry;
+typedef struct cocos_adam_group {          /* every field formed in double on the host and rounded once to fp32 */
+    float step_size;                       /* lr / (1 - beta1^t) */
+    float bc2_sqrt;                        /* sqrt(1 - beta2^t) */
+    float beta1, one_minus_beta1;
+    float beta2, one_minus_beta2;
+    float eps;
+    float weight_decay;                    /* L2 (added to the gradient), not decoupled */
+} cocos_adam_group;
+typedef struct cocos_ema_entry {
+    float* shadow;     /* running average (device), updated in place */
+    const float* p;    /* parameter (device), read only */
+    long long n;       /* elements, >= 1 */
+} cocos_ema_entry;
+#define COCOS_OPTIM_CONST_TABLE_ENTRIES 0
+#define COCOS_OPTIM_CONST_TABLE_GROUPS 1
+#define COCOS_OPTIM_CONST_CHUNK_ELEMS 2
+#define COCOS_OPTIM_CONST_ENTRY_ELEMS 3
+int cocos_optim_constant(int which);
+int cocos_adam_multi_step(const cocos_adam_entry* entries, int n_entries, const cocos_adam_group* groups, int n_groups,
+                          int* launches_out /* host, nullable */, cocos_stream_t stream);
+int cocos_ema_multi_update(const cocos_ema_entry* entries, int n_entries, double mu, int* launches_out /* host, nullable */,
+                           cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K16 2-D convolution (cross-correlation, zero padding, like torch.nn.functional.conv2d with groups = 1, one stride /
  *     padding / dilation for both axes)
  *     as an implicit GEMM on the f16 MFMA with split operands (conv_f16x3.hip).  Replaces the nn.Conv2d calls of the
