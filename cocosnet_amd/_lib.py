@@ -209,6 +209,10 @@ _SIGNATURES = {
     "cocos_upsample_nearest_bwd": (ctypes.c_int, [_c_float_p, _c_float_p] + [ctypes.c_int] * 4 + [_stream_t]),
     "cocos_warp_head_fwd": (ctypes.c_int, [_c_float_p, _c_float_p] + [ctypes.c_int] * 6 + [_stream_t]),
     "cocos_warp_head_bwd": (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 6 + [_stream_t]),
+    "cocos_warp_head_fwd_ex": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 7 + [_stream_t]),
+    "cocos_warp_head_bwd_ex": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 7 + [_stream_t]),
+    "cocos_warp_values_patch_amax": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 6 + [_c_float_p, _stream_t]),
+    "cocos_warp_head_bilinear_tap": (ctypes.c_float, [ctypes.c_int] * 4),
     "cocos_split_f16_transpose_pair": (ctypes.c_int, ([_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p]) * 2
                                        + [ctypes.c_int] * 4 + [_stream_t]),
     "cocos_warp_values": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 6 + [_stream_t]),

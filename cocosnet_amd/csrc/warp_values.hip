@@ -82,6 +82,40 @@ __global__ __launch_bounds__(256) void warp_values_kernel(const float* __restric
   }
 }
 
+// --warp_patch: the d x d patch of every image channel laid out along the channel axis (F.unfold(img, d, stride=d), :311) in front
+// of the nearest-sampled label channels.  One thread per output element, neighbouring lanes read addresses d floats apart.
+__global__ __launch_bounds__(256) void warp_values_patch_kernel(const float* __restrict__ img, const float* __restrict__ seg,
+                                                                float* __restrict__ out, int Ci, int Cs, int h, int w, int d,
+                                                                size_t n, unsigned* __restrict__ amax) {
+  float vmax = 0.f;
+  const size_t stride = (size_t)gridDim.x * 256;
+  const int W = w * d, H = h * d, Cp = Ci * d * d;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const int x = (int)(i % w);
+    size_t r = i / w;
+    const int y = (int)(r % h);
+    r /= h;
+    const int c = (int)(r % (Cp + Cs));
+    const size_t b = r / (Cp + Cs);
+    float v;
+    if (c < Cp) {
+      const int cc = c / (d * d), ij = c - cc * d * d, a = ij / d, e = ij - a * d;
+      v = img[((b * Ci + cc) * H + (size_t)y * d + a) * W + (size_t)x * d + e];
+    } else {
+      v = seg[((b * Cs + (c - Cp)) * H + (size_t)y * d) * W + (size_t)x * d];
+    }
+    out[i] = v;
+    vmax = fmaxf(vmax, fabsf(v));
+  }
+  if (amax) {
+      __shared__ float red[4];
+      vmax = wave_max_dpp(vmax);
+      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = vmax;
+      __syncthreads();
+      if (threadIdx.x == 0) atomicMax(amax, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
+  }
+}
+
 }  // namespace cocos
 
 // out [B, Ci+Cs, H/down, W/down]: channels [0,Ci) = down x down mean of img [B,Ci,H,W]; channels [Ci,Ci+Cs) =
@@ -115,4 +149,24 @@ extern "C" int cocos_warp_values_amax(const float* img, const float* seg, float*
                                       int down, float* amax_inout_dev, cocos_stream_t stream) {
     COCOS_REQUIRE(amax_inout_dev, COCOS_ERR_INVALID, "warp_values_amax: null amax cell");
     return warp_values_impl(img, seg, out, B, Ci, Cs, H, W, down, amax_inout_dev, stream);
+}
+
+// out [B, Ci*down^2 + Cs, H/down, W/down]: channels [0, Ci*down^2) = F.unfold(img, down, stride=down), then the sampled label
+// channels; max|out| into the cell when one is given.
+extern "C" int cocos_warp_values_patch_amax(const float* img, const float* seg, float* out, int B, int Ci, int Cs, int H, int W,
+                                            int down, float* amax_inout_dev, cocos_stream_t stream) {
+    using namespace cocos;
+    COCOS_REQUIRE(out && (img || Ci == 0) && (seg || Cs == 0), COCOS_ERR_INVALID, "warp_values_patch: null pointer");
+    COCOS_REQUIRE(B >= 1 && Ci >= 0 && Cs >= 0 && Ci + Cs >= 1 && H >= 1 && W >= 1 && down >= 1 && down <= 64, COCOS_ERR_INVALID,
+                  "warp_values_patch: bad dims B=%d Ci=%d Cs=%d H=%d W=%d down=%d", B, Ci, Cs, H, W, down);
+    COCOS_REQUIRE(H % down == 0 && W % down == 0, COCOS_ERR_UNSUPPORTED,
+                  "warp_values_patch: %dx%d is not a multiple of down=%d", H, W, down);
+    const size_t n = (size_t)B * ((size_t)Ci * down * down + Cs) * (H / down) * (W / down);
+    COCOS_REQUIRE((size_t)Ci * down * down + Cs <= 0x7fffffffull && (n + 255) / 256 <= 0x7fffffffull, COCOS_ERR_UNSUPPORTED,
+                  "warp_values_patch: tensor too large");
+    const size_t blocks = std::min<size_t>(2048, (n + 255) / 256);
+    hipLaunchKernelGGL(warp_values_patch_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), img, seg, out, Ci, Cs,
+                       H / down, W / down, down, n, reinterpret_cast<unsigned*>(amax_inout_dev));
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
 }

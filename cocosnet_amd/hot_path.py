@@ -323,11 +323,15 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
 
     # ---- R1: exemplar colours (+ direct mask) through the row softmax  (:309-336) ----------------
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
-    fused_values = (direct_mask and not cfg.warp_patch and _hip_fp32(ref_img) and _hip_fp32(ref_seg_map)
-                    and not (ref_img.requires_grad or ref_seg_map.requires_grad) and H % down == 0 and W % down == 0)
+    # K30: the head and the value kernels on every flag set (ops.WARP_HEAD_MODES; CPU / non-fp32 tensors keep the framework route)
+    modes = ops.WARP_HEAD_MODES and _hip_fp32(theta_raw) and _hip_fp32(ref_img)
+    fused_values = ((modes or (direct_mask and not cfg.warp_patch)) and _hip_fp32(ref_img) and not ref_img.requires_grad
+                    and (not direct_mask or (_hip_fp32(ref_seg_map) and not ref_seg_map.requires_grad))
+                    and H % down == 0 and W % down == 0)
     if fused_values:
-        n_ref = ref_img.shape[1]
-        v1 = _flat(ops.warp_values(ref_img, ref_seg_map, down))       # pooled image + sampled mask in one kernel (K14)
+        # pooled image (or its patches, --warp_patch) + sampled mask in one kernel (K14)
+        v1 = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down, patch=cfg.warp_patch))
+        n_ref = ref_img.shape[1] * (down * down if cfg.warp_patch else 1)
     else:
         if cfg.warp_patch:
             ref = F.unfold(ref_img, down, stride=down)                    # [B, 3*down^2, HW]
@@ -340,20 +344,38 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
             v_r1.append(_flat(ref_seg))
         v1 = torch.cat(v_r1, dim=1) if len(v_r1) > 1 else ref
     o_r1 = attn.rows(v1)
+    want_cycle = cfg.warp_cycle_w > 0
+    show_bi = (not cfg.isTrain) and cfg.show_corr
     # round 6: when the row pass's output goes to the up-sampling and the direct mask and nowhere else, both come from one op whose
-    # backward hands the K2 / K19 backward its d out, max|d out| and D in ONE kernel (ops.warp_head)
-    head = (direct_mask and not cfg.warp_patch and not cfg.warp_bilinear and not (cfg.warp_cycle_w > 0)
-            and not ((not cfg.isTrain) and cfg.show_corr) and ops.warp_head_ok(o_r1, n_ref, fh, fw, down))
-    if head:
+    # backward hands the K2 / K19 backward its d out, max|d out| and D in ONE kernel (ops.warp_head).  K30: the same op up-samples
+    # bilinearly or folds patches, works without mask channels, and with cycle terms also returns the image channels as a view whose
+    # gradient (from the column pass) its backward adds in the same pass.
+    head_mode = "patch" if cfg.warp_patch else ("bilinear" if cfg.warp_bilinear else "nearest")
+    if modes:
+        head = (ops.warp_head_ok(o_r1, n_ref, fh, fw, down, head_mode) and (fh * down, fw * down) == (H, W)
+                and (direct_mask or n_ref == o_r1.shape[1]))
+    else:
+        head = (direct_mask and not cfg.warp_patch and not cfg.warp_bilinear and not want_cycle
+                and not show_bi and ops.warp_head_ok(o_r1, n_ref, fh, fw, down) and n_ref < o_r1.shape[1])
+    if head and not modes:
         out["warp_out"], out["warp_mask"] = ops.warp_head(o_r1, n_ref, fh, fw, down)
         y = y_img = None          # (only the cycle terms read them: excluded above)
+    elif head:
+        want_bi = show_bi and head_mode == "nearest"
+        res = ops.warp_head(o_r1, n_ref, fh, fw, down, mode=head_mode, want_y=want_cycle, want_bi=want_bi)
+        if show_bi:               # (bilinear / patch mode: warp_out is the side output already, :326-327)
+            out["warp_out_bi"] = res[-1] if want_bi else res[0]
+        out["warp_out"] = y_img = res[0]
+        if direct_mask:
+            out["warp_mask"] = res[1]
+        y = res[2] if want_cycle else None
     else:
         y, o_mask = _split_channels(o_r1, n_ref) if direct_mask else (o_r1, None)   # [B, ch, HW], [B, nc, HW]
         if cfg.warp_patch:
             y_img = F.fold(y, (H, W), down, stride=down)                  # reference hard-codes 256 (:321)
         else:
             y_img = y.reshape(B, n_ref, fh, fw)
-        if (not cfg.isTrain) and cfg.show_corr:
+        if show_bi:
             out["warp_out_bi"] = y_img if cfg.warp_patch else _upsample(y_img, down, True)
         out["warp_out"] = y_img if cfg.warp_patch else _upsample(y_img, down, cfg.warp_bilinear)
         if direct_mask:
@@ -361,24 +383,37 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
 
     # ---- C1: everything that goes through the column softmax  (:337-343, :350-367) ---------------
     cycle_mask = (not direct_mask) and cfg.warp_mask_losstype == "cycle"
-    want_cycle = cfg.warp_cycle_w > 0
     want_two = want_cycle and cfg.two_cycle and not cfg.warp_patch
     v_c1, names = [], []
     if cycle_mask:
         seg = F.interpolate(seg_map, scale_factor=1 / down, mode="nearest")
         v_c1.append(_flat(seg)); names.append("mask")
     if want_cycle:
-        yy = F.unfold(y_img, down, stride=down) if cfg.warp_patch else y
+        # (:353 unfolds the fold of y: non-overlapping patches, so that is y itself, bit for bit)
+        yy = F.unfold(y_img, down, stride=down) if cfg.warp_patch and not modes else y
         v_c1.append(yy); names.append("cycle")
     if want_two:
-        v_c1.append(_flat(F.avg_pool2d(real_img, down))); names.append("i2r")
+        if modes and _hip_fp32(real_img) and not real_img.requires_grad and H % down == 0 and W % down == 0:
+            v_c1.append(_flat(ops.warp_values(real_img, None, down))); names.append("i2r")
+        else:
+            v_c1.append(_flat(F.avg_pool2d(real_img, down))); names.append("i2r")
     if v_c1:
         o_c1 = attn.cols(torch.cat(v_c1, dim=1) if len(v_c1) > 1 else v_c1[0])
-        parts = dict(zip(names, torch.split(o_c1, [t.shape[1] for t in v_c1], dim=1)))
+        # K30: the fold of the column pass's output (:357) is the head in patch mode without mask channels — its backward leaves
+        # d o, max|d o| and D for the column pass's backward
+        cycle_head = (modes and cfg.warp_patch and names == ["cycle"] and (fh * down, fw * down) == (H, W)
+                      and ops.warp_head_ok(o_c1, o_c1.shape[1], fh, fw, down, "patch"))
+        if cycle_head:
+            parts = {"cycle": o_c1}
+        else:
+            parts = dict(zip(names, torch.split(o_c1, [t.shape[1] for t in v_c1], dim=1)))
         if want_cycle:
             wc = parts["cycle"]
-            out["warp_cycle"] = (F.fold(wc, (H, W), down, stride=down) if cfg.warp_patch
-                                 else wc.reshape(B, -1, fh, fw))
+            if cycle_head:
+                out["warp_cycle"] = ops.warp_head(wc, wc.shape[1], fh, fw, down, mode="patch")[0]
+            else:
+                out["warp_cycle"] = (F.fold(wc, (H, W), down, stride=down) if cfg.warp_patch
+                                     else wc.reshape(B, -1, fh, fw))
         if want_two:
             out["warp_i2r"] = parts["i2r"].reshape(B, -1, fh, fw)
 

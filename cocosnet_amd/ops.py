@@ -1174,6 +1174,9 @@ def proj1x1(x, weight, bias=None):
 # ------------------------------------------------------------------------------------------
 #: False: the fused match_kernel-1 path projects with K0 and normalises with K1 in separate launches (the round-5 chain; A/B runs)
 PROJ_NORM_FUSED = os.environ.get("COCOS_PROJ_NORM_FUSED", "1") != "0"
+#: K30: the row pass's head (ops.warp_head) also on the --warp_bilinear / --warp_patch / --warp_cycle_w flag sets and on passes without
+#: mask channels, and warp_values without a direct mask / in patch mode (hot_path.py).  False: the framework ops of round 6.
+WARP_HEAD_MODES = os.environ.get("COCOS_WARP_HEAD_MODES", "1") != "0"
 #: False: the projections' backward runs as round 5's chain (K1 backward / K12 backward + autograd's add -> max|.| -> input gradient ->
 #: weight gradient); True: K24 (cocos_proj_bwd_input_f16x3) folds everything in front of the input gradient into it and the weight
 #: gradient rebuilds its dy on the fly (A/B runs)
@@ -2332,7 +2335,8 @@ class _LogitsSoftmaxWarp(torch.autograd.Function):
             dlg = torch.empty_like(logits_t)
             if ctx.split:
                 cvp = (Cv + 31) // 32 * 32
-                gph, gpl, gs = split_f16(dout, True, cpad=cvp, amax=absmax(dout))
+                g_amax = _recall_amax(dout)          # left by warp_head's backward, else one pass
+                gph, gpl, gs = split_f16(dout, True, cpad=cvp, amax=absmax(dout) if g_amax is None else g_amax)
                 vph, vpl, v_scale = split_f16(v, True, cpad=cvp, amax=ctx.v_amax)
                 _call("logits_softmax_warp_bwd", "cocos_logits_softmax_warp_bwd_f16x3", logits_t.data_ptr(),
                       vph.data_ptr(), vpl.data_ptr(), gph.data_ptr(), gpl.data_ptr(), gs.data_ptr(), v_scale.data_ptr(),
@@ -2775,20 +2779,79 @@ class _WarpHead(torch.autograd.Function):
         return dout, None, None, None, None
 
 
-def warp_head_ok(o: torch.Tensor, n_img: int, h: int, w: int, down: int) -> bool:
-    """Shapes cocos_warp_head_fwd / _bwd take: fp32 on the GPU, some image and some mask channels, grid width a multiple of 4."""
-    return (o.is_cuda and o.dtype == torch.float32 and o.dim() == 3 and 0 < n_img < o.shape[1] and w % 4 == 0
-            and o.shape[2] == h * w and o.shape[0] <= 65535)
+_HEAD_MODES = {"nearest": 0, "bilinear": 1, "patch": 2}      # COCOS_WARP_HEAD_* of cocos_hip.h
 
 
-def warp_head(o, n_img: int, h: int, w: int, down: int):
-    """(warp_out [B,n_img,h*down,w*down], warp_mask [B,C-n_img,h,w]) of the row pass's output o [B,C,h*w]: see _WarpHead."""
-    return _WarpHead.apply(o, int(n_img), int(h), int(w), int(down))
+class _WarpHeadModes(torch.autograd.Function):
+    """_WarpHead for every flag set (K30): warp_out by nearest / bilinear up-sampling or as the fold of non-overlapping patches, the
+    mask channels (if any) as a view, optionally the image channels themselves as a view (`want_y`: the column pass's values under
+    --warp_cycle_w) and the bilinear side output of inference --show_corr (`want_bi`, nearest mode).  Backward: ONE kernel
+    (cocos_warp_head_bwd_ex) sums both gradients of the image channels — the adjoint of the up-sampling, as a fixed-order gather, and
+    d y — next to d warp_mask, and leaves max|d o| and D for the K2 / K19 backward as _WarpHead does."""
+
+    @staticmethod
+    def forward(ctx, o, n_img: int, h: int, w: int, down: int, mode: str, want_y: bool, want_bi: bool):
+        o = _chk(o, "warp_head: o")
+        B, C, N = o.shape
+        m = _HEAD_MODES[mode]
+        planes = n_img // (down * down) if mode == "patch" else n_img
+        y = torch.empty((B, planes, h * down, w * down), device=o.device, dtype=torch.float32)
+        y_bi = torch.empty_like(y) if want_bi else None
+        _call("warp_head_fwd", "cocos_warp_head_fwd_ex", o.data_ptr(), y.data_ptr(), _ptr(y_bi), B, n_img, C, h, w, down, m, _stream())
+        ctx.save_for_backward(o)
+        ctx.cfg = (int(n_img), int(h), int(w), int(down), m)
+        return (y, o[:, n_img:].view(B, C - n_img, h, w) if n_img < C else None, o[:, :n_img] if want_y else None, y_bi)
+
+    @staticmethod
+    def backward(ctx, g_img, g_mask, g_y, g_bi):
+        o, = ctx.saved_tensors
+        n_img, h, w, down, m = ctx.cfg
+        B, C, N = o.shape
+        g_img, g_mask, g_y, g_bi = (None if g is None else _chk(g, "warp_head: gradient") for g in (g_img, g_mask, g_y, g_bi))
+        dout = torch.empty_like(o)
+        drow = torch.empty((B, N), device=o.device, dtype=torch.float32)
+        if g_bi is not None:        # (a loss on the inference side output: its adjoint first, then added like a second d y)
+            t = torch.empty((B, n_img, N), device=o.device, dtype=torch.float32)
+            o_img = o[:, :n_img].contiguous()
+            _call("warp_head_bwd", "cocos_warp_head_bwd_ex", g_bi.data_ptr(), None, _ptr(g_y), o_img.data_ptr(),
+                  t.data_ptr(), drow.data_ptr(), _zero_cell(o.device).data_ptr(), B, n_img, 0, h, w, down, _HEAD_MODES["bilinear"],
+                  _stream())
+            g_y = t
+        cell = _zero_cell(o.device)
+        _call("warp_head_bwd", "cocos_warp_head_bwd_ex", _ptr(g_img), _ptr(g_mask), _ptr(g_y), o.data_ptr(), dout.data_ptr(),
+              drow.data_ptr(), cell.data_ptr(), B, n_img, C - n_img, h, w, down, m, _stream())
+        if PRECISION == "f16x3":
+            _remember_amax(dout, cell)
+        _tls.known_rowdot = (weakref.ref(dout), dout._version, o.data_ptr(), drow)
+        return dout, None, None, None, None, None, None, None
 
 
-def warp_values(img, seg_map, down: int):
+def warp_head_ok(o: torch.Tensor, n_img: int, h: int, w: int, down: int, mode: str = "nearest") -> bool:
+    """Shapes cocos_warp_head_fwd_ex / _bwd_ex take: fp32 on the GPU, some image channels, grid width a multiple of 4; in patch mode the
+    image channels are whole down x down patches.  (n_img == C: no mask channels.)"""
+    return (mode in _HEAD_MODES and o.is_cuda and o.dtype == torch.float32 and o.dim() == 3 and 0 < n_img <= o.shape[1] and w % 4 == 0
+            and o.shape[2] == h * w and o.shape[0] <= 65535 and down >= 1 and (mode != "patch" or n_img % (down * down) == 0)
+            and (mode == "nearest" and n_img < o.shape[1] or o.is_contiguous()))
+
+
+def warp_head(o, n_img: int, h: int, w: int, down: int, mode: str = "nearest", want_y: bool = False, want_bi: bool = False):
+    """(warp_out, warp_mask or None[, y_view][, warp_out_bi]) of a row / column pass's output o [B,C,h*w]: see _WarpHead and
+    _WarpHeadModes.  warp_out is [B,n_img,h*down,w*down] (mode 'nearest' | 'bilinear') or the fold [B,n_img/down^2,h*down,w*down]
+    ('patch'); warp_mask [B,C-n_img,h,w] and y_view [B,n_img,h*w] are views of o."""
+    if mode not in _HEAD_MODES:
+        raise ValueError(f"warp_head: unknown mode {mode!r}")
+    if mode == "nearest" and not want_y and not want_bi and n_img < o.shape[1]:
+        return _WarpHead.apply(o, int(n_img), int(h), int(w), int(down))
+    if want_bi and mode != "nearest":
+        raise ValueError("warp_head: want_bi goes with mode='nearest' (the other modes' warp_out is the side output already)")
+    res = _WarpHeadModes.apply(o, int(n_img), int(h), int(w), int(down), mode, bool(want_y), bool(want_bi))
+    return res[:2] + ((res[2],) if want_y else ()) + ((res[3],) if want_bi else ())
+
+
+def warp_values(img, seg_map, down: int, patch: bool = False):
     """torch.cat((F.avg_pool2d(img, down), F.interpolate(seg_map, scale_factor=1/down, mode='nearest')), 1) in one
     kernel (K14; correspondence.py:314, :318-319, :331-334): img [B,Ci,H,W], seg_map [B,Cs,H,W] or None -> [B,Ci+Cs,
+    H/down,W/down].  patch=True (--warp_patch, :311): the image part is F.unfold(img, down, stride=down) instead, [B,Ci*down^2+Cs,
     H/down,W/down].  Forward only: the exemplar image and its label map are data (callers with gradients use torch)."""
     img = _chk(img, "warp_values: img")
     B, Ci, H, W = img.shape
@@ -2796,6 +2859,14 @@ def warp_values(img, seg_map, down: int):
     Cs = 0 if seg is None else seg.shape[1]
     if seg is not None and (seg.shape[0], seg.shape[2], seg.shape[3]) != (B, H, W):
         raise ValueError(f"warp_values: seg_map {tuple(seg.shape)} does not match img {tuple(img.shape)}")
+    if patch:
+        out = torch.empty((B, Ci * down * down + Cs, H // down, W // down), device=img.device, dtype=torch.float32)
+        cell = _zero_cell(out.device) if PRECISION == "f16x3" else None
+        _call("warp_values", "cocos_warp_values_patch_amax", img.data_ptr(), _ptr(seg), out.data_ptr(), B, Ci, Cs, H, W, int(down),
+              _ptr(cell), _stream())
+        if cell is not None:
+            _remember_amax(out, cell)
+        return out
     out = torch.empty((B, Ci + Cs, H // down, W // down), device=img.device, dtype=torch.float32)
     if PRECISION == "f16x3":      # max|V| as a by-product: the consumer (the K2 forward's f16 split of V) picks it up
         cell = _zero_cell(out.device)

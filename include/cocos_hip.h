@@ -544,6 +544,27 @@ int cocos_upsample_nearest_bwd(const float* dy, float* dx, int planes, int h, in
 int cocos_warp_head_fwd(const float* o, float* y, int B, int Ci, int C, int h, int w, int down, cocos_stream_t stream);
 int cocos_warp_head_bwd(const float* g_img, const float* g_mask, const float* o, float* dout, float* drow, float* amax_inout_dev,
                         int B, int Ci, int Cs, int h, int w, int down, cocos_stream_t stream);
+/* K30: the same head for --warp_bilinear and --warp_patch (:184-186, :321, :357) and for row / column passes without mask channels.
+ *   mode = COCOS_WARP_HEAD_NEAREST   y = nearest up-sampling (cocos_warp_head_fwd / _bwd are this mode)
+ *          COCOS_WARP_HEAD_BILINEAR  y = F.interpolate(o[:, :Ci], scale_factor=down, mode="bilinear", align_corners=False); the
+ *                                    backward is its adjoint as a gather in a fixed order (no atomics: reproducible bit for bit)
+ *          COCOS_WARP_HEAD_PATCH     y [B,Ci/down^2,h*down,w*down] = F.fold(o[:, :Ci], (h*down, w*down), down, stride=down), a copy:
+ *                                    y[b,c,yy*down+i,xx*down+j] = o[b, c*down^2 + i*down + j, yy*w + xx]; Ci % down^2 == 0
+ *   cocos_warp_head_fwd_ex: y_bi (optional, nearest mode only) receives the bilinear up-sampling from the same launch (the inference
+ *       --show_corr pair).  Ci <= C, (w*down) % 4 == 0, outputs 16-byte aligned.
+ *   cocos_warp_head_bwd_ex: as cocos_warp_head_bwd, and g_y [B,Ci,h*w] (optional) is added to rows [0,Ci) of dout before drow and
+ *       max|dout| are taken — the image channels' second gradient when they are also the column pass's values (:353-362).  g_img,
+ *       g_mask and g_y may each be NULL (a zero gradient), Cs may be 0.  w % 4 == 0, tensors 16-byte aligned. */
+#define COCOS_WARP_HEAD_NEAREST 0
+#define COCOS_WARP_HEAD_BILINEAR 1
+#define COCOS_WARP_HEAD_PATCH 2
+int cocos_warp_head_fwd_ex(const float* o, float* y, float* y_bi, int B, int Ci, int C, int h, int w, int down, int mode,
+                           cocos_stream_t stream);
+int cocos_warp_head_bwd_ex(const float* g_img, const float* g_mask, const float* g_y, const float* o, float* dout, float* drow,
+                           float* amax_inout_dev, int B, int Ci, int Cs, int h, int w, int down, int mode, cocos_stream_t stream);
+/* Host-side: the bilinear backward's compile-time tap table (down = 2, 4): weight of output index down*x - down/2 + idx, idx in
+ * [0, 2*down), on source index x; first / last = x is the first / last source index (clamped taps).  -1: no table for this scale. */
+float cocos_warp_head_bilinear_tap(int down, int idx, int first, int last);
 
 /* ---------------------------------------------------------------------------------------
  * K14  value tensor of the first row pass in one kernel (correspondence.py:314, :318-319, :331-334):
@@ -557,6 +578,11 @@ int cocos_warp_values(const float* img, const float* seg, float* out, int B, int
  * of the kernel that writes V. */
 int cocos_warp_values_amax(const float* img, const float* seg, float* out, int B, int Ci, int Cs, int H, int W,
                            int down, float* amax_inout_dev, cocos_stream_t stream);
+/* --warp_patch (:311): out[b, 0:Ci*down^2] = F.unfold(img, down, stride=down) — out[b, c*down^2 + i*down + j, y, x] =
+ * img[b, c, y*down + i, x*down + j], a copy — followed by the Cs nearest-sampled label channels as above;
+ * out [B, Ci*down^2 + Cs, H/down, W/down].  amax_inout_dev may be NULL (no maximum wanted). */
+int cocos_warp_values_patch_amax(const float* img, const float* seg, float* out, int B, int Ci, int Cs, int H, int W,
+                                 int down, float* amax_inout_dev, cocos_stream_t stream);
 
 /* Plane preparation folded into kernels that already touch the data (csrc/plane_prep.hip):
  *   cocos_concat2_amax: out[b] = [a[b] | b[b]] (torch.cat of two [B, *] fp32 tensors along dim 1; na, nb = elements per
