@@ -279,6 +279,11 @@ _SIGNATURES = {
     "cocos_optim_constant": (ctypes.c_int, [ctypes.c_int]),
     "cocos_adam_multi_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _stream_t]),
     "cocos_ema_multi_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _stream_t]),
+    # K32: `entries` are host arrays (cocos_wprep_absmax_entry = 3, cocos_wprep_planes_entry = 8 eight-byte words per entry)
+    "cocos_weight_prepare_constant": (ctypes.c_int, [ctypes.c_int]),
+    "cocos_weight_absmax_multi_workspace_floats": (ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_int]),
+    "cocos_weight_absmax_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _c_float_p, ctypes.c_longlong, ctypes.c_void_p, _stream_t]),
+    "cocos_weight_planes_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _stream_t]),
     "cocos_conv2d_out_size": (ctypes.c_int, [ctypes.c_int] * 5),
     "cocos_conv2d_kdim": (ctypes.c_int, [ctypes.c_int] * 3),
     "cocos_conv2d_fwd_f16x3": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,

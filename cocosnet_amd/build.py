@@ -60,6 +60,7 @@ HIP_SOURCES = [
     "vgg_glue.hip",
     "loss_reduce.hip",
     "optim_step.hip",
+    "weight_prepare_multi.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
 ]

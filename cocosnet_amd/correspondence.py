@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn import init
 
-from . import ops
+from . import inference, ops
 from .hot_path import HotPathConfig, correspondence_hot_path
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
@@ -163,11 +163,13 @@ class NoVGGCorrespondence(NetworkBase):
         else:
             cont, ref = self.layer(cont_in), self.layer(ref_in)
         if cont.is_cuda and cont.dtype == torch.float32:   # :272 / :282 on K0 (same parameters: checkpoints are unaffected)
+            # (frozen-weight inference: the projections' records, when freeze() attached them and this call may use them)
+            rt, rp = inference.usable_record(self.theta), inference.usable_record(self.phi)
             if lazy:      # forward(): the hot path decides — K23 (projection + K1 fused, no fp32 theta / phi) or K0 (ops.LazyProj1x1)
-                return (ops.LazyProj1x1(cont, self.theta.weight, self.theta.bias),
-                        ops.LazyProj1x1(ref, self.phi.weight, self.phi.bias))
-            return (ops.proj1x1(cont, self.theta.weight, self.theta.bias),
-                    ops.proj1x1(ref, self.phi.weight, self.phi.bias))
+                return (ops.LazyProj1x1(cont, self.theta.weight, self.theta.bias, rt),
+                        ops.LazyProj1x1(ref, self.phi.weight, self.phi.bias, rp))
+            return (ops.proj1x1(cont, self.theta.weight, self.theta.bias, rt),
+                    ops.proj1x1(ref, self.phi.weight, self.phi.bias, rp))
         return self.theta(cont), self.phi(ref)   # CPU / fp64: producer parity tests only; the hot path needs a GPU and fp32
 
     def forward(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, detach_flag=False,

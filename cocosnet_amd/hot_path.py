@@ -163,7 +163,9 @@ class _BoxedCorr:
             # round 6: projection + K12 statistics as ONE autograd node per tensor (ops.proj_unfold3_stats): its backward folds K12's
             # backward and the sum of theta_raw's two gradients into the projection's input gradient (K24)
             if ops.PROJ_PRECISION == "f16x3":      # max|.| of both feature tensors and both weights in one launch
-                ops.prefetch_amax([theta_raw.x, theta_raw.weight.reshape(C, -1), phi_raw.x, phi_raw.weight.reshape(C, -1)])
+                # (a projection with a frozen record brings its weight's cell: only the features are measured)
+                ops.prefetch_amax([theta_raw.x, None if theta_raw.prepared is not None else theta_raw.weight.reshape(C, -1),
+                                   phi_raw.x, None if phi_raw.prepared is not None else phi_raw.weight.reshape(C, -1)])
             theta_raw, mu, a = ops.proj_unfold3_stats(theta_raw, self.kc)
             phi_raw, nu, b = ops.proj_unfold3_stats(phi_raw, self.kc)
             self._cache["q"], self._cache["k"] = (mu, a), (nu, b)

@@ -1035,9 +1035,10 @@ def channel_sum(dy: torch.Tensor) -> torch.Tensor:
     return db
 
 
-def _proj1x1_forward(x, weight, bias, need_t: bool):
+def _proj1x1_forward(x, weight, bias, need_t: bool, prepared=None):
     """y = conv1x1(x, weight, bias) on K0 -> (y, x, w2, state): `state` = what the backward needs (split / stream flags, the max|.|
-    cells, the transposed weight planes when `need_t`).  Shared by _Proj1x1 and _ProjUnfoldStats."""
+    cells, the transposed weight planes when `need_t`).  Shared by _Proj1x1 and _ProjUnfoldStats.  `prepared`: the layer's frozen
+    record (inference.py) — its max|w| cell and, when no transposed planes are wanted, its k-padded planes replace the preparation."""
     x = _chk(x, "proj1x1: x")
     w2 = _chk(weight.reshape(weight.shape[0], -1), "proj1x1: weight")
     B, Cin, h, w = x.shape
@@ -1054,25 +1055,29 @@ def _proj1x1_forward(x, weight, bias, need_t: bool):
               and lib.cocos_proj1x1_stream_kpad(Cout) != 0)
     st = dict(split=split, stream=stream, amax=None, t_planes=None, wshape=tuple(weight.shape), has_bias=bias is not None)
     if split:      # products on the f16 MFMA, operands split on the fly (sgemm_f16x3.hip)
-        wa = _recall_amax(w2)      # left by K21 when the layer is spectral-normed (W / sigma) or by prefetch_amax, else one small pass
+        # left by K21 when the layer is spectral-normed (W / sigma) or by prefetch_amax, else one small pass
+        wa = _recall_amax(w2) if prepared is None else prepared.amax
         xa = _recall_amax(x)
         xa, wa = (absmax(x) if xa is None else xa), (absmax(w2) if wa is None else wa)
         if stream:
             # A = W as planes [Cout][Kpad], rows zero-padded to whole MFMA k-steps
             kp = lib.cocos_proj1x1_stream_kpad(Cin)
-            wh = torch.empty((Cout, kp), device=x.device, dtype=torch.float16)
-            wl = torch.empty((Cout, kp), device=x.device, dtype=torch.float16)
-            ws = torch.empty(1, device=x.device, dtype=torch.float32)
-            # ... and, when the input gradient will be wanted, the transposed planes [Cin][Kpad(Cout)] of dx = W^T dy
-            # in the same launch (they used to be a second split in the backward)
-            th = tl = None
-            if need_t:
-                kpo = lib.cocos_proj1x1_stream_kpad(Cout)
-                th = torch.empty((Cin, kpo), device=x.device, dtype=torch.float16)
-                tl = torch.empty((Cin, kpo), device=x.device, dtype=torch.float16)
-            _call("split_f16", "cocos_proj_weight_planes", w2.data_ptr(), wh.data_ptr(), wl.data_ptr(), _ptr(th), _ptr(tl),
-                  Cout, Cin, kp, lib.cocos_proj1x1_stream_kpad(Cout), wa.data_ptr(), ws.data_ptr(), _stream())
-            st["t_planes"] = (th, tl, ws) if th is not None else None
+            if prepared is not None and not need_t:
+                wh, wl, ws = prepared.planes("rows", kp)
+            else:
+                wh = torch.empty((Cout, kp), device=x.device, dtype=torch.float16)
+                wl = torch.empty((Cout, kp), device=x.device, dtype=torch.float16)
+                ws = torch.empty(1, device=x.device, dtype=torch.float32)
+                # ... and, when the input gradient will be wanted, the transposed planes [Cin][Kpad(Cout)] of dx = W^T dy
+                # in the same launch (they used to be a second split in the backward)
+                th = tl = None
+                if need_t:
+                    kpo = lib.cocos_proj1x1_stream_kpad(Cout)
+                    th = torch.empty((Cin, kpo), device=x.device, dtype=torch.float16)
+                    tl = torch.empty((Cin, kpo), device=x.device, dtype=torch.float16)
+                _call("split_f16", "cocos_proj_weight_planes", w2.data_ptr(), wh.data_ptr(), wl.data_ptr(), _ptr(th), _ptr(tl),
+                      Cout, Cin, kp, lib.cocos_proj1x1_stream_kpad(Cout), wa.data_ptr(), ws.data_ptr(), _stream())
+                st["t_planes"] = (th, tl, ws) if th is not None else None
             _call("proj1x1_fwd", "cocos_proj1x1_stream_f16x3", x.data_ptr(), wh.data_ptr(), wl.data_ptr(),
                   ws.data_ptr(), _ptr(bb), y.data_ptr(), B, Cin, Cout, h * w, xa.data_ptr(), _stream())
         else:
@@ -1087,8 +1092,8 @@ def _proj1x1_forward(x, weight, bias, need_t: bool):
 
 class _Proj1x1(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        y, x, w2, st = _proj1x1_forward(x, weight, bias, ctx.needs_input_grad[0])
+    def forward(ctx, x, weight, bias, prepared=None):
+        y, x, w2, st = _proj1x1_forward(x, weight, bias, ctx.needs_input_grad[0], prepared)
         ctx.split, ctx.stream, ctx.amax, ctx.t_planes = st["split"], st["stream"], st["amax"], st["t_planes"]
         ctx.save_for_backward(x, w2)
         ctx.wshape, ctx.has_bias = st["wshape"], st["has_bias"]
@@ -1097,9 +1102,9 @@ class _Proj1x1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w2 = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad
-        return _proj1x1_backward(x, w2, dy, ctx.amax if ctx.split else None, getattr(ctx, "t_planes", None), ctx.split, ctx.stream,
-                                 need_x, need_w, need_b and ctx.has_bias, ctx.wshape)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        return (*_proj1x1_backward(x, w2, dy, ctx.amax if ctx.split else None, getattr(ctx, "t_planes", None), ctx.split, ctx.stream,
+                                   need_x, need_w, need_b and ctx.has_bias, ctx.wshape), None)
 
 
 def _proj1x1_backward(x, w2, dy, amax, t_planes, split, stream, need_x, need_w, need_b, wshape):
@@ -1163,10 +1168,11 @@ def _proj1x1_backward(x, w2, dy, amax, t_planes, split, stream, need_x, need_w, 
     return dx, dw, db
 
 
-def proj1x1(x, weight, bias=None):
+def proj1x1(x, weight, bias=None, prepared=None):
     """nn.Conv2d(Cin, Cout, kernel_size=1): x [B,Cin,h,w], weight [Cout,Cin,1,1].  PROJ_PRECISION "f16x3" (default):
-    the streaming split-precision kernels at the reference's shapes, else the split GEMM; "fp32": the fp32-MFMA GEMM."""
-    return _Proj1x1.apply(x, weight, bias)
+    the streaming split-precision kernels at the reference's shapes, else the split GEMM; "fp32": the fp32-MFMA GEMM.
+    `prepared`: the layer's frozen record (cocosnet_amd.inference), or None — today's route, byte for byte."""
+    return _Proj1x1.apply(x, weight, bias, prepared)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1192,10 +1198,11 @@ class LazyProj1x1:
     planes straight from `x` (K23) and the projection never exists in HBM.  Quacks like the tensor it stands for where
     `correspondence_hot_path` looks (shape, is_cuda, dtype, requires_grad, detach)."""
 
-    def __init__(self, x, weight, bias=None):
+    def __init__(self, x, weight, bias=None, prepared=None):
         if x.dim() != 4 or weight.shape[1] != x.shape[1]:
             raise ValueError(f"LazyProj1x1: weight {tuple(weight.shape)} does not match input {tuple(x.shape)}")
         self.x, self.weight, self.bias = x, weight, bias
+        self.prepared = prepared      # the projection's frozen record (cocosnet_amd.inference), or None
         self._raw = None
 
     @property
@@ -1211,12 +1218,18 @@ class LazyProj1x1:
         return any(t is not None and t.requires_grad for t in (self.x, self.weight, self.bias))
 
     def detach(self):
-        return LazyProj1x1(self.x.detach(), self.weight.detach(), None if self.bias is None else self.bias.detach())
+        return LazyProj1x1(self.x.detach(), self.weight.detach(), None if self.bias is None else self.bias.detach(), self.prepared)
 
     def raw(self):
         if self._raw is None:
-            self._raw = proj1x1(self.x, self.weight, self.bias)
+            self._raw = proj1x1(self.x, self.weight, self.bias, self.prepared)
         return self._raw
+
+
+def _prepared_pair(theta: LazyProj1x1, phi: LazyProj1x1):
+    """(theta's record, phi's record) when BOTH projections carry a frozen record, else None (the pair kernels prepare both or neither)."""
+    a, b = getattr(theta, "prepared", None), getattr(phi, "prepared", None)
+    return (a, b) if a is not None and b is not None else None
 
 
 def proj_norm_fused_ok(p: LazyProj1x1) -> bool:
@@ -1233,7 +1246,7 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
     go through K1's backward (cocos_center_l2norm_bwd_planes) and K0's (_proj1x1_backward)."""
 
     @staticmethod
-    def forward(ctx, x1, w1, b1, x2, w2, b2, center_over_channels: int, eps: float, planes, want_chan: bool):
+    def forward(ctx, x1, w1, b1, x2, w2, b2, center_over_channels: int, eps: float, planes, want_chan: bool, prepared=None):
         lib = _lib.load()
         xs = [_chk(x1, "proj_center_l2norm_planes: x (theta)"), _chk(x2, "proj_center_l2norm_planes: x (phi)")]
         ws = [_chk(w1.reshape(w1.shape[0], -1), "proj_center_l2norm_planes: weight"),
@@ -1249,19 +1262,27 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
         args, keep, tplanes, tfrags = [], [], [], []
         # max|.| of the two feature tensors and the two weights: the ones no producer left behind (K21 leaves a spectral-normed
         # weight's, K13 / K9 epilogues the features') share ONE launch
-        amax = [_recall_amax(xs[0], consume=False), _recall_amax(ws[0]), _recall_amax(xs[1], consume=False), _recall_amax(ws[1])]
+        if prepared is None:
+            amax = [_recall_amax(xs[0], consume=False), _recall_amax(ws[0]), _recall_amax(xs[1], consume=False), _recall_amax(ws[1])]
+        else:      # frozen records (inference.py): the weights' cells are theirs
+            amax = [_recall_amax(xs[0], consume=False), prepared[0].amax, _recall_amax(xs[1], consume=False), prepared[1].amax]
         missing = [i for i, c in enumerate(amax) if c is None]
         if missing:
             for i, c in zip(missing, absmax_many([(xs[0], ws[0], xs[1], ws[1])[i] for i in missing])):
                 amax[i] = c
+        # ... and so are the fragment-ordered planes, unless an input gradient wants the transposed layouts made with them
+        frozen = prepared is not None and not ((ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and torch.is_grad_enabled())
         wprep = []
         for pi, (x, w2d, bb) in enumerate(zip(xs, ws, bs)):
             xa, wa = amax[2 * pi], amax[2 * pi + 1]
-            wfrag = torch.empty(lib.cocos_proj_weight_frag_bytes(Cin), device=dev, dtype=torch.uint8)
-            wsc = torch.empty(1, device=dev, dtype=torch.float32)
+            if frozen:
+                wfrag, _, wsc = prepared[pi].planes("frag")
+            else:
+                wfrag = torch.empty(lib.cocos_proj_weight_frag_bytes(Cin), device=dev, dtype=torch.uint8)
+                wsc = torch.empty(1, device=dev, dtype=torch.float32)
             # ... and, when the input gradient will be wanted, the transposed planes [Cin][256] of dx = W^T dy in the same launch
             th = tl = None
-            if ctx.needs_input_grad[3 * len(keep)]:
+            if ctx.needs_input_grad[3 * len(keep)] and not frozen:
                 th, tl = torch.empty((Cin, FUSED_K), **half), torch.empty((Cin, FUSED_K), **half)
             tplanes.append((th, tl, wsc) if th is not None else None)
             # ... and W^T in K24's fragment order when the fused backward will run
@@ -1279,7 +1300,8 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
                      pl.data_ptr(), _ptr(ch), _ptr(cl)]
             keep.append((xa, wa, wfrag, wsc, norm, ph, pl, ch, cl))
         # every weight layout of both projections in one launch (they were four)
-        _call("split_f16", "cocos_proj_weight_prep_pair", 2, *wprep, FUSED_K, Cin, _stream())
+        if not frozen:
+            _call("split_f16", "cocos_proj_weight_prep_pair", 2, *wprep, FUSED_K, Cin, _stream())
         _call("proj_center_l2norm_fwd", "cocos_proj_center_l2norm_planes_f16x3", 2, *args, B, Cin, N, int(center_over_channels),
               float(eps), SPLIT_OPERAND_SCALE, _stream())
         handles = []
@@ -1305,7 +1327,7 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
     def backward(ctx, d1, d2):
         x1, w1, x2, w2, n1, n2 = ctx.saved_tensors
         mode, eps = ctx.cfg
-        needs = ctx.needs_input_grad
+        needs = ctx.needs_input_grad[:10]
         if (d1 is not None and d2 is not None and needs[0] and needs[3] and all(t is not None for t in ctx.tfrags)
                 and (needs[1] or not needs[2]) and (needs[4] or not needs[5])):
             # K24: K1's backward + the input gradient of BOTH projections in one launch; the weight gradients rebuild d on the fly
@@ -1331,7 +1353,7 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
                                                   for i in range(2)], SPLIT_OPERAND_SCALE, nb[0])
                 for i in range(2):
                     out += [dxs[i], res[i][0].reshape(ctx.wshapes[i]), res[i][1]]
-                return (*out, None, None, None, None)
+                return (*out, None, None, None, None, None)
             for i in range(2):
                 need_w, need_b = needs[3 * i + 1], nb[i]
                 dw = db = None
@@ -1340,7 +1362,7 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
                     dw, db = _proj1x1_dw_affine(2, d[i], ch, cl, coefs[i], SPLIT_OPERAND_SCALE, xs[i], cells[i], ctx.amax[i][0], need_b)
                     dw = dw.reshape(ctx.wshapes[i])
                 out += [dxs[i], dw, db]
-            return (*out, None, None, None, None)
+            return (*out, None, None, None, None, None)
         out = []
         for i, (x, w2d, norm, dy) in enumerate(((x1, w1, n1, d1), (x2, w2, n2, d2))):
             need_x, need_w, need_b = ctx.needs_input_grad[3 * i:3 * i + 3]
@@ -1362,7 +1384,7 @@ class _ProjCenterL2NormPlanesPair(torch.autograd.Function):
             stream = PROJ_STREAM and N % 64 == 0 and lib.cocos_proj1x1_stream_kpad(Cin) != 0 and lib.cocos_proj1x1_stream_kpad(K) != 0
             out += list(_proj1x1_backward(x, w2d, dth, ctx.amax[i], ctx.t_planes[i], True, stream, need_x, need_w,
                                           need_b and ctx.has_bias[i], ctx.wshapes[i]))
-        return (*out, None, None, None, None)
+        return (*out, None, None, None, None, None)
 
 
 def _proj1x1_dw_affine(mode, in1, in2a, in2b, coef, plane_scale, x, d_amax, x_amax, need_b):
@@ -1425,10 +1447,10 @@ class _ProjUnfoldStats(torch.autograd.Function):
     addition and the max|.| pass into the projection's input gradient (K24 mode 1); the weight gradient rebuilds d on the fly."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, k_unfolded: float, eps: float):
+    def forward(ctx, x, weight, bias, k_unfolded: float, eps: float, prepared=None):
         lib = _lib.load()
         ctx.set_materialize_grads(False)      # (nrm is not differentiable: autograd would hand its backward a zero-filled [B,N] tensor per call)
-        y, x, w2, st = _proj1x1_forward(x, weight, bias, ctx.needs_input_grad[0])
+        y, x, w2, st = _proj1x1_forward(x, weight, bias, ctx.needs_input_grad[0], prepared)
         B, C, h, w = y.shape
         N = h * w
         mk = lambda: torch.empty((B, N), device=y.device, dtype=torch.float32)
@@ -1477,7 +1499,7 @@ class _ProjUnfoldStats(torch.autograd.Function):
             if need_w:
                 dw, db = _proj1x1_dw_affine(1, dy.reshape(B, C, N), y, None, coef, 1.0, x, cell, st["amax"][0], need_b)
                 dw = dw.reshape(st["wshape"])
-            return dx, dw, db, None, None
+            return dx, dw, db, None, None, None
         # round 5's chain: K12's backward as a tensor, autograd-style addition, then the projection's backward
         dth = torch.empty_like(y)
         ws = torch.empty(2 * B * N, device=y.device, dtype=torch.float32)
@@ -1486,7 +1508,7 @@ class _ProjUnfoldStats(torch.autograd.Function):
         if dy is not None:
             dth = dth + dy
         return (*_proj1x1_backward(x, w2, dth, st["amax"], st["t_planes"], st["split"], st["stream"], need_x, need_w, need_b,
-                                   st["wshape"]), None, None)
+                                   st["wshape"]), None, None, None)
 
 
 #: False: match_kernel 3 projects with K0 and takes the statistics / operand planes in separate launches (A/B runs)
@@ -1539,7 +1561,7 @@ class _ProjRawPlanesStatsPair(torch.autograd.Function):
     K24 mode C for both input gradients (one launch), both weight gradients (one launch + one reduction)."""
 
     @staticmethod
-    def forward(ctx, x1, w1, b1, x2, w2, b2, k_unfolded: float, eps: float, holder):
+    def forward(ctx, x1, w1, b1, x2, w2, b2, k_unfolded: float, eps: float, holder, prepared=None):
         lib = _lib.load()
         ctx.set_materialize_grads(False)
         xs = [_chk(x1, "proj_raw_planes_stats: x (theta)"), _chk(x2, "proj_raw_planes_stats: x (phi)")]
@@ -1550,16 +1572,24 @@ class _ProjRawPlanesStatsPair(torch.autograd.Function):
         dev = xs[0].device
         half, f32 = dict(device=dev, dtype=torch.float16), dict(device=dev, dtype=torch.float32)
         want_grad = any(ctx.needs_input_grad[:6])
-        amax = [_recall_amax(xs[0], consume=False), _recall_amax(ws[0]), _recall_amax(xs[1], consume=False), _recall_amax(ws[1])]
+        if prepared is None:
+            amax = [_recall_amax(xs[0], consume=False), _recall_amax(ws[0]), _recall_amax(xs[1], consume=False), _recall_amax(ws[1])]
+        else:      # frozen records (inference.py): the weights' cells and, without a backward, their fragment-ordered planes
+            amax = [_recall_amax(xs[0], consume=False), prepared[0].amax, _recall_amax(xs[1], consume=False), prepared[1].amax]
+        # (needs_input_grad mirrors requires_grad even under no_grad: a backward can only follow with gradients enabled)
+        frozen = prepared is not None and not (want_grad and torch.is_grad_enabled())
         missing = [i for i, c in enumerate(amax) if c is None]
         if missing:
             for i, c in zip(missing, absmax_many([(xs[0], ws[0], xs[1], ws[1])[i] for i in missing])):
                 amax[i] = c
         wprep, args, keep = [], [], []
         for pi in range(2):
-            wfrag = torch.empty(lib.cocos_proj_weight_frag_bytes(Cin), device=dev, dtype=torch.uint8)
-            wsc = torch.empty(1, **f32)
-            wtf = torch.empty(lib.cocos_proj_weight_tfrag_bytes(), device=dev, dtype=torch.uint8) if want_grad else None
+            if frozen:
+                wfrag, _, wsc = prepared[pi].planes("frag")
+            else:
+                wfrag = torch.empty(lib.cocos_proj_weight_frag_bytes(Cin), device=dev, dtype=torch.uint8)
+                wsc = torch.empty(1, **f32)
+            wtf = torch.empty(lib.cocos_proj_weight_tfrag_bytes(), device=dev, dtype=torch.uint8) if want_grad and not frozen else None
             wprep += [ws[pi].data_ptr(), amax[2 * pi + 1].data_ptr(), wfrag.data_ptr(), wsc.data_ptr(), None, None, _ptr(wtf)]
             sums = torch.empty((2, B, N), **f32)
             ysc = torch.empty(1, **f32)
@@ -1570,7 +1600,8 @@ class _ProjRawPlanesStatsPair(torch.autograd.Function):
             args += [xs[pi].data_ptr(), wfrag.data_ptr(), wsc.data_ptr(), _ptr(bs[pi]), amax[2 * pi].data_ptr(), sums[0].data_ptr(),
                      sums[1].data_ptr(), ysc.data_ptr(), ph.data_ptr(), pl.data_ptr(), _ptr(ch), _ptr(cl)]
             keep.append((wfrag, wsc, wtf, sums, ysc, ph, pl, ch, cl))
-        _call("split_f16", "cocos_proj_weight_prep_pair", 2, *wprep, FUSED_K, Cin, _stream())
+        if not frozen:
+            _call("split_f16", "cocos_proj_weight_prep_pair", 2, *wprep, FUSED_K, Cin, _stream())
         _call("proj1x1_fwd", "cocos_proj_raw_planes_stats_f16x3", 2, *args, B, Cin, N, _stream())
         stats = [tuple(torch.empty((B, N), **f32) for _ in range(3)) for _ in range(2)]      # (mu, a, nrm) per tensor
         fa = []
@@ -1634,20 +1665,20 @@ class _ProjRawPlanesStatsPair(torch.autograd.Function):
             #  biases' gradients are computed and the unwanted one dropped)
             res = _proj1x1_dw_affine_pair(2, probs, 1.0, True, scale_cells)
             res = [(res[pi][0], res[pi][1] if nb[pi] else None) for pi in range(2)]
-        return (dxs[0], res[0][0].reshape(ctx.wshapes[0]), res[0][1], dxs[1], res[1][0].reshape(ctx.wshapes[1]), res[1][1], None, None, None)
+        return (dxs[0], res[0][0].reshape(ctx.wshapes[0]), res[0][1], dxs[1], res[1][0].reshape(ctx.wshapes[1]), res[1][1], None, None, None, None)
 
 
 def proj_raw_planes_stats_pair(theta: LazyProj1x1, phi: LazyProj1x1, k_unfolded: float, holder: Box3RawPlanes, eps: float = NORM_EPS):
     """((theta handle, mu, a), (phi handle, nu, b)) of two lazy projections through K25: see _ProjRawPlanesStatsPair.  The handles go
     to box3_corr_xbox(..., raw_planes=holder).  Only for proj_raw_fused_ok() pairs."""
     th, mu, a, ph, nu, b, _, _ = _ProjRawPlanesStatsPair.apply(theta.x, theta.weight, theta.bias, phi.x, phi.weight, phi.bias,
-                                                               float(k_unfolded), eps, holder)
+                                                               float(k_unfolded), eps, holder, _prepared_pair(theta, phi))
     return (th, mu, a), (ph, nu, b)
 
 
 def proj_unfold3_stats(p: LazyProj1x1, k_unfolded: float, eps: float = NORM_EPS):
     """(theta_raw [B,C,h,w], mu, a [B,h*w]) of a lazy projection: K0 + K12 as one autograd node (see _ProjUnfoldStats)."""
-    y, mu, a, _ = _ProjUnfoldStats.apply(p.x, p.weight, p.bias, float(k_unfolded), eps)
+    y, mu, a, _ = _ProjUnfoldStats.apply(p.x, p.weight, p.bias, float(k_unfolded), eps, p.prepared)
     return y, mu, a
 
 
@@ -1656,7 +1687,7 @@ def proj_center_l2norm_planes_pair(theta: LazyProj1x1, phi: LazyProj1x1, center_
     """(qn handle, kn handle) of the two lazy projections through K23: see _ProjCenterL2NormPlanesPair.  Pass the handles to
     corr_softmax_warp(..., planes=planes).  Only for proj_norm_fused_ok() shapes on the split path (corr_split_ok)."""
     return _ProjCenterL2NormPlanesPair.apply(theta.x, theta.weight, theta.bias, phi.x, phi.weight, phi.bias,
-                                             int(center_over_channels), eps, planes, bool(want_chan))
+                                             int(center_over_channels), eps, planes, bool(want_chan), _prepared_pair(theta, phi))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1843,7 +1874,7 @@ def _conv_dgrad_strided(xshape, weight, dy, ga, wa, s: int, p: int):
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, stride: int, pad: int, dil: int, reflect: int = 0):
+    def forward(ctx, x, weight, bias, stride: int, pad: int, dil: int, reflect: int = 0, prepared=None):
         x = _chk(x, "conv2d: x")
         weight = _chk(weight, "conv2d: weight")
         if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
@@ -1859,10 +1890,16 @@ class _Conv2d(torch.autograd.Function):
             if xa is None:
                 xa = absmax(x)
                 _remember_amax(x, xa, weak=True)     # ... and the second one finds what the first one measured
-            wa = _recall_amax(weight)          # K21 leaves it for spectral-normed layers
-            if wa is None:
-                wa = absmax(weight)
-        wh, wl, ws = _conv_weight_planes(weight, wa, 0)
+            if prepared is not None:           # the layer's frozen record (inference.py): its cell, its planes
+                wa = prepared.amax
+            else:
+                wa = _recall_amax(weight)          # K21 leaves it for spectral-normed layers
+                if wa is None:
+                    wa = absmax(weight)
+        if prepared is not None:
+            wh, wl, ws = prepared.planes("conv_fwd" if wa is not None else "conv_fwd_bf16")
+        else:
+            wh, wl, ws = _conv_weight_planes(weight, wa, 0)
         xp = None
         if wa is not None and CONV_NHWC_F16X3 and _conv_nhwc_ok(Cin, Cout, KH, KW, stride):
             # K16c: the split arithmetic on K16b's data path — hi/lo planes NHWC in memory, LDS-DMA GEMM, three terms
@@ -1885,6 +1922,8 @@ class _Conv2d(torch.autograd.Function):
         ctx.x_shape, ctx.has_xp, ctx.reflect = tuple(x.shape), keep_xp, int(reflect)
         ctx.cfg = (int(stride), int(pad), int(dil), bias is not None)
         ctx.amax = (xa, wa)
+        # the input-gradient planes come from the record only where freeze() asked for them (the fixed VGG of a training step)
+        ctx.prepared = prepared if prepared is not None and prepared.keep_dgrad else None
         return y
 
     @staticmethod
@@ -1917,14 +1956,17 @@ class _Conv2d(torch.autograd.Function):
         fold = bool(dx_nhwc and reflect == 1 and H - 2 >= 4 and W - 2 >= 4)     # the mirrored border folded back by the GEMM itself
         if need_x:
             if dx_nhwc and not bf:
-                th, tl, ts = _conv_weight_planes(weight, wa, 1)
+                th, tl, ts = _conv_weight_planes(weight, wa, 1) if ctx.prepared is None else ctx.prepared.planes("conv_dgrad")
                 dx = _conv_nhwc_split_call(dyp, th, tl, ts, ga, None, Cin, KH, KW, dil, fold=fold)
             elif dx_nhwc:
-                th, _, _ = _conv_weight_planes(weight, None, 1)
+                th, _, _ = _conv_weight_planes(weight, None, 1) if ctx.prepared is None else ctx.prepared.planes("conv_dgrad_bf16")
                 dx = _conv_nhwc_call(dyp, th, None, Cin, KH, KW, dil, fold=fold)
             elif stride == 1 and q >= 0 and KW == KH:
                 # dx = conv(dy, flipped weights with the channel roles swapped, padding d(K-1)-p): the same kernel
-                th, tl, ts = _conv_weight_planes(weight, wa, 1)
+                if ctx.prepared is None:
+                    th, tl, ts = _conv_weight_planes(weight, wa, 1)
+                else:
+                    th, tl, ts = ctx.prepared.planes("conv_dgrad" if not bf else "conv_dgrad_bf16")
                 dx = _conv_fwd_call(dy, th, tl, ts, ga, None, Cin, KH, KW, 1, dil * (KH - 1) - pad, dil)
             elif stride > 1 and dil == 1 and (dx := _conv_dgrad_strided((B, Cin, H, W), weight, dy, ga, wa, stride, pad)) is not None:
                 pass    # stride^2 parity classes, each a stride-1 convolution of dy scattered into dx (K16)
@@ -1962,15 +2004,17 @@ class _Conv2d(torch.autograd.Function):
             dxp, dx = dx, torch.empty(ctx.x_shape, device=dy.device, dtype=torch.float32)
             _call("reflect_pad2d_bwd", "cocos_reflect_pad2d_bwd", dxp.data_ptr(), dx.data_ptr(), B * Cin, ctx.x_shape[2], ctx.x_shape[3],
                   reflect, _stream())
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
-def conv2d(x, weight, bias=None, stride: int = 1, padding: int = 0, dilation: int = 1, reflect: int = 0):
+def conv2d(x, weight, bias=None, stride: int = 1, padding: int = 0, dilation: int = 1, reflect: int = 0, prepared=None):
     """torch.nn.functional.conv2d(x, weight, bias, stride, padding, dilation) for groups = 1 and one stride / padding /
     dilation for both axes: fp32 in and out, products on the f16 MFMA with split operands (3 terms, fp32 accumulate) —
     conv_f16x3.hip — or, under COCOS_CONV=bf16, in one bf16 term (stride-1 layers with >= 128 output channels: conv_nhwc_bf16.hip).
     `reflect` = r > 0: the convolution of nn.ReflectionPad2d(r)(x) — on the K16b path the mirrored border is written by the
-    operand preparation (no padded fp32 tensor), everywhere else it is ops.reflect_pad2d followed by the plain layer."""
+    operand preparation (no padded fp32 tensor), everywhere else it is ops.reflect_pad2d followed by the plain layer.
+    `prepared`: the layer's frozen record (cocosnet_amd.inference) — max|w| cell and weight planes are taken from it instead of being
+    derived again; None: today's route, byte for byte."""
     reflect = int(reflect)
     if reflect:
         Cout, Cin, KH, KW = weight.shape
@@ -1979,7 +2023,7 @@ def conv2d(x, weight, bias=None, stride: int = 1, padding: int = 0, dilation: in
                  and ow >= 32 and ow % 32 == 0 and _conv_nhwc_ok(Cin, Cout, KH, KW, 1))
         if not fused:
             x, reflect = reflect_pad2d(x, reflect), 0
-    return _Conv2d.apply(x, weight, bias, int(stride), int(padding), int(dilation), reflect)
+    return _Conv2d.apply(x, weight, bias, int(stride), int(padding), int(dilation), reflect, prepared)
 
 
 # ------------------------------------------------------------------------------------------
@@ -3528,6 +3572,92 @@ def ema_multi_update(shadows, params, mu: float) -> int:
     _call("ema_multi", "cocos_ema_multi_update", ctypes.addressof(entries), len(shadows), float(mu), ctypes.addressof(launches), _stream())
     torch.autograd.graph.increment_version(shadows)
     return launches.value
+
+
+# ------------------------------------------------------------------------------------------
+# K32  weight preparation for frozen-weight inference: many weights per launch   (inference.py; weight_prepare_multi.hip)
+# ------------------------------------------------------------------------------------------
+#: layout name -> COCOS_WPREP_* (include/cocos_hip.h)
+WPREP_LAYOUTS = {"conv_fwd": 0, "conv_dgrad": 1, "conv_fwd_bf16": 2, "conv_dgrad_bf16": 3, "rows": 4, "frag": 5}
+
+
+def weight_prepare_constants() -> dict:
+    """COCOS_WPREP_* as the loaded library was built with them: TABLE_ENTRIES (entries per launch), ABSMAX_CHUNK (elements per workgroup)."""
+    f = _lib.load().cocos_weight_prepare_constant
+    return {name: f(k) for k, name in enumerate(("TABLE_ENTRIES", "ABSMAX_CHUNK"))}
+
+
+def weight_absmax_multi(weights):
+    """([max|w| cell for w in weights], kernel launches): one pass over every listed weight, two launches per 64 of them
+    (per-workgroup maxima, then one finishing workgroup per weight) — the bits `absmax(w)` leaves, without its launch per tensor."""
+    weights = list(weights)
+    if not weights:
+        return [], 0
+    for w in weights:
+        _optim_chk(w, "weight_absmax_multi: weight")
+    dev = weights[0].device
+    if any(w.device != dev for w in weights):
+        raise ValueError("weight_absmax_multi: the weights live on different devices")
+    cells = torch.empty(len(weights), device=dev, dtype=torch.float32)
+    words = []
+    for i, w in enumerate(weights):
+        words += (w.data_ptr(), w.numel(), cells.data_ptr() + 4 * i)
+    entries = _table(ctypes.c_uint64, words)
+    n_ws = _lib.load().cocos_weight_absmax_multi_workspace_floats(ctypes.addressof(entries), len(weights))
+    ws = torch.empty(max(int(n_ws), 1), device=dev, dtype=torch.float32)
+    launches = ctypes.c_int(0)
+    _call("weight_prepare", "cocos_weight_absmax_multi", ctypes.addressof(entries), len(weights), ws.data_ptr(), ws.numel(),
+          ctypes.addressof(launches), _stream())
+    return [cells[i:i + 1] for i in range(len(weights))], launches.value
+
+
+def weight_planes_shape(weight, layout: str, aux: int = 0):
+    """(hi shape, dtype, has lo) of `layout` for a weight [Cout,Cin,KH,KW] (or [Cout,Cin])."""
+    Cout, Cin = weight.shape[:2]
+    KH, KW = (weight.shape[2], weight.shape[3]) if weight.dim() == 4 else (1, 1)
+    if layout.startswith("conv_"):
+        M, C = (Cout, Cin) if "fwd" in layout else (Cin, Cout)
+        return (KH * KW * ((C + 31) // 32), M, 32), torch.float16, not layout.endswith("bf16")
+    if layout == "rows":
+        return (Cout, int(aux)), torch.float16, True
+    if layout == "frag":
+        return (int(_lib.load().cocos_proj_weight_frag_bytes(Cin * KH * KW)),), torch.uint8, False
+    raise ValueError(f"weight_planes_multi: unknown layout {layout!r} (expected one of {sorted(WPREP_LAYOUTS)})")
+
+
+def weight_planes_multi(requests):
+    """requests: (weight, max|w| cell or None, layout, aux) each -> ([(hi, lo, scale)], kernel launches): the planes of ONE layout per
+    request, one launch per 64 requests, byte for byte what the single-tensor routines write —
+      "conv_fwd" / "conv_dgrad"            _conv_weight_planes(weight, cell, 0 / 1): K16 / K16c;
+      "conv_fwd_bf16" / "conv_dgrad_bf16"  _conv_weight_planes(weight, None, 0 / 1): one bf16 plane, lo and scale None (K16b);
+      "rows"                               cocos_split_f16_rows with rows of `aux` halfs (K0 stream, aux = cocos_proj1x1_stream_kpad(Cin));
+      "frag"                               cocos_proj_weight_frag_planes (K23 / K25): hi = the fragment buffer, lo None."""
+    requests = list(requests)
+    if not requests:
+        return [], 0
+    out, words = [], []
+    for weight, cell, layout, aux in requests:
+        _optim_chk(weight, "weight_planes_multi: weight")
+        if weight.dim() not in (2, 4):
+            raise ValueError(f"weight_planes_multi: weight {tuple(weight.shape)}")
+        shape, dtype, has_lo = weight_planes_shape(weight, layout, aux)
+        bf = layout.endswith("bf16")
+        if not bf and cell is None:
+            raise ValueError(f"weight_planes_multi: layout {layout!r} needs the weight's max|w| cell")
+        hi = torch.empty(shape, device=weight.device, dtype=dtype)
+        lo = torch.empty_like(hi) if has_lo else None
+        sc = None if bf else torch.empty(1, device=weight.device, dtype=torch.float32)
+        Cout, Cin = weight.shape[:2]
+        KH, KW = (weight.shape[2], weight.shape[3]) if weight.dim() == 4 else (1, 1)
+        if layout == "frag":
+            Cin, KH, KW = Cin * KH * KW, 1, 1
+        words += (weight.data_ptr(), 0 if bf else cell.data_ptr(), hi.data_ptr(), _ptr(lo), _ptr(sc),
+                  WPREP_LAYOUTS[layout] | (Cout << 32), Cin | (KH << 32), KW | (int(aux) << 32))
+        out.append((hi, lo, sc))
+    entries = _table(ctypes.c_uint64, words)
+    launches = ctypes.c_int(0)
+    _call("weight_prepare", "cocos_weight_planes_multi", ctypes.addressof(entries), len(requests), ctypes.addressof(launches), _stream())
+    return out, launches.value
 
 
 def mfma_probe() -> torch.Tensor:

@@ -56,10 +56,20 @@ class Conv2d(nn.Conv2d):
                 and input.dim() == 4 and self.groups == 1 and self.padding_mode == "zeros"
                 and not isinstance(p, str) and s[0] == s[1] and p[0] == p[1] and d[0] == d[1]):
             from . import _lib, ops
+            # frozen-weight inference (inference.py): a record attached by freeze(), validated, when this call may use it
+            # — only for the tensor the record stands for: the module's own weight, or the W / sigma its spectral hook just handed out
+            # (validated there: once per call)
+            rec = self.__dict__.get("_cocos_frozen")
+            if rec is not None:
+                if rec.hook is not None:
+                    handed, rec.handed = rec.handed, False
+                    rec = rec if handed and weight is rec.weight else None
+                else:
+                    rec = rec.use() if weight is self.weight else None
             try:
                 if k == (1, 1) and s[0] == 1 and p[0] == 0 and not reflect:
-                    return ops.proj1x1(input, weight, bias)
-                return ops.conv2d(input, weight, bias, s[0], p[0], d[0], reflect)
+                    return ops.proj1x1(input, weight, bias, rec)
+                return ops.conv2d(input, weight, bias, s[0], p[0], d[0], reflect, rec)
             except _lib.CocosHipError as e:
                 # kernel-side limits (a tensor of 2 GiB or more, a grid too large for the 32-bit index arithmetic: the
                 # discriminator / VGG at very large batch or resolution) are not part of the check above: they take the
@@ -78,12 +88,39 @@ import importlib                                            # noqa: E402
 _sn_mod = importlib.import_module("torch.nn.utils.spectral_norm")    # the MODULE (torch.nn.utils re-exports its function under the same name)
 
 
+def _frozen_weight(module):
+    """W / sigma from the layer's frozen record (inference.py), validated against weight_orig / u / v — or None"""
+    rec = module.__dict__.get("_cocos_frozen")
+    if rec is not None:
+        used = rec.use()
+        rec.handed = used is not None      # (Conv2d._conv_forward takes the validated record over: one validation per call)
+        if used is not None:
+            return used.weight
+    return None
+
+
+class _SpectralNormRecord(_sn_mod.SpectralNorm):
+    """torch.nn.utils.spectral_norm's own hook, plus the frozen record in eval(): inference.freeze() re-classes the framework's hook to
+    this one (and unfreeze() back) — layers wrapped with the framework's `spectral_norm` (Attention) keep the framework's arithmetic."""
+
+    def compute_weight(self, module, do_power_iteration):
+        w = None if do_power_iteration else _frozen_weight(module)
+        return w if w is not None else super().compute_weight(module, do_power_iteration)
+
+    def compute_weight_unfrozen(self, module, do_power_iteration):
+        return super().compute_weight(module, do_power_iteration)
+
+
 class _SpectralNormHIP(_sn_mod.SpectralNorm):
     """torch.nn.utils.spectral_norm's hook with `compute_weight` on K21 (ops.spectral_weight) for fp32 GPU weights: same buffers
     (weight_orig / weight_u / weight_v: checkpoints unchanged), same in-place update of u and v, same gradient — four launches
     forward and two backward instead of ~20 framework launches per layer and step."""
 
     def compute_weight(self, module, do_power_iteration):
+        w = None if do_power_iteration else _frozen_weight(module)      # eval(): a frozen record (inference.py) holds W / sigma
+        return w if w is not None else self.compute_weight_unfrozen(module, do_power_iteration)
+
+    def compute_weight_unfrozen(self, module, do_power_iteration):
         weight = getattr(module, self.name + "_orig")
         if (SPECTRAL_HIP and conv_backend() in _HIP_BACKENDS and weight.is_cuda and weight.dtype == torch.float32 and self.dim == 0
                 and self.n_power_iterations == 1 and weight.is_contiguous() and weight.numel() // weight.shape[0] <= 16384):

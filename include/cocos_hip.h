@@ -872,6 +872,55 @@ int cocos_ema_multi_update(const cocos_ema_entry* entries, int n_entries, double
                            cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K32 weight preparation for frozen-weight inference (cocosnet_amd/inference.py; csrc/weight_prepare_multi.hip): the max|w| cells
+ *     and the operand planes of MANY weights per launch.  `entries` are HOST arrays, copied COCOS_WPREP_TABLE_ENTRIES at a time into
+ *     the kernel arguments (as K29); *launches_out (host, nullable) receives the number of kernel launches made.
+ *   weight_absmax_multi: *cell = max|w[0..n)| for every entry (the cell is WRITTEN, not accumulated): one workgroup per
+ *       COCOS_WPREP_ABSMAX_CHUNK elements leaves its maximum in `workspace` (device, >= cocos_weight_absmax_multi_workspace_floats
+ *       floats), one finishing workgroup per entry reduces them — two launches per table, no atomics.  Bitwise cocos_absmax.
+ *   weight_planes_multi: per entry the planes of ONE layout of w [Cout][Cin][KH][KW], scaled by the power of two that brings *amax
+ *       into [2^9, 2^10) (written to *scale_out), byte for byte what the single-tensor routine writes:
+ *         COCOS_WPREP_CONV_FWD / _DGRAD            cocos_conv2d_weight_planes mode 0 / 1 (whole kernel: J = K, r = 0, s = 1); hi, lo
+ *         COCOS_WPREP_CONV_FWD_BF16 / _DGRAD_BF16  ... mode 2 / 3: one bf16 plane in hi; lo, amax, scale_out unused
+ *         COCOS_WPREP_ROWS                         cocos_split_f16_rows(rows = Cout, cols = Cin*KH*KW, cols_pad = aux, amax given);
+ *                                                  aux a multiple of 8
+ *         COCOS_WPREP_FRAG                         cocos_proj_weight_frag_planes (no transposed planes) of w [256][Cin]: hi = the
+ *                                                  cocos_proj_weight_frag_bytes(Cin) buffer, lo unused
+ *       Planes 16-byte aligned.
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_WPREP_TABLE_ENTRIES 64          /* table entries per launch */
+#define COCOS_WPREP_ABSMAX_CHUNK 8192         /* elements per workgroup of the max|w| pass */
+#define COCOS_WPREP_CONV_FWD 0
+#define COCOS_WPREP_CONV_DGRAD 1
+#define COCOS_WPREP_CONV_FWD_BF16 2
+#define COCOS_WPREP_CONV_DGRAD_BF16 3
+#define COCOS_WPREP_ROWS 4
+#define COCOS_WPREP_FRAG 5
+typedef struct cocos_wprep_absmax_entry {
+    const float* w;    /* weight (device) */
+    long long n;       /* elements, >= 1 */
+    float* cell;       /* max|w| (device), written */
+} cocos_wprep_absmax_entry;
+typedef struct cocos_wprep_planes_entry {
+    const float* w;       /* weight (device) */
+    const float* amax;    /* its max|w| cell (device); NULL for the bf16 layouts */
+    void* hi;             /* hi plane / bf16 plane / fragment buffer (device) */
+    void* lo;             /* lo plane (device); NULL where unused */
+    float* scale_out;     /* the scale the planes carry (device); NULL for the bf16 layouts */
+    int layout;           /* COCOS_WPREP_* */
+    int Cout, Cin, KH, KW;
+    int aux;              /* COCOS_WPREP_ROWS: padded row length */
+} cocos_wprep_planes_entry;
+#define COCOS_WPREP_CONST_TABLE_ENTRIES 0
+#define COCOS_WPREP_CONST_ABSMAX_CHUNK 1
+int cocos_weight_prepare_constant(int which);
+long long cocos_weight_absmax_multi_workspace_floats(const cocos_wprep_absmax_entry* entries, int n_entries);
+int cocos_weight_absmax_multi(const cocos_wprep_absmax_entry* entries, int n_entries, float* workspace, long long workspace_floats,
+                              int* launches_out /* host, nullable */, cocos_stream_t stream);
+int cocos_weight_planes_multi(const cocos_wprep_planes_entry* entries, int n_entries, int* launches_out /* host, nullable */,
+                              cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K16 2-D convolution (cross-correlation, zero padding, like torch.nn.functional.conv2d with groups = 1, one stride /
  *     padding / dilation for both axes)
  *     as an implicit GEMM on the f16 MFMA with split operands (conv_f16x3.hip).  Replaces the nn.Conv2d calls of the
