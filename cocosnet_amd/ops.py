@@ -2271,6 +2271,10 @@ class _Box3SoftmaxWarp(torch.autograd.Function):
               v_scale.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), g.data_ptr(), dmu.data_ptr(),
               da.data_ptr(), dnu.data_ptr(), db.data_ptr(), colpart.data_ptr(), gmax.data_ptr(), _ptr(psh), _ptr(psl),
               _ptr(ctx.v_lomask), B, N, N, Cv, cvp, h, w, kc, scale, _ptr(d_pre), flags, _stream())
+        if flags & 2:
+            # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand, so that whatever
+            # was derived from the buffer as it was (the first pass's max|G| cell among them) is void
+            torch.autograd.graph.increment_version(g)
         _remember_amax(g, gmax)      # (an accumulating pass replaces the cell remembered for the shared buffer)
         if sink is not None and t.numel() * 4 >= BOX3_ALIAS_T_BYTES:
             sink.t_dead = t          # (only when T's node will take the storage over: the reference keeps T alive until then)
@@ -3029,6 +3033,10 @@ class _SpectralWeight(torch.autograd.Function):
         cell = _zero_cell(w.device) if CONV_PRECISION != "bf16" else None
         _call("spectral_weight_fwd", "cocos_spectral_weight_fwd", w.data_ptr(), u.data_ptr(), v.data_ptr(), wsn.data_ptr(), sigma.data_ptr(),
               _ptr(cell), ws.data_ptr(), R, K, float(eps), int(bool(power_iteration)), _stream())
+        if power_iteration:
+            # the kernel wrote u and v through raw pointers, which autograd cannot see: whatever watches (data_ptr, _version) of the
+            # buffers — a frozen record's signature (inference.py), a max|.| cell, operand planes — must find them changed
+            torch.autograd.graph.increment_version([u, v])
         if cell is not None:
             _remember_amax(wsn, cell)
         # the vectors sigma was taken with: copies, because the next forward (GAN training: D(real), D(fake)) updates the buffers in place
