@@ -236,6 +236,9 @@ _SIGNATURES = {
     "cocos_instnorm_prelu_fwd_amax": (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 2 + [ctypes.c_float, _stream_t]),
     "cocos_instnorm_prelu_bwd_amax": (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p]
                                       + [ctypes.c_int] * 2 + [ctypes.c_float, _stream_t]),
+    "cocos_instnorm_prelu_split_workspace_floats": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "cocos_instnorm_prelu_split_fwd": (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 2 + [ctypes.c_float, _stream_t]),
+    "cocos_instnorm_prelu_split_bwd": (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 2 + [ctypes.c_float, _stream_t]),
     "cocos_contextual_rows_fwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_float,
                                                  ctypes.c_float, _stream_t]),
     "cocos_contextual_rows_bwd": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_float,

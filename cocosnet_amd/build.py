@@ -48,6 +48,7 @@ HIP_SOURCES = [
     "wta_scale.hip",
     "pono_spade.hip",
     "instnorm_prelu.hip",
+    "instnorm_split.hip",
     "upsample_nearest.hip",
     "warp_values.hip",
     "warp_head.hip",

@@ -2949,9 +2949,24 @@ def concat_channels_amax(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 INSTNORM_EPS = 1e-5   # nn.InstanceNorm2d default
 
 
+#: planes above 128 x 128 (the adaptors' layer1 at the image size, the PatchGAN's first norm) take K34 (instnorm_prelu_split) in
+#: producers.py / translation.py when True, the framework's InstanceNorm2d + leaky_relu when False.  Read at call time.  On by the
+#: measurement of tools/instnorm_split_bench.py (0.19 against 0.31 ms forward + backward at [8, 64, 256, 256], ahead at
+#: every shape).
+INSTNORM_SPLIT = True
+
+
+def _instnorm_split_workspace(x, planes: int, N: int) -> torch.Tensor:
+    # (fp64 storage: the library wants the buffer 8-byte aligned whatever the allocator's granularity)
+    return torch.empty((_lib.load().cocos_instnorm_prelu_split_workspace_floats(planes, N) + 1) // 2, device=x.device, dtype=torch.float64)
+
+
 class _InstNormPReLU(torch.autograd.Function):
+    """split = False: K13 (one workgroup per plane); True: K34 (instnorm_split.hip: a plane over several workgroups, the per-plane
+    (mean, rstd) saved for the backward).  One Function: what leaves besides y and the gradients — the max|.| cells — is the same."""
+
     @staticmethod
-    def forward(ctx, x, residual, weight, eps: float):
+    def forward(ctx, x, residual, weight, eps: float, split: bool = False):
         x = _chk(x, "instnorm_prelu: x")
         res = None if residual is None else _chk(residual, "instnorm_prelu: residual")
         w = _chk(weight, "instnorm_prelu: weight")
@@ -2962,23 +2977,30 @@ class _InstNormPReLU(torch.autograd.Function):
         B, C = x.shape[:2]
         N = x.numel() // (B * C)
         y = torch.empty_like(x)
-        if CONV_PRECISION == "f16x3":
-            # max|y| as a by-product: y is the next convolution's (or the projections') input, split with that scale
-            cell = _zero_cell(x.device)
+        stats = None
+        # max|y| as a by-product: y is the next convolution's (or the projections') input, split with that scale
+        cell = _zero_cell(x.device) if CONV_PRECISION == "f16x3" else None
+        if split:
+            stats = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)       # (mean, rstd) per plane: the backward takes them
+            ws = _instnorm_split_workspace(x, B * C, N)       # held by this name until the call below has launched what uses it
+            _call("instnorm_prelu_split_fwd", "cocos_instnorm_prelu_split_fwd", x.data_ptr(), _ptr(res), w.data_ptr(), y.data_ptr(),
+                  stats.data_ptr(), ws.data_ptr(), _ptr(cell), B * C, N, float(eps), _stream())
+        elif cell is not None:
             part = torch.empty(B * C, device=x.device, dtype=torch.float32)       # one maximum per plane, reduced by the same call
             _call("instnorm_prelu_fwd", "cocos_instnorm_prelu_fwd_amax", x.data_ptr(), _ptr(res), w.data_ptr(), y.data_ptr(), cell.data_ptr(),
                   part.data_ptr(), B * C, N, float(eps), _stream())
-            _remember_amax(y, cell, weak=True)
         else:
             _call("instnorm_prelu_fwd", "cocos_instnorm_prelu_fwd", x.data_ptr(), _ptr(res), w.data_ptr(), y.data_ptr(),
                   B * C, N, float(eps), _stream())
-        ctx.save_for_backward(x, res, w)
+        if cell is not None:
+            _remember_amax(y, cell, weak=True)
+        ctx.save_for_backward(x, res, w, stats)
         ctx.eps = float(eps)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, res, w = ctx.saved_tensors
+        x, res, w, stats = ctx.saved_tensors
         dy = _chk(dy, "instnorm_prelu: dy")
         B, C = x.shape[:2]
         N = x.numel() // (B * C)
@@ -2989,28 +3011,43 @@ class _InstNormPReLU(torch.autograd.Function):
         if need_w:
             # the weight's gradient is ONE number summed over every element of the layer, with cancelling terms: fp64 from the
             # products to the last addition (cocos_instnorm_prelu_bwd_f64; in fp32 it was up to 90x further from fp64 than the framework's)
-            dap = torch.empty(B * C, device=x.device, dtype=torch.float64)
             dw = torch.empty(1, device=x.device, dtype=torch.float32)
-        if dx is not None and CONV_PRECISION == "f16x3":
-            # max|dx| as a by-product: dx is the output gradient of the convolution in front of the norm, whose backward splits it next
-            cell = _zero_cell(x.device)
-            part = torch.empty(B * C, device=x.device, dtype=torch.float32)
-            _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd_amax", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(), dx.data_ptr(),
-                  _ptr(dr), _ptr(dap), _ptr(dw), cell.data_ptr(), part.data_ptr(), B * C, N, ctx.eps, _stream())
-            _remember_amax(dx, cell, weak=True)
-        elif need_w:
-            _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd_f64", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(),
-                  _ptr(dx), _ptr(dr), dap.data_ptr(), dw.data_ptr(), B * C, N, ctx.eps, _stream())
+        # max|dx| as a by-product: dx is the output gradient of the convolution in front of the norm, whose backward splits it next
+        cell = _zero_cell(x.device) if (dx is not None and CONV_PRECISION == "f16x3") else None
+        if stats is not None:
+            if dx is not None or dr is not None or dw is not None:
+                ws = _instnorm_split_workspace(x, B * C, N)   # (the fp64 partials of d weight live in it)
+                _call("instnorm_prelu_split_bwd", "cocos_instnorm_prelu_split_bwd", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(),
+                      stats.data_ptr(), _ptr(dx), _ptr(dr), _ptr(dw), ws.data_ptr(), _ptr(cell), B * C, N, ctx.eps, _stream())
         else:
-            _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(),
-                  _ptr(dx), _ptr(dr), None, B * C, N, ctx.eps, _stream())
-        return dx, dr, (dw.reshape(w.shape) if need_w else None), None
+            if need_w:
+                dap = torch.empty(B * C, device=x.device, dtype=torch.float64)
+            if cell is not None:
+                part = torch.empty(B * C, device=x.device, dtype=torch.float32)
+                _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd_amax", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                      _ptr(dr), _ptr(dap), _ptr(dw), cell.data_ptr(), part.data_ptr(), B * C, N, ctx.eps, _stream())
+            elif need_w:
+                _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd_f64", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(),
+                      _ptr(dx), _ptr(dr), dap.data_ptr(), dw.data_ptr(), B * C, N, ctx.eps, _stream())
+            else:
+                _call("instnorm_prelu_bwd", "cocos_instnorm_prelu_bwd", x.data_ptr(), _ptr(res), w.data_ptr(), dy.data_ptr(),
+                      _ptr(dx), _ptr(dr), None, B * C, N, ctx.eps, _stream())
+        if cell is not None:
+            _remember_amax(dx, cell, weak=True)
+        return dx, dr, (dw.reshape(w.shape) if need_w else None), None, None
 
 
 def instnorm_prelu(x, residual, weight, eps: float = INSTNORM_EPS):
     """prelu(InstanceNorm2d(x) [+ residual], weight) for x [B,C,h,w]: nn.InstanceNorm2d(affine=False) statistics per
     (sample, channel) plane, nn.PReLU() with one parameter."""
-    return _InstNormPReLU.apply(x, residual, weight, eps)
+    return _InstNormPReLU.apply(x, residual, weight, eps, False)
+
+
+def instnorm_prelu_split(x, residual, weight, eps: float = INSTNORM_EPS):
+    """K34 (instnorm_split.hip): `instnorm_prelu` for planes of any size — every (sample, channel) plane is cut into slices of 16384
+    positions, one workgroup each, so a [B, 64, 256, 256] activation fills the device instead of running one workgroup per plane.
+    Saves x, the residual, the weight and the per-plane (mean, rstd)."""
+    return _InstNormPReLU.apply(x, residual, weight, eps, True)
 
 
 # ------------------------------------------------------------------------------------------

@@ -410,16 +410,18 @@ class AdaptiveFeatureGenerator(nn.Module):
                 and not layer[1].track_running_stats and x.is_cuda and x.dtype == torch.float32 and conv_backend() in _HIP_BACKENDS):
             from . import ops
             y = layer[0](x)
-            if y.shape[2] * y.shape[3] > 16384:
+            large = y.shape[2] * y.shape[3] > 16384
+            if large and not ops.INSTNORM_SPLIT:
                 # K13 keeps a plane in registers up to 128 x 128; beyond that its streaming flavour (one workgroup per plane, five
-                # passes backward) measured SLOWER than the framework's two-kernel batch norm (2.1 vs 1.2 ms per step): not used
+                # passes backward) measured SLOWER than the framework's two-kernel batch norm (2.1 vs 1.2 ms per step).  Larger
+                # planes take K34 (a plane over several workgroups) under ops.INSTNORM_SPLIT, the framework otherwise
                 y = layer[1](y)
                 return y if slope == 1.0 else nn.functional.leaky_relu(y, slope)
             key = (y.device, float(slope))
             w = self._slopes.get(key)
             if w is None:
                 w = self._slopes[key] = torch.full((1,), float(slope), device=y.device, dtype=torch.float32)
-            return ops.instnorm_prelu(y, None, w, layer[1].eps)
+            return (ops.instnorm_prelu_split if large else ops.instnorm_prelu)(y, None, w, layer[1].eps)
         y = layer(x)
         return y if slope == 1.0 else nn.functional.leaky_relu(y, slope)
 

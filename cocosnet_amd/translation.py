@@ -88,11 +88,12 @@ class _ConvNormAct(nn.Sequential):
         if (isinstance(first, nn.Sequential) and len(first) == 2 and type(first[1]) is nn.InstanceNorm2d and not first[1].affine
                 and x.is_cuda and x.dtype == torch.float32 and ops.CONV_PRECISION != "torch" and len(self) == 2):
             y = first[0](x)
-            if y.shape[2] * y.shape[3] <= 16384:
+            large = y.shape[2] * y.shape[3] > 16384           # beyond K13's register path: K34 under ops.INSTNORM_SPLIT
+            if not large or ops.INSTNORM_SPLIT:
                 slope = getattr(self, "_slope", None)
                 if slope is None or slope.device != y.device:
                     slope = self._slope = torch.full((1,), float(self[1].negative_slope), device=y.device)
-                return ops.instnorm_prelu(y, None, slope, first[1].eps)
+                return (ops.instnorm_prelu_split if large else ops.instnorm_prelu)(y, None, slope, first[1].eps)
             y = first[1](y)
             return self[1](y)
         return super().forward(x)

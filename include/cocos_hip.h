@@ -1095,6 +1095,31 @@ int cocos_instnorm_prelu_bwd_amax(const float* x, const float* residual, const f
                                   float* dresidual, double* da_partials_f64, float* da_out, float* dx_amax_inout_dev, float* amax_partials,
                                   int planes, int N, float eps, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K34 the same InstanceNorm2d(affine=False) (+ residual) + PReLU for planes of ANY size: a plane is cut into
+ *     S = ceil(N / 16384) slices, one workgroup each, and every direction is two launches (per-slice partials, then
+ *     the apply pass that combines them in a fixed order) — the adaptors' layer1 at the full image size
+ *     (correspondence.py:150-173) and the PatchGAN's first norm (discriminator.py:92-115).  No workgroup waits for
+ *     another, no atomics: results are bitwise reproducible.  Any planes >= 1, N >= 1 (N % 4 != 0 or tensors that are
+ *     not 16-byte aligned take 4-byte accesses).
+ *   cocos_instnorm_prelu_split_workspace_floats: floats of `workspace` for either call (host arithmetic, no GPU needed;
+ *       0 for planes < 1 or N < 1) = 7 * planes * S: the forward's (mean, M2) and the backward's (sum dz, sum dz xn) per
+ *       slice, the fp64 da partials (two floats each) and one maximum per slice.  8-byte aligned.  The same buffer may
+ *       serve both calls; its contents need not survive between them.
+ *   _fwd: y as K13's; stats [planes][2] = (mean, 1/sqrt(biased var + eps)) of every plane, which _bwd takes instead of
+ *       recomputing them (per-slice mean and centred squares, combined by Chan's formula in fp64).
+ *       y_amax_inout_dev (nullable): *cell = max(*cell, max|y|), the cell holding a finite value >= 0.
+ *   _bwd: dx (nullable), dresidual (nullable, = dz), da_out (nullable): 1 float = sum over the layer of dy z where
+ *       z <= 0, accumulated in fp64 from the products to the last addition as cocos_instnorm_prelu_bwd_f64 does.
+ *       dx_amax_inout_dev (nullable, needs dx): *cell = max(*cell, max|dx|).  eps is not read (the statistics are given).
+ * ------------------------------------------------------------------------------------- */
+size_t cocos_instnorm_prelu_split_workspace_floats(int planes, int N);
+int cocos_instnorm_prelu_split_fwd(const float* x, const float* residual, const float* prelu_weight, float* y, float* stats,
+                                   float* workspace, float* y_amax_inout_dev, int planes, int N, float eps, cocos_stream_t stream);
+int cocos_instnorm_prelu_split_bwd(const float* x, const float* residual, const float* prelu_weight, const float* dy,
+                                   const float* stats, float* dx, float* dresidual, float* da_out, float* workspace,
+                                   float* dx_amax_inout_dev, int planes, int N, float eps, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
