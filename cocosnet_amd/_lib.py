@@ -99,6 +99,10 @@ _SIGNATURES = {
                                                                                                     _c_float_p, ctypes.c_void_p]
                                              + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, _c_float_p, _c_float_p,
                                                                      _c_float_p, _c_float_p, ctypes.c_int, _stream_t]),
+    "cocos_corr_softmax_warp_fwd_f16x3_shared": (ctypes.c_int, [ctypes.c_void_p] * 6 + [_c_float_p] * 2 + [ctypes.c_void_p,
+                                                                                                        _c_float_p, ctypes.c_void_p]
+                                                 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, ctypes.c_longlong,
+                                                                         ctypes.c_longlong, _stream_t]),
     "cocos_f16_plane_block_mask": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p, _stream_t]),
     "cocos_split_f16_ex": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5
                            + [ctypes.c_float, _c_float_p, _c_float_p, _stream_t]),

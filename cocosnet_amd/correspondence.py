@@ -126,9 +126,78 @@ class NoVGGCorrespondence(NetworkBase):
         yy = ys.view(1, 1, h, 1).expand(B, 1, h, w)
         return torch.cat((x, xx, yy, torch.sqrt(xx ** 2 + yy ** 2)), dim=1)
 
-    def project(self, ref_img, real_img, seg_map, ref_seg_map, coor_out=None, lazy=False):
-        """Everything BEFORE the hot path (:239-272, :282): returns (theta_raw, phi_raw)."""
+    def exemplar_stream(self, ref_img, ref_seg_map):
+        """The exemplar side of project() up to and including `self.layer` (:240-266): adaptive_model_img, feature_normalize,
+        coord-conv, the maskmix concat (with its noise_for_mask draw) and the four shared ResidualBlocks.  What
+        inference.prepare_exemplar runs once; the ordinary route keeps its own (batched) copy in project()."""
         opt = self.opt
+        feat_img = feature_normalize(self.adaptive_model_img(ref_img, ref_img))
+        if opt.use_coordconv:
+            feat_img = self.addcoords(feat_img)
+        if opt.maskmix:
+            ref_seg = F.interpolate(ref_seg_map, size=feat_img.shape[2:], mode="nearest")
+            if opt.noise_for_mask and ((not opt.isTrain) or (opt.isTrain and opt.epoch > opt.mask_epoch)):
+                noise = torch.randn_like(ref_seg, requires_grad=False) * 0.01
+                ref_in = torch.cat((feat_img, noise), 1)
+            else:
+                ref_in = torch.cat((feat_img, ref_seg), 1)
+        else:
+            ref_in = feat_img
+        return self.layer(ref_in)
+
+    def _check_exemplar(self, exemplar, batch):
+        """the record, fresh — or ValueError where a record cannot stand in for the exemplar stream"""
+        opt = self.opt
+        if not isinstance(exemplar, inference.PreparedExemplar) or exemplar.net is not self:
+            raise ValueError("exemplar: expected the record inference.prepare_exemplar(net, ...) made for THIS network")
+        if self.training:
+            raise ValueError("exemplar: a prepared exemplar needs net.eval()")
+        if (torch.is_grad_enabled() and opt.isTrain) or opt.warp_cycle_w > 0 or (opt.isTrain and opt.novgg_featpair > 0):
+            # the cycle terms (warp_cycle_w, and two_cycle, which only exists with it) and novgg_featpair are training terms whose
+            # gradient runs through the exemplar side; the path computes the cycle terms whenever warp_cycle_w > 0.  THE rule: the
+            # hot path itself only insists on torch.no_grad()
+            raise ValueError("exemplar: a prepared exemplar is inference-only (grad mode with isTrain, warp_cycle_w / two_cycle and "
+                             "novgg_featpair need the exemplar stream)")
+        if exemplar.batch not in (batch, 1):
+            raise ValueError(f"exemplar: prepared for a batch of {exemplar.batch}, used with {batch} inputs (expected {batch} or 1)")
+        return exemplar.ensure() if inference.FROZEN else exemplar      # (ignored under COCOS_FROZEN=0: nothing is prepared for it)
+
+    def _project_content(self, seg_map, exemplar, lazy):
+        """project() with a prepared exemplar: the content stream alone (`self.layer` sees cont_in alone)."""
+        opt = self.opt
+        if opt.mask_noise:
+            noise = torch.randn_like(seg_map, requires_grad=False) * 0.1
+            noise[seg_map == 0] = 0
+            seg_input = seg_map + noise
+        else:
+            seg_input = seg_map
+        feat_seg = feature_normalize(self.adaptive_model_seg(seg_input, seg_input))
+        if opt.use_coordconv:
+            feat_seg = self.addcoords(feat_seg)
+        if opt.maskmix:
+            seg = F.interpolate(seg_map, size=feat_seg.shape[2:], mode="nearest")
+            cont = self.layer(torch.cat((feat_seg, seg), 1))
+        else:
+            cont = self.layer(feat_seg)
+        if cont.is_cuda and cont.dtype == torch.float32:
+            rt = inference.usable_record(self.theta)
+            if lazy:
+                return ops.LazyProj1x1(cont, self.theta.weight, self.theta.bias, rt), exemplar.keys
+            return ops.proj1x1(cont, self.theta.weight, self.theta.bias, rt), exemplar.phi_raw()
+        return self.theta(cont), exemplar.phi_raw()
+
+    def project(self, ref_img, real_img, seg_map, ref_seg_map, coor_out=None, lazy=False, *, exemplar=None):
+        """Everything BEFORE the hot path (:239-272, :282): returns (theta_raw, phi_raw).  `exemplar`: a record of
+        inference.prepare_exemplar — ref_img / ref_seg_map may then be None, only the content stream runs and phi_raw is the record's
+        (with inference.FROZEN off the record is ignored: the ordinary route, from the record's stored inputs)."""
+        opt = self.opt
+        if exemplar is not None:
+            exemplar = self._check_exemplar(exemplar, seg_map.shape[0])
+            if inference.FROZEN:
+                return self._project_content(seg_map, exemplar, lazy)
+            ref_img, ref_seg_map = _stored_inputs(exemplar, seg_map.shape[0])
+        elif ref_img is None or ref_seg_map is None:
+            raise ValueError("project: ref_img and ref_seg_map are required without a prepared exemplar")
         if opt.mask_noise:
             noise = torch.randn_like(seg_map, requires_grad=False) * 0.1
             noise[seg_map == 0] = 0
@@ -173,17 +242,41 @@ class NoVGGCorrespondence(NetworkBase):
         return self.theta(cont), self.phi(ref)   # CPU / fp64: producer parity tests only; the hot path needs a GPU and fp32
 
     def forward(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, detach_flag=False,
-                WTA_scale_weight=1, alpha=1, return_corr=False):
+                WTA_scale_weight=1, alpha=1, return_corr=False, *, exemplar=None):
         coor_out = {}
-        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        keys = None
+        if exemplar is not None:
+            exemplar = self._check_exemplar(exemplar, seg_map.shape[0])
+            if inference.FROZEN:
+                with torch.no_grad():
+                    theta_raw, keys = self._project_content(seg_map, exemplar, lazy=True)
+                phi_raw = ref_img = ref_seg_map = None
+            else:
+                ref_img, ref_seg_map = _stored_inputs(exemplar, seg_map.shape[0])
+        elif ref_img is None or ref_seg_map is None:
+            raise ValueError("forward: ref_img and ref_seg_map are required without a prepared exemplar")
+        if keys is None:
+            theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-        res = correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_seg_map, cfg,
-                                      temperature=temperature, detach_flag=detach_flag,
-                                      WTA_scale_weight=WTA_scale_weight, return_corr=return_corr)
+        kw = dict(temperature=temperature, detach_flag=detach_flag, WTA_scale_weight=WTA_scale_weight, return_corr=return_corr)
+        if keys is None:      # (the ordinary call, argument for argument as before)
+            res = correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_seg_map, cfg, **kw)
+        else:
+            with torch.no_grad():      # a record's route is forward-only
+                res = correspondence_hot_path(theta_raw, None, None, real_img, seg_map, None, cfg, exemplar=keys, **kw)
         if return_corr:
             return res
         coor_out.update(res)
         return coor_out
+
+
+def _stored_inputs(exemplar, batch):
+    """(ref_img, ref_seg_map) of a record for the ordinary route: one exemplar for all inputs is repeated"""
+    ref_img, ref_seg_map = exemplar.ref_img, exemplar.ref_seg_map
+    if ref_img.shape[0] != batch:
+        ref_img = ref_img.expand(batch, -1, -1, -1).contiguous()
+        ref_seg_map = ref_seg_map.expand(batch, -1, -1, -1).contiguous()
+    return ref_img, ref_seg_map
 
 
 def base_options(**overrides) -> argparse.Namespace:

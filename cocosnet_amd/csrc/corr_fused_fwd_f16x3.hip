@@ -109,6 +109,8 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
     const _Float16* __restrict__ kl, const _Float16* __restrict__ vh, const _Float16* __restrict__ vl,
     float* __restrict__ out, float* __restrict__ lse, float* __restrict__ lg, const float* __restrict__ v_scale,
     const unsigned* __restrict__ v_lo_mask, int B, int Nq, int Nk, int Cv, float scale_log2 /* inv_temperature * log2(e) / (q_scale * k_scale) */,
+    size_t k_bstride /* halfs from one sample's key planes to the next: Nk * 256, or 0 = every sample reads ONE key set */,
+    size_t v_bstride /* the same of the value planes: Cv * Nk, or 0 */,
     float* __restrict__ rowstat = nullptr /* RAWM: [B][3][Nq] = (m_hi, m_lo in raw units, log2 l - bias) for the backward; nullable */,
     float* __restrict__ mtile = nullptr /* RAWM + STORE_S: [B][Nk/32 tiles][2][Nq] = (m_hi, m_lo) when the tile's logits were stored */) {
     // KST (RAWM): 16-channel steps that hold non-zero channels — the Attention block's K = C/8 = 32 or 64 channels sit zero-padded
@@ -135,10 +137,10 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
     const size_t qbytes = (size_t)Nq * SP_KD * 2, kbytes = (size_t)Nk * SP_KD * 2, vbytes = (size_t)Cv * Nk * 2;
     const __amdgpu_buffer_rsrc_t qh_rs = make_rsrc(qh + (size_t)b * Nq * SP_KD, qbytes);
     const __amdgpu_buffer_rsrc_t ql_rs = make_rsrc(ql + (size_t)b * Nq * SP_KD, qbytes);
-    const __amdgpu_buffer_rsrc_t kh_rs = make_rsrc(kh + (size_t)b * Nk * SP_KD, kbytes);
-    const __amdgpu_buffer_rsrc_t kl_rs = make_rsrc(kl + (size_t)b * Nk * SP_KD, kbytes);
-    const __amdgpu_buffer_rsrc_t vh_rs = make_rsrc(vh + (size_t)b * Cv * Nk, vbytes);
-    const __amdgpu_buffer_rsrc_t vl_rs = make_rsrc(vl + (size_t)b * Cv * Nk, vbytes);
+    const __amdgpu_buffer_rsrc_t kh_rs = make_rsrc(kh + (size_t)b * k_bstride, kbytes);
+    const __amdgpu_buffer_rsrc_t kl_rs = make_rsrc(kl + (size_t)b * k_bstride, kbytes);
+    const __amdgpu_buffer_rsrc_t vh_rs = make_rsrc(vh + (size_t)b * v_bstride, vbytes);
+    const __amdgpu_buffer_rsrc_t vl_rs = make_rsrc(vl + (size_t)b * v_bstride, vbytes);
     // saved logits, tile-blocked (see header): per sample ntiles x nqblk blocks of 4 KB
     const int nqblk = (Nq + 31) / 32;
     const size_t lg_bytes = (size_t)((Nk + SP_BK - 1) / SP_BK) * nqblk * 4096;
@@ -541,19 +543,19 @@ __global__ __launch_bounds__(256, 1) void corr_fwd_f16x3_kernel(
     float* __restrict__ out, float* __restrict__ lse, float* __restrict__ lg, const float* __restrict__ v_scale,
     const unsigned* __restrict__ v_lo_mask, int B, int Nq, int Nk, int Cv, float scale_log2,
     const float* __restrict__ q_scale_dev, const float* __restrict__ k_scale_dev, float* __restrict__ rowstat,
-    float* __restrict__ mtile, int ksteps) {
+    float* __restrict__ mtile, int ksteps, size_t k_bstride, size_t v_bstride) {
     // operands without an a-priori magnitude (ops.softmax_attention: the reference's Attention block feeds raw 1x1-conv
     // outputs): their planes carry device-side power-of-two scales; scale_log2 then arrives WITHOUT the 1 / (q_scale k_scale)
     if (q_scale_dev) scale_log2 = scale_log2 / (*q_scale_dev * *k_scale_dev);
     if constexpr (DUAL) {
         if ((__builtin_amdgcn_readfirstlane(*v_lo_mask) & ~1u) == 0u)
-            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, true>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2);
+            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, true>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
         else
-            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2);
+            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
     } else {
         if (q_scale_dev) {        // the magnitude-free flavour (host side: no lo mask together with device-side operand scales)
 #define COCOS_RAWM_BODY(KST_) corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false, true, KST_>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, \
-                                                                                           v_lo_mask, B, Nq, Nk, Cv, scale_log2, rowstat, mtile)
+                                                                                           v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride, rowstat, mtile)
             if constexpr (RAGGED) {      // (odd key counts: the general instantiation only)
                 COCOS_RAWM_BODY(SP_KD / 16);
             } else {
@@ -564,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void corr_fwd_f16x3_kernel(
             }
 #undef COCOS_RAWM_BODY
         } else
-            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2);
+            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
     }
 }
 
@@ -572,14 +574,15 @@ template <int CVB, bool STORE_S, bool RAGGED, bool VLO0>
 static int launch_f16x3_k(const _Float16* qh, const _Float16* ql, const _Float16* kh, const _Float16* kl,
                           const _Float16* vh, const _Float16* vl, float* out, float* lse, float* lg,
                           const float* v_scale, const unsigned* v_lo_mask, int B, int Nq, int Nk, int Cv, float scale_log2,
-                          const float* qsd, const float* ksd, float* rowstat, float* mtile, int ksteps, hipStream_t stream) {
+                          const float* qsd, const float* ksd, float* rowstat, float* mtile, int ksteps, size_t k_bstride, size_t v_bstride,
+                          hipStream_t stream) {
     auto kern = corr_fwd_f16x3_kernel<CVB, STORE_S, RAGGED, VLO0>;
     const size_t smem = (size_t)2 * (2 * SP_BK * SP_KROW + 3 * CVB * 32 * SP_VROW) * sizeof(_Float16);
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int nqb = (Nq + SP_BQ - 1) / SP_BQ;
     hipLaunchKernelGGL(kern, dim3(B * nqb), dim3(256), smem, stream, qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale,
-                       v_lo_mask, B, Nq, Nk, Cv, scale_log2, qsd, ksd, rowstat, mtile, ksteps);
+                       v_lo_mask, B, Nq, Nk, Cv, scale_log2, qsd, ksd, rowstat, mtile, ksteps, k_bstride, v_bstride);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }
@@ -625,13 +628,15 @@ extern "C" int cocos_corr_softmax_warp_fwd_f16x3(const void* qh, const void* ql,
                                                 Nk, Cv, inv_temperature, operand_scale, q_scale_dev, k_scale_dev, nullptr, nullptr, 0, stream);
 }
 
-extern "C" int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* ql, const void* kh,
-                                                    const void* kl, const void* vh, const void* vl, float* out,
-                                                    float* lse, void* saved_logits, const float* v_scale_dev,
-                                                    const unsigned* v_lo_mask_dev, int B,
-                                                    int K, int Nq, int Nk, int Cv, float inv_temperature,
-                                                    float operand_scale, const float* q_scale_dev, const float* k_scale_dev,
-                                                    float* rowstat_out, float* mtile_out, int k_active, cocos_stream_t stream) {
+// The one implementation behind the entry points.  dense_kv: the key and value planes are [B][...] like the query's; else every
+// sample reads the ONE key / value set at kh, kl, vh, vl (batch stride 0: cocos_corr_softmax_warp_fwd_f16x3_shared).
+static int corr_softmax_warp_fwd_f16x3_impl(const void* qh, const void* ql, const void* kh,
+                                            const void* kl, const void* vh, const void* vl, float* out,
+                                            float* lse, void* saved_logits, const float* v_scale_dev,
+                                            const unsigned* v_lo_mask_dev, int B,
+                                            int K, int Nq, int Nk, int Cv, float inv_temperature,
+                                            float operand_scale, const float* q_scale_dev, const float* k_scale_dev,
+                                            float* rowstat_out, float* mtile_out, int k_active, bool dense_kv, cocos_stream_t stream) {
     using namespace cocos;
     COCOS_REQUIRE(k_active >= 0 && k_active <= K && (k_active == 0 || k_active == K || q_scale_dev), COCOS_ERR_INVALID,
                   "corr_softmax_warp_fwd_f16x3: k_active=%d (channels >= k_active are zero in q and k) belongs to the magnitude-free flavour", k_active);
@@ -668,6 +673,7 @@ extern "C" int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* 
                   "corr_softmax_warp_fwd_f16x3: the device-side operand scales come as a pair");
     const float scale_log2 = q_scale_dev ? inv_temperature * kLog2e : inv_temperature * kLog2e / (operand_scale * operand_scale);
     const bool ragged = (Nk % SP_BK) != 0;
+    const size_t k_bstride = dense_kv ? (size_t)Nk * SP_KD : 0, v_bstride = dense_kv ? (size_t)Cv * Nk : 0;
     float* lgp = static_cast<float*>(saved_logits);
     const _Float16 *a = static_cast<const _Float16*>(qh), *b2 = static_cast<const _Float16*>(ql),
                    *c2 = static_cast<const _Float16*>(kh), *d = static_cast<const _Float16*>(kl),
@@ -675,7 +681,7 @@ extern "C" int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* 
     // with a mask and more than one value block the kernel holds both flavours and picks one from the device-side mask
 #define COCOS_GO(CVB, ST, RG) \
     cocos_go_both<CVB, ST, RG>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, v_lo_mask_dev, B, Nq, Nk, Cv, scale_log2, \
-                               q_scale_dev, k_scale_dev, rowstat_out, mtile_out, ksteps, s)
+                               q_scale_dev, k_scale_dev, rowstat_out, mtile_out, ksteps, k_bstride, v_bstride, s)
 #define COCOS_CVB(CVB)                                                           \
     case CVB:                                                                    \
         if (lgp) return ragged ? COCOS_GO(CVB, true, true) : COCOS_GO(CVB, true, false); \
@@ -686,4 +692,39 @@ extern "C" int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* 
     }
 #undef COCOS_CVB
 #undef COCOS_GO
+}
+
+extern "C" int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* ql, const void* kh,
+                                                    const void* kl, const void* vh, const void* vl, float* out,
+                                                    float* lse, void* saved_logits, const float* v_scale_dev,
+                                                    const unsigned* v_lo_mask_dev, int B,
+                                                    int K, int Nq, int Nk, int Cv, float inv_temperature,
+                                                    float operand_scale, const float* q_scale_dev, const float* k_scale_dev,
+                                                    float* rowstat_out, float* mtile_out, int k_active, cocos_stream_t stream) {
+    return corr_softmax_warp_fwd_f16x3_impl(qh, ql, kh, kl, vh, vl, out, lse, saved_logits, v_scale_dev, v_lo_mask_dev, B, K, Nq, Nk, Cv,
+                                            inv_temperature, operand_scale, q_scale_dev, k_scale_dev, rowstat_out, mtile_out, k_active,
+                                            true, stream);
+}
+
+extern "C" int cocos_corr_softmax_warp_fwd_f16x3_shared(const void* qh, const void* ql, const void* kh,
+                                                        const void* kl, const void* vh, const void* vl, float* out,
+                                                        float* lse, void* saved_logits, const float* v_scale_dev,
+                                                        const unsigned* v_lo_mask_dev, int B,
+                                                        int K, int Nq, int Nk, int Cv, float inv_temperature,
+                                                        float operand_scale, long long k_batch_stride,
+                                                        long long v_batch_stride, cocos_stream_t stream) {
+    COCOS_REQUIRE(!saved_logits, COCOS_ERR_INVALID,
+                  "corr_softmax_warp_fwd_f16x3_shared: inference only: saved_logits must be NULL");
+    COCOS_REQUIRE(v_scale_dev, COCOS_ERR_INVALID, "corr_softmax_warp_fwd_f16x3_shared: null pointer (v_scale_dev)");
+    COCOS_REQUIRE(K == 256, COCOS_ERR_UNSUPPORTED, "corr_softmax_warp_fwd_f16x3_shared: needs K == 256 (got %d)", K);
+    COCOS_REQUIRE(B >= 1 && Nq >= 1 && Nk >= 1 && Cv >= 1, COCOS_ERR_INVALID,
+                  "corr_softmax_warp_fwd_f16x3_shared: bad dims B=%d Nq=%d Nk=%d Cv=%d", B, Nq, Nk, Cv);
+    // both sides dense or both shared: the record owns keys and values of the same exemplars
+    const long long kd = (long long)Nk * K, vd = (long long)Cv * Nk;
+    const bool dense = k_batch_stride == kd && v_batch_stride == vd;
+    COCOS_REQUIRE(dense || (k_batch_stride == 0 && v_batch_stride == 0), COCOS_ERR_INVALID,
+                  "corr_softmax_warp_fwd_f16x3_shared: batch strides (%lld, %lld): expected (0, 0) or the dense (%lld, %lld)",
+                  k_batch_stride, v_batch_stride, kd, vd);
+    return corr_softmax_warp_fwd_f16x3_impl(qh, ql, kh, kl, vh, vl, out, lse, nullptr, v_scale_dev, v_lo_mask_dev, B, K, Nq, Nk, Cv,
+                                            inv_temperature, operand_scale, nullptr, nullptr, nullptr, nullptr, 0, dense, stream);
 }

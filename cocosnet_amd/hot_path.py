@@ -123,6 +123,8 @@ class _Attention:
 
     def rows(self, v):
         """softmax over exemplar positions, then @ v   (f_div_C @ v, :307/:318)."""
+        if isinstance(v, ops.PreparedValues):      # a record's value tensor on a back end without a native broadcast
+            v = v.expanded(self._batch())
         if self.fused:
             return ops.corr_softmax_warp(self.qn, self.kn, v, self.inv_t, self._planes)
         if self._boxed is not None:
@@ -130,6 +132,14 @@ class _Attention:
         if self._lk is not None:
             return ops.logits_softmax_warp(self._get("lk", self._lk), v)
         return ops.warp_materialized(self._get("p_row", lambda: ops.row_softmax(self._f)), v)
+
+    def _batch(self):
+        """B of this call, for a record's value tensor that has to be expanded"""
+        if self.fused:
+            return self.qn.shape[0]
+        if self._boxed is not None:
+            return self._boxed.th.shape[0]
+        return (self._f if self._f is not None else self._get("lk" if self._lk is not None else "lq", self._lk or self._lq)).shape[0]
 
     def cols(self, v):
         """softmax over content positions of f^T, then @ v   (f_div_C_v @ v, :338/:351)."""
@@ -143,17 +153,65 @@ class _Attention:
             self._get("p_col", lambda: ops.row_softmax(self._f.transpose(1, 2).contiguous())), v)
 
 
+class _SharedAttention(_Attention):
+    """The fused back end of a call with a prepared exemplar (ops.PreparedKeys): the row pass over the record's own value tensor
+    reads the record's key / value planes in place (cocos_corr_softmax_warp_fwd_f16x3_shared: ONE set for all B inputs when the
+    record's batch is 1).  Every other pass (cycle mask: columns, second row pass) runs the ordinary kernels over per-call
+    OperandPlanes, made the first time such a pass comes: handles for qn / kn and the record's key planes, expanded to B."""
+
+    def __init__(self, qh, ql, keys, inv_t):
+        super().__init__(inv_t=inv_t)
+        self._qh, self._ql, self._keys = qh, ql, keys
+
+    def _ordinary(self):
+        if not self.fused:
+            B, N, C = self._qh.shape
+            kh, kl, _ = self._keys.split_planes(B)
+            self._planes = ops.OperandPlanes()
+            # (handles: fp32 tensors that stand for the planes and are never written or read — see ops._CenterL2NormPlanes)
+            self.qn = torch.empty((B, C, N), device=self._qh.device, dtype=torch.float32)
+            self.kn = torch.empty((B, C, kh.shape[1]), device=self._qh.device, dtype=torch.float32)
+            self._planes.put(self.qn, True, ops.SPLIT_OPERAND_SCALE, self._qh, self._ql)
+            self._planes.put(self.kn, True, ops.SPLIT_OPERAND_SCALE, kh, kl)
+            self.fused = True
+
+    def rows(self, v):
+        if isinstance(v, ops.PreparedValues) and v.v.shape[1] <= ops.MAX_FUSED_SPLIT_CV:
+            return ops.corr_softmax_warp_shared(self._qh, self._ql, self._keys, v, self.inv_t)
+        self._ordinary()
+        return super().rows(v)
+
+    def cols(self, v):
+        self._ordinary()
+        return super().cols(v)
+
+
 class _BoxedCorr:
     """match_kernel 3, PONO_C, 64- or 128-wide grid: the statistics of the unfolded vectors (K12) and, per orientation that is
     actually used, T = xbox(C_raw) from the correlation GEMM's epilogue; every softmax + warp pass then reads T three
     blocks at a time (K19).  Nothing box-filtered and no logits matrix reaches HBM."""
 
-    def __init__(self, theta_raw, phi_raw, inv_t):
+    def __init__(self, theta_raw, phi_raw, inv_t, prepared_k=None):
         _, C, self.fh, self.fw = theta_raw.shape
         self.kc = float(C * 9)
         self._cache = {}
         self._raw_planes = None
-        if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_raw_fused_ok(theta_raw, phi_raw):
+        if prepared_k is not None:
+            # a prepared exemplar (inference only): phi's planes and (nu, b) are the record's, `phi_raw` is a handle that stands for
+            # them; theta alone goes through K0, K12 and the operand split — the key side is not touched
+            kh, kl, ks, nu, b = prepared_k
+            if isinstance(theta_raw, ops.LazyProj1x1):
+                theta_raw = theta_raw.raw()
+            theta_raw = theta_raw.detach()
+            B = theta_raw.shape[0]
+            mu, a = ops.unfold3_stats(theta_raw, self.kc)
+            tf = theta_raw.reshape(B, C, -1)
+            qh, ql, qs = ops.split_f16(tf, True, amax=ops.absmax(tf))
+            self._raw_planes = ops.Box3RawPlanes()
+            self._raw_planes.put(theta_raw, qh, ql, None, None, qs)
+            self._raw_planes.put(phi_raw, kh, kl, None, None, ks)
+            self._cache["q"], self._cache["k"] = (mu, a), (nu, b)
+        elif isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_raw_fused_ok(theta_raw, phi_raw):
             # round 6, K25: ONE launch from the features of both tensors to the operand planes of the raw projections and the sums
             # behind K12's statistics — the fp32 projections never exist; theta_raw / phi_raw are autograd handles from here on
             self._raw_planes = ops.Box3RawPlanes()
@@ -251,16 +309,94 @@ def _scaled_logits(theta_raw, phi_raw, cfg, inv_t, detach_flag, wta):
     return f * inv_t                                                         # :304 (detached: no graph)
 
 
+def _row_values(ref_img, ref_seg_map, down, patch, direct_mask, fused_values):
+    """(V of the row pass [B,Cv,HW], number of image channels): pooled exemplar (or its patches) + the sampled direct mask"""
+    if fused_values:
+        # pooled image (or its patches, --warp_patch) + sampled mask in one kernel (K14)
+        v1 = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down, patch=patch))
+        return v1, ref_img.shape[1] * (down * down if patch else 1)
+    if patch:
+        ref = F.unfold(ref_img, down, stride=down)                    # [B, 3*down^2, HW]
+    else:
+        ref = _flat(F.avg_pool2d(ref_img, down))                      # [B, 3, HW]
+    v_r1 = [ref]
+    if direct_mask:
+        ref_seg = F.interpolate(ref_seg_map, scale_factor=1 / down, mode="nearest")
+        v_r1.append(_flat(ref_seg))
+    return (torch.cat(v_r1, dim=1) if len(v_r1) > 1 else ref), ref.shape[1]
+
+
+def _fused_values_ok(ref_img, ref_seg_map, down, patch, direct_mask, modes):
+    H, W = ref_img.shape[2], ref_img.shape[3]
+    return bool((modes or (direct_mask and not patch)) and _hip_fp32(ref_img) and not ref_img.requires_grad
+                and (not direct_mask or (_hip_fp32(ref_seg_map) and not ref_seg_map.requires_grad))
+                and H % down == 0 and W % down == 0)
+
+
+def exemplar_values(ref_img, ref_seg_map, down, patch, direct_mask) -> "ops.PreparedValues":
+    """The row pass's value tensor as a prepared exemplar keeps it (inference.PreparedExemplar): the same tensor the ordinary route
+    forms per call (its max|v| cell is taken when the split flavour first asks for the planes)."""
+    modes = ops.WARP_HEAD_MODES and _hip_fp32(ref_img)
+    v1, n_ref = _row_values(ref_img, ref_seg_map, down, patch, direct_mask,
+                            _fused_values_ok(ref_img, ref_seg_map, down, patch, direct_mask, modes))
+    v1 = v1.contiguous()
+    return ops.PreparedValues(v1, n_ref)
+
+
+def _attention_with_exemplar(theta_raw, keys, cfg, inv_t, WTA_scale_weight, return_corr):
+    """The _Attention of a forward call whose exemplar side is a record (ops.PreparedKeys): the query side is made here, per call;
+    key planes / statistics / phi_raw come from the record — in place on the fused match_kernel-1 back end (any record batch),
+    expanded to B once per record on the others."""
+    B, C, fh, fw = theta_raw.shape
+    N = fh * fw
+    mk = cfg.match_kernel
+    keys.check(B)
+    if keys.shape[1:] != theta_raw.shape[1:]:
+        raise ValueError(f"prepared exemplar: feature grid {tuple(keys.shape)} does not match the content's {tuple(theta_raw.shape)}")
+    plain = WTA_scale_weight == 1 and not return_corr
+    if (mk == 1 and C == ops.FUSED_K and plain and cfg.PONO_C and _hip_fp32(theta_raw)
+            and ops.corr_split_ok(B, C, N, N, 1, False)):
+        if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
+            qh, ql, _ = ops.proj_center_l2norm_planes_one(theta_raw, 1)      # K23, theta alone
+        else:
+            th = theta_raw.raw() if isinstance(theta_raw, ops.LazyProj1x1) else theta_raw
+            qh, ql, _ = ops.center_l2norm_planes_fwd(_flat(th), 1)
+        return _SharedAttention(qh, ql, keys, inv_t)
+    theta = theta_raw.raw() if isinstance(theta_raw, ops.LazyProj1x1) else theta_raw
+    if mk == 3 and cfg.PONO_C and plain and _hip_fp32(theta) and ops.box3_fused_ok(B, C, fh, fw):
+        pk = keys.box_planes(B)
+        theta = theta.detach()
+        ph = theta.view_as(theta)      # a handle for phi's planes (another object of theta's shape, no memory): never read
+        return _Attention(inv_t=inv_t, boxed=_BoxedCorr(theta, ph, inv_t, prepared_k=pk))
+    return None      # every other back end reads phi_raw as fp32: the caller continues on the ordinary route with keys.phi_raw(B)
+
+
 def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_seg_map,
                             cfg: HotPathConfig, temperature=0.01, detach_flag=False,
-                            WTA_scale_weight=1, return_corr=False):
+                            WTA_scale_weight=1, return_corr=False, *, exemplar=None):
     """correspondence.py:272-372 from the theta/phi conv outputs onward.
 
     theta_raw, phi_raw: [B,256,h,w] CUDA fp32.  Returns the `coor_out` dict of the reference
-    (or the scaled correlation [B,HW,HW] when return_corr, :305-306)."""
+    (or the scaled correlation [B,HW,HW] when return_corr, :305-306).
+
+    `exemplar`: the ops.PreparedKeys of a prepared exemplar (inference.PreparedExemplar) IN PLACE of phi_raw, ref_img and
+    ref_seg_map (all three None): the key side and the row pass's value tensor are the record's.  Forward only (no autograd
+    graph is built)."""
     B, C, fh, fw = theta_raw.shape
-    H, W = ref_img.shape[2], ref_img.shape[3]
     down, mk = cfg.down, cfg.match_kernel
+    attn = None
+    if exemplar is not None:
+        if phi_raw is not None or ref_img is not None or ref_seg_map is not None:
+            raise ValueError("correspondence_hot_path: a prepared exemplar stands in place of phi_raw, ref_img and ref_seg_map")
+        if torch.is_grad_enabled():      # (which configurations may use a record at all: NoVGGCorrespondence._check_exemplar)
+            raise ValueError("correspondence_hot_path: a prepared exemplar is forward-only (call under torch.no_grad())")
+        H, W = exemplar.image_size
+        attn = _attention_with_exemplar(theta_raw, exemplar, cfg, 1.0 / temperature, WTA_scale_weight, return_corr)
+        if attn is None:
+            theta_raw = theta_raw.raw() if isinstance(theta_raw, ops.LazyProj1x1) else theta_raw
+            phi_raw = exemplar.phi_raw(B)
+    else:
+        H, W = ref_img.shape[2], ref_img.shape[3]
     out = {}
 
     inv_t = 1.0 / temperature
@@ -269,8 +405,8 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
     # fused match_kernel-1 / PONO_C path K23 then goes from the features straight to the correlation kernels' operand planes
     # (projection + centring + normalisation in one launch for both tensors: the fp32 projections never exist); every other
     # back end asks for the projections (K0) and continues as before.
-    lazy = isinstance(theta_raw, ops.LazyProj1x1) and isinstance(phi_raw, ops.LazyProj1x1)
-    if lazy != (isinstance(theta_raw, ops.LazyProj1x1) or isinstance(phi_raw, ops.LazyProj1x1)):
+    lazy = attn is None and isinstance(theta_raw, ops.LazyProj1x1) and isinstance(phi_raw, ops.LazyProj1x1)
+    if attn is None and lazy != (isinstance(theta_raw, ops.LazyProj1x1) or isinstance(phi_raw, ops.LazyProj1x1)):
         raise TypeError("correspondence_hot_path: theta and phi must both be tensors or both be ops.LazyProj1x1")
     k23 = boxed_lazy = False
     if lazy:
@@ -282,7 +418,9 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
                       and ops.PROJ_BWD_FUSED and ops.box3_fused_ok(B, C, fh, fw))
         if not (k23 or boxed_lazy):
             theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
-    if k23:
+    if attn is not None:
+        pass      # (a prepared exemplar's: made above)
+    elif k23:
         th_l, ph_l = (theta_raw.detach(), phi_raw.detach()) if detach_flag else (theta_raw, phi_raw)   # :292-293 `f = f.detach()`
         planes = ops.OperandPlanes()
         qn, kn = ops.proj_center_l2norm_planes_pair(th_l, ph_l, 1, planes, want_chan=keep)
@@ -325,26 +463,15 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
 
     # ---- R1: exemplar colours (+ direct mask) through the row softmax  (:309-336) ----------------
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
-    # K30: the head and the value kernels on every flag set (ops.WARP_HEAD_MODES; CPU / non-fp32 tensors keep the framework route)
-    modes = ops.WARP_HEAD_MODES and _hip_fp32(theta_raw) and _hip_fp32(ref_img)
-    fused_values = ((modes or (direct_mask and not cfg.warp_patch)) and _hip_fp32(ref_img) and not ref_img.requires_grad
-                    and (not direct_mask or (_hip_fp32(ref_seg_map) and not ref_seg_map.requires_grad))
-                    and H % down == 0 and W % down == 0)
-    if fused_values:
-        # pooled image (or its patches, --warp_patch) + sampled mask in one kernel (K14)
-        v1 = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down, patch=cfg.warp_patch))
-        n_ref = ref_img.shape[1] * (down * down if cfg.warp_patch else 1)
+    if exemplar is not None:
+        modes = ops.WARP_HEAD_MODES and _hip_fp32(theta_raw)
+        v1 = exemplar.values(down, cfg.warp_patch, direct_mask)      # an ops.PreparedValues: _Attention.rows knows it
+        n_ref = v1.n_ref
     else:
-        if cfg.warp_patch:
-            ref = F.unfold(ref_img, down, stride=down)                    # [B, 3*down^2, HW]
-        else:
-            ref = _flat(F.avg_pool2d(ref_img, down))                      # [B, 3, HW]
-        n_ref = ref.shape[1]
-        v_r1 = [ref]
-        if direct_mask:
-            ref_seg = F.interpolate(ref_seg_map, scale_factor=1 / down, mode="nearest")
-            v_r1.append(_flat(ref_seg))
-        v1 = torch.cat(v_r1, dim=1) if len(v_r1) > 1 else ref
+        # K30: the head and the value kernels on every flag set (ops.WARP_HEAD_MODES; CPU / non-fp32 tensors keep the framework route)
+        modes = ops.WARP_HEAD_MODES and _hip_fp32(theta_raw) and _hip_fp32(ref_img)
+        v1, n_ref = _row_values(ref_img, ref_seg_map, down, cfg.warp_patch, direct_mask,
+                                _fused_values_ok(ref_img, ref_seg_map, down, cfg.warp_patch, direct_mask, modes))
     o_r1 = attn.rows(v1)
     want_cycle = cfg.warp_cycle_w > 0
     show_bi = (not cfg.isTrain) and cfg.show_corr

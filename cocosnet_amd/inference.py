@@ -22,6 +22,9 @@ again (`FrozenReport.repreparations`), a stale record is never read.  In every o
     from cocosnet_amd import inference
     report = inference.freeze(model.net)        # or any nn.Module; inference.unfreeze(...) removes the records
     inference.FROZEN = False                    # A/B switch (env COCOS_FROZEN=0): ignore attached records
+
+`prepare_exemplar(net, ref_img, ref_seg_map)` does the same for everything a `NoVGGCorrespondence` derives from the EXEMPLAR (one
+style image against many label maps): see PreparedExemplar.
 """
 from __future__ import annotations
 
@@ -31,8 +34,9 @@ import os
 import torch
 import torch.nn as nn
 
-#: False (env COCOS_FROZEN=0): attached records are ignored — every call takes the unfrozen route (A/B runs).  This only bypasses
-#: records that freeze() attached explicitly; nothing is frozen by default.  Module attribute, read at call time.
+#: False (env COCOS_FROZEN=0): attached records are ignored — every call takes the unfrozen route (A/B runs) — and so is a prepared
+#: exemplar handed to forward(exemplar=...).  This only bypasses records that freeze() attached / the caller passed explicitly;
+#: nothing is frozen by default.  Module attribute, read at call time.
 FROZEN = os.environ.get("COCOS_FROZEN", "1") != "0"
 
 _ATTR = "_cocos_frozen"
@@ -280,6 +284,123 @@ def unfreeze(module) -> int:
                 if type(hook) is producers._SpectralNormRecord:
                     hook.__class__ = producers._sn_mod.SpectralNorm
     return n
+
+
+# ---- prepared exemplars ------------------------------------------------------------------------------------------------------------
+class PreparedExemplar:
+    """Everything `NoVGGCorrespondence.forward` derives from the EXEMPLAR (ref_img, ref_seg_map) alone, made once and reused for any
+    number of content inputs — see prepare_exemplar().  Holds the exemplar stream's features behind `self.layer` and, made the first
+    time a route asks for them (as PreparedWeight._layouts), the products of the route in force (an ops.PreparedKeys):
+
+      fused match_kernel 1 (split flavour)   position-major hi / lo key planes of kn and its row norms — the fp32 kn never exists
+      fused match_kernel 3 (_BoxedCorr)      phi_raw's position-major hi / lo planes, their scale cell and its (nu, b) statistics
+      every other back end                   phi_raw as fp32 (generic, WTA, return_corr, COCOS_PRECISION=fp32)
+      always                                 the row pass's value tensor (pooled image or its patches + the sampled direct mask, i.e.
+                                             the resized ref_seg of warp_mask / show_warpmask) with its max|v| cell and, on the split
+                                             flavour, its hi / lo planes and the lo-plane block mask
+
+    It keeps references to ref_img and ref_seg_map and watches (data_ptr, _version) of both and of every parameter and buffer of
+    adaptive_model_img, layer and phi: a record found stale at use time prepares again (`repreparations` counts it) — a stale record
+    is never read.  `batch` (Be) is the exemplar batch: a forward with B inputs takes Be == B or Be == 1 (one exemplar for all)."""
+
+    def __init__(self, net, ref_img, ref_seg_map):
+        self.net, self.ref_img, self.ref_seg_map = net, ref_img, ref_seg_map
+        self.repreparations = 0
+        self._sig = None
+        self.feat = None            # the exemplar stream behind self.layer [Be, cl, fh, fw]
+        self.keys = None            # ops.PreparedKeys on the GPU (fp32); None on the CPU
+        self._phi_raw = None        # CPU / fp64: the projection itself
+
+    batch = property(lambda self: self.ref_img.shape[0])
+
+    def sources(self):
+        net = self.net
+        out = [self.ref_img, self.ref_seg_map]
+        for m in (net.adaptive_model_img, net.layer, net.phi):
+            out += list(m.parameters()) + list(m.buffers())
+        return out
+
+    def signature(self):
+        return tuple((t.data_ptr(), t._version) for t in self.sources())
+
+    def stale(self) -> bool:
+        return self._sig is not None and self._sig != self.signature()
+
+    def ensure(self):
+        """prepare now if never prepared; prepare AGAIN (and count it) if a watched tensor changed or moved"""
+        if self.net.training:
+            raise ValueError("PreparedExemplar: the network must be in eval() mode")
+        sig = self.signature()
+        if self._sig == sig:
+            return self
+        if self._sig is not None:
+            self.repreparations += 1
+        self.feat = self.keys = self._phi_raw = None
+        self._prepare()
+        self._sig = sig
+        return self
+
+    def phi_raw(self):
+        """the exemplar's fp32 projection [Be,256,fh,fw]"""
+        return self._phi_raw if self.keys is None else self.keys.phi_raw()
+
+    # ---- the exemplar stream (correspondence.py project(), exemplar side) -----------------------------------------------------------
+    def _prepare(self):
+        from . import ops
+        net = self.net
+        with torch.no_grad():
+            ref = self.feat = net.exemplar_stream(self.ref_img, self.ref_seg_map)
+            if not (ref.is_cuda and ref.dtype == torch.float32):
+                self._phi_raw = net.phi(ref)      # CPU / fp64: producer parity tests only (the hot path needs a GPU and fp32)
+                return
+        rec = self
+        ref_img, ref_seg_map = self.ref_img, self.ref_seg_map
+        lazy = lambda: ops.LazyProj1x1(ref, net.phi.weight.detach(), None if net.phi.bias is None else net.phi.bias.detach(),
+                                       usable_record(net.phi))
+
+        def make_phi_raw():
+            return lazy().raw()
+
+        def make_split():      # K23 with one problem where it takes the shape, else K0 + K1's planes flavour
+            p = lazy()
+            if ops.proj_norm_fused_ok(p):
+                return ops.proj_center_l2norm_planes_one(p, 1)
+            x = rec.keys.phi_raw()
+            return ops.center_l2norm_planes_fwd(x.reshape(x.shape[0], x.shape[1], -1), 1)
+
+        def make_box():
+            x = rec.keys.phi_raw()
+            B, C, h, w = x.shape
+            nu, b = ops.unfold3_stats(x, float(C * 9))
+            xf = x.reshape(B, C, h * w)
+            kh, kl, ks = ops.split_f16(xf, True, amax=ops.absmax(xf))
+            return kh, kl, ks, nu, b
+
+        def make_values(down, patch, direct_mask):
+            from .hot_path import exemplar_values
+            return exemplar_values(ref_img, ref_seg_map, down, patch, direct_mask)
+
+        B, _, fh, fw = ref.shape
+        self.keys = ops.PreparedKeys(B, (B, net.phi.weight.shape[0], fh, fw), ref_img.shape[2:], make_phi_raw, make_split, make_box,
+                                     make_values)
+
+
+def prepare_exemplar(net, ref_img, ref_seg_map) -> PreparedExemplar:
+    """Run the exemplar stream of a `NoVGGCorrespondence` once: `net.forward(None, real_img, seg_map, None, exemplar=record)` then
+    runs the content stream alone.  Requires `net.eval()` (ValueError otherwise) and runs under torch.no_grad().
+
+    The stream includes the `noise_for_mask` draw of the maskmix concat: that noise is FIXED at preparation time — every forward with
+    the record sees the same draw (the ordinary route draws per call); a record that prepares again (see PreparedExemplar) draws again.
+    `COCOS_FROZEN=0` / `inference.FROZEN = False` makes forward ignore the record and run the ordinary route from the record's stored
+    ref_img / ref_seg_map."""
+    from . import correspondence
+    if not isinstance(net, correspondence.NoVGGCorrespondence):
+        raise TypeError(f"prepare_exemplar: expected a NoVGGCorrespondence, got {type(net).__name__}")
+    if net.training:
+        raise ValueError("prepare_exemplar: the network must be in eval() mode")
+    if ref_img is None or ref_seg_map is None or ref_img.shape[0] != ref_seg_map.shape[0]:
+        raise ValueError("prepare_exemplar: ref_img and ref_seg_map of one batch size are required")
+    return PreparedExemplar(net, ref_img, ref_seg_map).ensure()
 
 
 # ---- the reference's facade -------------------------------------------------------------------------------------------------------

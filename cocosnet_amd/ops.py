@@ -238,6 +238,19 @@ def center_l2norm_planes(x: torch.Tensor, center_over_channels, planes: OperandP
     return _CenterL2NormPlanes.apply(x, int(center_over_channels), eps, planes, bool(want_chan))
 
 
+def center_l2norm_planes_fwd(x: torch.Tensor, center_over_channels, eps: float = NORM_EPS):
+    """K1's planes flavour, forward only and without an autograd node (inference with a prepared exemplar): x [B,256,N] ->
+    (pos_hi, pos_lo [B,N,256] of SPLIT_OPERAND_SCALE * y, norm [B,N]).  Only on the split path (corr_split_ok)."""
+    x = _chk(x.detach(), "center_l2norm_planes: x")
+    B, K, N = x.shape
+    norm = torch.empty((B, N), device=x.device, dtype=torch.float32)
+    ph = torch.empty((B, N, K), device=x.device, dtype=torch.float16)
+    pl = torch.empty((B, N, K), device=x.device, dtype=torch.float16)
+    _call("center_l2norm_fwd", "cocos_center_l2norm_fwd_planes", x.data_ptr(), norm.data_ptr(), ph.data_ptr(), pl.data_ptr(), None, None,
+          B, K, N, int(center_over_channels), float(eps), SPLIT_OPERAND_SCALE, _stream())
+    return ph, pl, norm
+
+
 def corr_split_ok(B, K, Nq, Nk, Cv, keep: bool) -> bool:
     """True when corr_softmax_warp takes the split-precision kernels for this shape (forward and, when `keep`, backward):
     the condition under which qn / kn may exist as operand planes only."""
@@ -758,6 +771,109 @@ def corr_softmax_warp(qn, kn, v, inv_temperature: float, planes: OperandPlanes |
     if Cv <= limit:
         return run(v)
     return torch.cat([run(v[:, c0:c0 + limit]) for c0 in range(0, Cv, limit)], dim=1)
+
+
+class PreparedValues:
+    """The value tensor of the row pass of a prepared exemplar (inference.PreparedExemplar): v [Be,Cv,N] fp32 with its max|v| cell
+    and, made on first use by the split flavour, its channel-major hi / lo planes, their scale cell and the lo-plane block mask.
+    `n_ref`: how many leading channels are image (the rest is the direct mask)."""
+
+    def __init__(self, v: torch.Tensor, n_ref: int):
+        self.v, self.n_ref = v, int(n_ref)
+        self.amax = None            # max|v| cell: taken when the split flavour first asks for the planes
+        self._split = None
+        self._expanded = {}         # B -> the copy for B query batches (kept, as PreparedKeys keeps its copies)
+
+    def split(self):
+        """(vh, vl, scale cell, lo mask | None): what corr_softmax_warp's run() makes of V per launch, made once"""
+        if self._split is None:
+            self.amax = absmax(self.v)
+            self._split = split_f16_chan_mask(self.v, self.amax, VALUE_LO_SKIP and self.v.shape[1] > 32)
+        return self._split
+
+    def expanded(self, B: int) -> torch.Tensor:
+        """v for B query batches: itself, or ONE exemplar's copied B times, once per record (the routes without a native broadcast:
+        their kernels measure and split V per call, as for any other value tensor)"""
+        Be = self.v.shape[0]
+        if Be == B:
+            return self.v
+        if Be != 1:
+            raise ValueError(f"prepared exemplar of batch {Be} used with {B} inputs (expected {B} or 1)")
+        if B not in self._expanded:
+            self._expanded[B] = self.v.expand(B, -1, -1).contiguous()
+        return self._expanded[B]
+
+
+class PreparedKeys:
+    """The key side and the value side of a correlation that outlive ONE forward call — the halves of what ops.OperandPlanes (a
+    per-call object) holds that depend on the exemplar alone.  Owned by an inference.PreparedExemplar, which fills it through the
+    `make_*` callables it passes in; every product is made the first time a route asks for it and kept until the record finds its
+    sources changed (it then builds a new PreparedKeys: nothing here is ever updated in place).  Inference only: nothing in it
+    carries an autograd graph.  `Be` is the exemplar batch: the number of query batches B, or 1 = all of them share one exemplar."""
+
+    def __init__(self, Be: int, shape, image_size, make_phi_raw, make_split, make_box, make_values):
+        self.Be = int(Be)
+        self.shape = torch.Size(shape)            # of phi_raw: [Be, 256, fh, fw]
+        self.image_size = tuple(image_size)       # (H, W) of ref_img
+        self._make = dict(phi_raw=make_phi_raw, split=make_split, box=make_box, values=make_values)
+        self._got = {}
+
+    def _get(self, key, fn):
+        if key not in self._got:
+            with torch.no_grad():
+                self._got[key] = fn()
+        return self._got[key]
+
+    def check(self, B: int):
+        if self.Be not in (B, 1):
+            raise ValueError(f"prepared exemplar of batch {self.Be} used with {B} inputs (expected {B} or 1)")
+
+    def _bcast(self, key, t, B):
+        """t [Be,...] for B query batches: expand().contiguous() once per call site and record state (kept: the next call reuses it)"""
+        if t is None or t.shape[0] == B:
+            return t
+        return self._get((key, "x", B), lambda: t.expand(B, *t.shape[1:]).contiguous())
+
+    def phi_raw(self, B=None):
+        """the fp32 projection [Be,256,fh,fw] (generic back end, WTA, return_corr, the fp32 flavour); [B,...] when B is given"""
+        t = self._get("phi_raw", self._make["phi_raw"])
+        return t if B is None else self._bcast("phi_raw", t, B)
+
+    def split_planes(self, B=None):
+        """(kh, kl, norm): position-major planes [Be,N,256] of SPLIT_OPERAND_SCALE * kn and the row norms (fused match_kernel 1)"""
+        got = self._get("split", self._make["split"])
+        return got if B is None else tuple(self._bcast(("split", i), t, B) for i, t in enumerate(got))
+
+    def box_planes(self, B=None):
+        """(kh, kl, scale cell, nu, b): phi_raw's position-major planes and its K12 statistics (fused match_kernel 3)"""
+        got = self._get("box", self._make["box"])
+        if B is None:
+            return got
+        return tuple(t if i == 2 else self._bcast(("box", i), t, B) for i, t in enumerate(got))
+
+    def values(self, down: int, patch: bool, direct_mask: bool) -> PreparedValues:
+        key = ("values", int(down), bool(patch), bool(direct_mask))
+        return self._get(key, lambda: self._make["values"](int(down), bool(patch), bool(direct_mask)))
+
+
+def corr_softmax_warp_shared(qh, ql, keys: PreparedKeys, values: PreparedValues, inv_temperature: float):
+    """corr_softmax_warp(qn, kn, v, ...) of the split flavour, forward only, with the key planes and V of a prepared exemplar:
+    qh, ql [B,Nq,256] (this call's query planes); keys / values of batch B or 1 — with 1 every query batch reads the ONE key /
+    value set (batch stride 0 in cocos_corr_softmax_warp_fwd_f16x3_shared: no copies).  Cv <= MAX_FUSED_SPLIT_CV."""
+    B, Nq, K = qh.shape
+    kh, kl, _ = keys.split_planes()
+    vh, vl, v_scale, v_lomask = values.split()
+    Be, Nk = kh.shape[0], kh.shape[1]
+    Cv = vh.shape[1]
+    if Be not in (B, 1) or vh.shape[0] != Be or vh.shape[2] != Nk or kh.shape[2] != K:
+        raise ValueError(f"corr_softmax_warp_shared: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)} v{tuple(vh.shape)}")
+    dense = Be == B
+    out = torch.empty((B, Cv, Nq), device=qh.device, dtype=torch.float32)
+    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("corr_softmax_warp_fwd", "cocos_corr_softmax_warp_fwd_f16x3_shared", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(),
+          kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(), lse.data_ptr(), None, v_scale.data_ptr(), _ptr(v_lomask),
+          B, K, Nq, Nk, Cv, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if dense else 0, Cv * Nk if dense else 0, _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------
@@ -1688,6 +1804,39 @@ def proj_center_l2norm_planes_pair(theta: LazyProj1x1, phi: LazyProj1x1, center_
     corr_softmax_warp(..., planes=planes).  Only for proj_norm_fused_ok() shapes on the split path (corr_split_ok)."""
     return _ProjCenterL2NormPlanesPair.apply(theta.x, theta.weight, theta.bias, phi.x, phi.weight, phi.bias,
                                              int(center_over_channels), eps, planes, bool(want_chan), _prepared_pair(theta, phi))
+
+
+def proj_center_l2norm_planes_one(p: LazyProj1x1, center_over_channels, eps: float = NORM_EPS):
+    """K23 for ONE lazy projection, forward only (inference with a prepared exemplar: theta alone per call, phi alone when the
+    record is made): (pos_hi, pos_lo [B,N,256], norm [B,N]).  The same kernel as the pair's, launched with one problem
+    (cocos_proj_center_l2norm_planes_f16x3, nprob = 1).  Only for proj_norm_fused_ok() shapes; no autograd node."""
+    lib = _lib.load()
+    with torch.no_grad():
+        x = _chk(p.x, "proj_center_l2norm_planes: x")
+        w2d = _chk(p.weight.reshape(p.weight.shape[0], -1), "proj_center_l2norm_planes: weight")
+        bias = None if p.bias is None else _chk(p.bias, "proj_center_l2norm_planes: bias")
+        B, Cin, h, w = x.shape
+        N = h * w
+        if w2d.shape != (FUSED_K, Cin):
+            raise ValueError(f"proj_center_l2norm_planes_one: weight {tuple(w2d.shape)} does not match x {tuple(x.shape)}")
+        dev = x.device
+        xa = absmax(x)      # (its own pass: the version-keyed max|x| table is the training routes')
+        if p.prepared is not None:      # frozen record (inference.py): its cell and its fragment-ordered planes
+            wfrag, _, wsc = p.prepared.planes("frag")
+        else:
+            wa = absmax(w2d)
+            wfrag = torch.empty(lib.cocos_proj_weight_frag_bytes(Cin), device=dev, dtype=torch.uint8)
+            wsc = torch.empty(1, device=dev, dtype=torch.float32)
+            _call("split_f16", "cocos_proj_weight_prep_pair", 1, w2d.data_ptr(), wa.data_ptr(), wfrag.data_ptr(), wsc.data_ptr(),
+                  None, None, None, None, None, None, None, None, None, None, FUSED_K, Cin, _stream())
+        norm = torch.empty((B, N), device=dev, dtype=torch.float32)
+        ph = torch.empty((B, N, FUSED_K), device=dev, dtype=torch.float16)
+        pl = torch.empty((B, N, FUSED_K), device=dev, dtype=torch.float16)
+        _call("proj_center_l2norm_fwd", "cocos_proj_center_l2norm_planes_f16x3", 1, x.data_ptr(), wfrag.data_ptr(), wsc.data_ptr(),
+              _ptr(bias), xa.data_ptr(), norm.data_ptr(), ph.data_ptr(), pl.data_ptr(), None, None,
+              None, None, None, None, None, None, None, None, None, None, B, Cin, N, int(center_over_channels), float(eps),
+              SPLIT_OPERAND_SCALE, _stream())
+    return ph, pl, norm
 
 
 # ------------------------------------------------------------------------------------------

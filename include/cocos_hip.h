@@ -154,6 +154,20 @@ int cocos_corr_softmax_warp_fwd_f16x3_ex(const void* qh, const void* ql, const v
                                          block's C/8 channels in 256-channel planes): k_active <= 32 / <= 64 / <= 128 run instantiations without
                                          the QK steps, fragment reads and key fetches of the padding */,
                                          cocos_stream_t stream);
+/* The inference forward with key and value planes that several query batches may SHARE (a prepared exemplar, inference.py:
+ * one style image against B label maps).  Same kernels, same arithmetic in the same order as cocos_corr_softmax_warp_fwd_f16x3
+ * on the unit-norm flavour (no q_scale_dev / k_scale_dev, no k_active); the only difference is where sample b's key / value planes
+ * start: kh, kl at b * k_batch_stride halfs, vh, vl at b * v_batch_stride halfs.  (k_batch_stride, v_batch_stride) is (0, 0) — kh,kl
+ * [Nk,256] and vh,vl [Cv,Nk] hold ONE set that all B samples read — or the dense (Nk * 256, Cv * Nk); anything else is
+ * COCOS_ERR_INVALID.  *v_scale_dev (required) and *v_lo_mask_dev (nullable) describe the value planes as a whole, as above.
+ * saved_logits must be NULL (COCOS_ERR_INVALID otherwise: this entry point has no backward).  Supported shapes as above
+ * (K != 256, Cv > 159, Nk % 4 != 0: COCOS_ERR_UNSUPPORTED).  Nothing is launched when an error is returned. */
+int cocos_corr_softmax_warp_fwd_f16x3_shared(const void* qh, const void* ql, const void* kh, const void* kl,
+                                             const void* vh, const void* vl, float* out, float* lse,
+                                             void* saved_logits /* must be NULL */, const float* v_scale_dev,
+                                             const unsigned* v_lo_mask_dev /* nullable */, int B, int K, int Nq, int Nk, int Cv,
+                                             float inv_temperature, float operand_scale, long long k_batch_stride,
+                                             long long v_batch_stride, cocos_stream_t stream);
 /* bit (c >> 5) of *mask_inout_dev |= (channel c of the channel-major f16 plane [B,C,N] has a non-zero element); the
  * cell must hold 0 (or an earlier partial mask) on entry; C <= 1024.  Run on the LO plane of V: value channels that
  * are exact in f16 (one-hot labels, masks) have an all-zero lo plane, and when every 32-channel block but the first
