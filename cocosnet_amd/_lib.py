@@ -304,6 +304,12 @@ _SIGNATURES = {
     "cocos_conv2d_wgrad_slices": (ctypes.c_int, [ctypes.c_int] * 10),
     "cocos_conv2d_wgrad_f16x3": (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 10 + [_stream_t]),
     "cocos_conv2d_wgrad_bf16": (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 10 + [_stream_t]),
+    # K35: label_map is int64, index int32 device memory
+    "cocos_labels_one_hot": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [_stream_t]),
+    "cocos_label_conv_table": (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [_stream_t]),
+    "cocos_label_conv3x3_fwd": (ctypes.c_int, [ctypes.c_void_p] + [_c_float_p] * 4 + [ctypes.c_int] * 8 + [_stream_t]),
+    "cocos_label_conv3x3_bwd_workspace_floats": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "cocos_label_conv3x3_bwd": (ctypes.c_int, [ctypes.c_void_p] + [_c_float_p] * 5 + [ctypes.c_int] * 7 + [_stream_t]),
     "cocos_debug_mfma_probe": (ctypes.c_int, [_c_float_p, _stream_t]),
 }
 

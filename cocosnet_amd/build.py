@@ -49,6 +49,7 @@ HIP_SOURCES = [
     "pono_spade.hip",
     "instnorm_prelu.hip",
     "instnorm_split.hip",
+    "label_conv.hip",
     "upsample_nearest.hip",
     "warp_values.hip",
     "warp_head.hip",

@@ -146,6 +146,15 @@ class PreparedWeight:
             self._layouts[key] = got
         return got
 
+    def label_table(self):
+        """the tap-major table of K35 (ops.label_conv_table) of the effective weight, made on first request and kept like the planes"""
+        key = ("label_taps", 0)
+        got = self._layouts.get(key)
+        if got is None:
+            from . import ops
+            got = self._layouts[key] = ops.label_conv_table(self.weight)
+        return got
+
 
 def _effective_weight(rec):
     """(weight, max|w| cell or None) as the unfrozen eval() route forms them: the parameter itself, or the spectral hook's W / sigma

@@ -3200,6 +3200,110 @@ def instnorm_prelu_split(x, residual, weight, eps: float = INSTNORM_EPS):
 
 
 # ------------------------------------------------------------------------------------------
+# K35  3x3 convolution of a one-hot label map as table look-ups   (label_conv.hip; pix2pix_model.py:177-187 builds the map)
+# ------------------------------------------------------------------------------------------
+def labels_one_hot(label_map: torch.Tensor, nc: int):
+    """(one-hot fp32 [B,nc,H,W], index int32 [B,H,W]) of an integer label map [B,1,H,W] on the GPU: `zeros.scatter_(1, label_map, 1.0)`
+    with every element written by one kernel, and the compact index map the label route reads.  A label outside [0, nc) gives an
+    all-zero column and index -1 (scatter_ raises there)."""
+    if not label_map.is_cuda:
+        raise _lib.CocosHipError("labels_one_hot: expected a CUDA/HIP tensor; cocosnet_amd.labels.one_hot handles host tensors")
+    if label_map.dim() != 4 or label_map.shape[1] != 1 or label_map.dtype != torch.int64:
+        raise ValueError(f"labels_one_hot: int64 [B,1,H,W] expected, got {label_map.dtype} {tuple(label_map.shape)}")
+    lab = label_map.contiguous()
+    B, _, H, W = lab.shape
+    seg = torch.empty((B, int(nc), H, W), device=lab.device, dtype=torch.float32)
+    index = torch.empty((B, H, W), device=lab.device, dtype=torch.int32)
+    _call("labels_one_hot", "cocos_labels_one_hot", lab.data_ptr(), seg.data_ptr(), index.data_ptr(), B, int(nc), H, W, _stream())
+    return seg, index
+
+
+def label_conv_ok(weight, index, sample: int = 1, reflect: int = 0, stride=1, padding=1, dilation=1, nc=None) -> bool:
+    """The ONE predicate of the label route: weight fp32 [Cout, nc, 3, 3] on the GPU with Cout % 16 == 0 and 1 <= nc <= 32767;
+    stride 1, dilation 1; padding 1 (zeros) or ReflectionPad2d(1) in front of padding 0 with an output grid of 2x2 or more; the
+    index map [B, Hs, Ws] int32 on the same device with Hs % sample == 0 and Ws % sample == 0.  Anything else: the dense route."""
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if not (torch.is_tensor(weight) and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4):
+        return False
+    Cout, Cin, KH, KW = weight.shape
+    if (KH, KW) != (3, 3) or Cout % 16 != 0 or not 1 <= Cin <= 32767 or (nc is not None and int(nc) != Cin):
+        return False
+    if pair(stride) != (1, 1) or pair(dilation) != (1, 1) or isinstance(padding, str):
+        return False
+    if not (torch.is_tensor(index) and index.is_cuda and index.device == weight.device and index.dtype == torch.int32 and index.dim() == 3):
+        return False
+    sample, reflect = int(sample), int(reflect)
+    Hs, Ws = index.shape[1:]
+    if sample < 1 or Hs < 1 or Ws < 1 or Hs % sample or Ws % sample:
+        return False
+    if reflect == 0:
+        return pair(padding) == (1, 1)
+    return reflect == 1 and pair(padding) == (0, 0) and Hs // sample >= 2 and Ws // sample >= 2
+
+
+def label_conv_table(weight: torch.Tensor) -> torch.Tensor:
+    """W [Cout, nc, 3, 3] -> the tap-major table Wt [9, nc, Cout] of K35"""
+    w = _chk(weight, "label_conv_table: weight")
+    Cout, nc = w.shape[:2]
+    table = torch.empty((9, nc, Cout), device=w.device, dtype=torch.float32)
+    _call("label_conv_table", "cocos_label_conv_table", w.data_ptr(), table.data_ptr(), Cout, nc, _stream())
+    return table
+
+
+class _LabelConv3x3(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, index, weight, bias, nc: int, sample: int, reflect: int, relu: bool, prepared=None):
+        weight = _chk(weight, "label_conv3x3: weight")
+        bb = None if bias is None else _chk(bias, "label_conv3x3: bias")
+        if not label_conv_ok(weight, index, sample, reflect, 1, 0 if reflect else 1, 1, nc):
+            raise ValueError(f"label_conv3x3: weight {tuple(weight.shape)} / index {tuple(index.shape)} {index.dtype} / nc {nc} / sample "
+                             f"{sample} / reflect {reflect} is outside ops.label_conv_ok")
+        index = index.contiguous()
+        Cout = weight.shape[0]
+        B, Hs, Ws = index.shape
+        table = prepared.label_table() if prepared is not None else label_conv_table(weight)
+        y = torch.empty((B, Cout, Hs // sample, Ws // sample), device=weight.device, dtype=torch.float32)
+        # max|y| as a by-product, as the other producer kernels leave it: a convolution that reads y directly finds the cell
+        cell = _zero_cell(y.device) if CONV_PRECISION == "f16x3" else None
+        _call("label_conv3x3_fwd", "cocos_label_conv3x3_fwd", index.data_ptr(), table.data_ptr(), _ptr(bb), y.data_ptr(), _ptr(cell),
+              B, Hs, Ws, int(sample), int(reflect), int(bool(relu)), int(nc), Cout, _stream())
+        _glue_remember(y, cell)           # (weak: the entry must not keep the activation alive)
+        ctx.save_for_backward(index, *((y,) if relu else ()))
+        ctx.cfg = (int(nc), int(sample), int(reflect), bool(relu), tuple(weight.shape), bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        index, *rest = ctx.saved_tensors
+        nc, sample, reflect, relu, wshape, has_bias = ctx.cfg
+        ysaved = rest[0] if relu else None
+        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and has_bias
+        dw = db = None
+        if need_w or need_b:
+            dy = _chk(dy, "label_conv3x3: dy")
+            B, Hs, Ws = index.shape
+            Cout = wshape[0]
+            dw = torch.empty(wshape, device=dy.device, dtype=torch.float32)
+            db = torch.empty(Cout, device=dy.device, dtype=torch.float32) if need_b else None
+            n = _lib.load().cocos_label_conv3x3_bwd_workspace_floats(B, Hs // sample, Ws // sample, nc, Cout)
+            ws = torch.empty(n, device=dy.device, dtype=torch.float32)      # held by this name until the call below has launched
+            _call("label_conv3x3_bwd", "cocos_label_conv3x3_bwd", index.data_ptr(), dy.data_ptr(), _ptr(ysaved), dw.data_ptr(), _ptr(db),
+                  ws.data_ptr(), B, Hs, Ws, sample, reflect, nc, Cout, _stream())
+            if not need_w:
+                dw = None
+        return None, dw, db, None, None, None, None, None
+
+
+def label_conv3x3(index, weight, bias, nc: int, sample: int = 1, reflect: int = 0, relu: bool = False, prepared=None):
+    """conv2d(one_hot(index), weight, bias) for a 3x3 kernel as nine table look-ups per output pixel (K35):
+    `index` int32 [B, Hs, Ws] (-1: no class) is read at every `sample`-th pixel of both axes — the nearest resize to
+    (Hs / sample) x (Ws / sample) — with zero padding 1 (`reflect` = 0) or ReflectionPad2d(1) (`reflect` = 1), optionally followed by
+    ReLU.  Exact fp32 sums of at most ten numbers.  Gradients reach weight and bias only (bit-reproducible: fixed order, no atomics).
+    Saves the index map and, with relu, the output.  `prepared`: the layer's frozen record (its tap table is made once)."""
+    return _LabelConv3x3.apply(index, weight, bias, int(nc), int(sample), int(reflect), bool(relu), prepared)
+
+
+# ------------------------------------------------------------------------------------------
 # K21  torch.nn.utils.spectral_norm's weight: power iteration + W / sigma, and its backward   (spectral_norm.hip)
 # ------------------------------------------------------------------------------------------
 class _SpectralWeight(torch.autograd.Function):

@@ -42,12 +42,38 @@ class Conv2d(nn.Conv2d):
     `.weight`).  Anything the kernels do not cover (groups, non-zero padding modes, rectangular stride / padding /
     dilation, other dtypes, CPU) takes the framework path."""
 
-    def forward(self, input, reflect: int = 0):
+    def forward(self, input, reflect: int = 0, labels=None, sample: int = 1, relu: bool = False):
         """`reflect` = r: this call is conv(ReflectionPad2d(r)(input)) — passed explicitly by reflect_conv() THROUGH the
-        module call (forward pre-hooks such as spectral norm see only the positional input and still run)."""
-        return self._conv_forward(input, self.weight, self.bias, int(reflect))
+        module call (forward pre-hooks such as spectral norm see only the positional input and still run).
+        `labels`: the label record of a one-hot `input` (labels.record_of) — the layer then reads the record's index map (K35,
+        ops.label_conv3x3) and leaves `input` untouched.  `sample` = s: the convolution is of `input` nearest-resized to 1/s of its
+        grid; `relu`: followed by ReLU.  Both are part of the label call; on the dense route they are applied here, around it."""
+        return self._conv_forward(input, self.weight, self.bias, int(reflect), labels, int(sample), bool(relu))
 
-    def _conv_forward(self, input, weight, bias, reflect: int = 0):
+    def _frozen_record(self, weight):
+        """frozen-weight inference (inference.py): a record attached by freeze(), validated, when this call may use it
+        — only for the tensor the record stands for: the module's own weight, or the W / sigma its spectral hook just handed out
+        (validated there: once per call)"""
+        rec = self.__dict__.get("_cocos_frozen")
+        if rec is not None:
+            if rec.hook is not None:
+                handed, rec.handed = rec.handed, False
+                rec = rec if handed and weight is rec.weight else None
+            else:
+                rec = rec.use() if weight is self.weight else None
+        return rec
+
+    def _conv_forward(self, input, weight, bias, reflect: int = 0, labels=None, sample: int = 1, relu: bool = False):
+        if labels is not None or sample != 1 or relu:
+            from . import labels as _labels, ops
+            if (labels is not None and _labels.enabled() and conv_backend() in _HIP_BACKENDS and self.groups == 1
+                    and self.padding_mode == "zeros" and (bias is None or (bias.is_cuda and bias.dtype == torch.float32))
+                    and ops.label_conv_ok(weight, labels.index, sample, reflect, self.stride, self.padding, self.dilation, labels.nc)):
+                return ops.label_conv3x3(labels.index, weight, bias, labels.nc, sample, reflect, relu, self._frozen_record(weight))
+            if sample != 1:                 # the dense route: what the caller left to this call, around the convolution
+                input = nn.functional.interpolate(input, size=(input.shape[2] // sample, input.shape[3] // sample), mode="nearest")
+            y = self._conv_forward(input, weight, bias, reflect)
+            return nn.functional.relu(y) if relu else y
         s, p, k, d = self.stride, self.padding, self.kernel_size, self.dilation
         hip = conv_backend() in _HIP_BACKENDS
         if reflect and not (hip and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4):
@@ -56,16 +82,7 @@ class Conv2d(nn.Conv2d):
                 and input.dim() == 4 and self.groups == 1 and self.padding_mode == "zeros"
                 and not isinstance(p, str) and s[0] == s[1] and p[0] == p[1] and d[0] == d[1]):
             from . import _lib, ops
-            # frozen-weight inference (inference.py): a record attached by freeze(), validated, when this call may use it
-            # — only for the tensor the record stands for: the module's own weight, or the W / sigma its spectral hook just handed out
-            # (validated there: once per call)
-            rec = self.__dict__.get("_cocos_frozen")
-            if rec is not None:
-                if rec.hook is not None:
-                    handed, rec.handed = rec.handed, False
-                    rec = rec if handed and weight is rec.weight else None
-                else:
-                    rec = rec.use() if weight is self.weight else None
+            rec = self._frozen_record(weight)
             try:
                 if k == (1, 1) and s[0] == 1 and p[0] == 0 and not reflect:
                     return ops.proj1x1(input, weight, bias, rec)
@@ -324,7 +341,9 @@ class SPADEResnetBlock(nn.Module):
     def forward(self, x, seg):
         # ONE nearest resize of the label map for the block's two or three SPADEs (the reference resizes inside each,
         # normalization.py:133: same values; spade.spade_forward skips it when the grids already agree)
-        if seg.shape[2:] != x.shape[2:]:
+        # (a label map with a fresh record stays as it is: its SPADEs sample the record's index map themselves — spade.label_plan)
+        from .spade import keeps_label_grid
+        if seg.shape[2:] != x.shape[2:] and not keeps_label_grid(x, seg):
             seg = nn.functional.interpolate(seg, size=x.size()[2:], mode="nearest")
         x_s = self.conv_s(self.norm_s(x, seg)) if self.learned_shortcut else x
         dx = reflect_conv(self.pad, self.conv_0, self._norm_act(self.norm_0, x, seg))         # norm -> LeakyReLU(0.2) -> pad -> conv
@@ -405,11 +424,16 @@ class AdaptiveFeatureGenerator(nn.Module):
     def _conv_norm_act(self, layer, x, slope: float):
         """`layer` = conv [+ InstanceNorm2d] (nonspade_norm_layer), followed by LeakyReLU(slope) (slope 1.0: none).  The parameter-free
         InstanceNorm and the activation are K13 — one HBM pass forward, one backward — instead of the framework's batch-norm
-        kernels + leaky_relu (generator.py:133-138 calls them as `layerK(self.actvn(x))`: same values, other grouping)."""
+        kernels + leaky_relu (generator.py:133-138 calls them as `layerK(self.actvn(x))`: same values, other grouping).
+        layer1 of a one-hot input that carries a label record (labels.record_of): its convolution is K35 on the record's index map."""
+        labels = None
+        if layer is self.layer1 and x.is_cuda:
+            from .labels import record_of
+            labels = record_of(x)
         if (isinstance(layer, nn.Sequential) and len(layer) == 2 and type(layer[1]) is nn.InstanceNorm2d and not layer[1].affine
                 and not layer[1].track_running_stats and x.is_cuda and x.dtype == torch.float32 and conv_backend() in _HIP_BACKENDS):
             from . import ops
-            y = layer[0](x)
+            y = layer[0](x) if labels is None else layer[0](x, labels=labels)
             large = y.shape[2] * y.shape[3] > 16384
             if large and not ops.INSTNORM_SPLIT:
                 # K13 keeps a plane in registers up to 128 x 128; beyond that its streaming flavour (one workgroup per plane, five
@@ -422,7 +446,10 @@ class AdaptiveFeatureGenerator(nn.Module):
             if w is None:
                 w = self._slopes[key] = torch.full((1,), float(slope), device=y.device, dtype=torch.float32)
             return (ops.instnorm_prelu_split if large else ops.instnorm_prelu)(y, None, w, layer[1].eps)
-        y = layer(x)
+        if labels is not None and isinstance(layer, Conv2d):      # (layer1 without a norm behind it: norm_E = spectral | none)
+            y = layer(x, labels=labels)
+        else:
+            y = layer(x)
         return y if slope == 1.0 else nn.functional.leaky_relu(y, slope)
 
     def forward(self, x, seg):

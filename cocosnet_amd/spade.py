@@ -76,9 +76,41 @@ def modulate(x, gamma, beta, pono: bool, param_free_norm=None, slope: float = 1.
     return y if slope == 1.0 else F.leaky_relu(y, slope)
 
 
-def shared_activation(self, segmap):
+def label_plan(self, x, segmap):
+    """(record, s) when this SPADE's `mlp_shared(resize(segmap))` can run on the label route (K35, ops.label_conv3x3), else None:
+    segmap carries a fresh label record (labels.record_of), its grid is a whole multiple s of x's, x is CUDA fp32 and mlp_shared is
+    Sequential(ReflectionPad2d(1), producers.Conv2d 3x3, ReLU) of a shape ops.label_conv_ok takes.  Every other mlp_shared (the
+    reference's own nn.Conv2d, a 5x5 SPADE, pad_type "zero" variants) runs as it always did."""
+    from . import labels, producers
+    rec = labels.record_of(segmap)
+    if rec is None or not _hip_ok(x) or x.dim() != 4 or producers.conv_backend() not in producers._HIP_BACKENDS:
+        return None
+    m = getattr(self, "mlp_shared", None)
+    if not (isinstance(m, nn.Sequential) and len(m) == 3 and isinstance(m[0], nn.ReflectionPad2d) and tuple(m[0].padding) == (1, 1, 1, 1)
+            and isinstance(m[1], producers.Conv2d) and type(m[2]) is nn.ReLU):
+        return None
+    conv = m[1]
+    s = labels.whole_ratio(rec, x.shape[2:])
+    if (s < 1 or conv.groups != 1 or conv.padding_mode != "zeros" or rec.index.device != x.device
+            or not ops.label_conv_ok(conv.weight, rec.index, s, 1, conv.stride, conv.padding, conv.dilation, rec.nc)):
+        return None
+    return rec, s
+
+
+def keeps_label_grid(x, segmap) -> bool:
+    """A SPADEResnetBlock does NOT resize a label map that carries a fresh record whose grid is a whole multiple of x's: its SPADEs
+    sample the index map themselves (a SPADE that cannot resizes the tensor itself, as the reference does)."""
+    from . import labels
+    rec = labels.record_of(segmap)
+    return rec is not None and _hip_ok(x) and x.dim() == 4 and labels.whole_ratio(rec, x.shape[2:]) >= 1
+
+
+def shared_activation(self, segmap, labels=None, sample: int = 1):
     """`self.mlp_shared(segmap)` (normalization.py:139): conv + ReLU of the label map.  Its own function so that a caller can put
-    another evaluation of the same piecewise-linear map in its place."""
+    another evaluation of the same piecewise-linear map in its place.  `labels`, `sample`: what label_plan found — the reflect-padded
+    3x3 convolution + ReLU of the map sampled at every `sample`-th pixel, from the record's index map (segmap itself is not read)."""
+    if labels is not None:
+        return self.mlp_shared[1](segmap, reflect=1, labels=labels, sample=sample, relu=True)
     return self.mlp_shared(segmap)
 
 
@@ -86,9 +118,13 @@ def spade_forward(self, x, segmap, similarity_map=None, slope: float = 1.0):
     """Drop-in for `SPADE.forward(x, segmap, similarity_map=None)` (normalization.py:129-151); works on the reference's
     module instances (attributes param_free_norm, mlp_shared, pad, mlp_gamma, mlp_beta, pad_type).  `slope`: negative
     slope of the LeakyReLU the caller would apply next (1.0 = none)."""
-    if segmap.shape[2:] != x.shape[2:]:      # (spade_resnet_block_forward resizes once for the block's two or three SPADEs)
-        segmap = F.interpolate(segmap, size=x.size()[2:], mode="nearest")
-    actv = shared_activation(self, segmap)
+    plan = label_plan(self, x, segmap)
+    if plan is not None:                     # K35 on the record's index map: no resize, the one-hot tensor is not read
+        actv = shared_activation(self, segmap, labels=plan[0], sample=plan[1])
+    else:
+        if segmap.shape[2:] != x.shape[2:]:      # (spade_resnet_block_forward resizes once for the block's two or three SPADEs)
+            segmap = F.interpolate(segmap, size=x.size()[2:], mode="nearest")
+        actv = shared_activation(self, segmap)
     if getattr(self, "pad_type", "nozero") != "zero":
         actv = self.pad(actv)
     gamma, beta = self.mlp_gamma(actv), self.mlp_beta(actv)
@@ -108,7 +144,7 @@ def spade_resnet_block_forward(self, x, seg1):
     # the reference resizes the label map inside every SPADE (normalization.py:133): the block's SPADEs all see x's grid (its
     # convolutions keep the size), so ONE nearest resize serves them — and the convolutions that read it find its max|.| from the
     # first one (per module step: 24 resize kernels and as many max|.| passes less)
-    if seg1.shape[2:] != x.shape[2:]:
+    if seg1.shape[2:] != x.shape[2:] and not keeps_label_grid(x, seg1):      # (a recorded label map: its SPADEs sample the index map)
         seg1 = F.interpolate(seg1, size=x.size()[2:], mode="nearest")
     x_s = self.conv_s(self.norm_s(x, seg1)) if self.learned_shortcut else x            # :97-102
     pad = self.pad if getattr(self, "pad_type", "nozero") != "zero" else (lambda t: t)

@@ -1134,6 +1134,35 @@ int cocos_instnorm_prelu_split_bwd(const float* x, const float* residual, const 
                                    const float* stats, float* dx, float* dresidual, float* da_out, float* workspace,
                                    float* dx_amax_inout_dev, int planes, int N, float eps, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K35 3x3 convolution of a ONE-HOT label map as nine table look-ups per output pixel (label_conv.hip):
+ *       y[b, :, p] = bias + sum_tap W[:, label(p + tap), tap]
+ *     exact fp32 sums of at most ten numbers; 4 bytes read per pixel instead of 4 nc; no operand preparation.
+ *   cocos_labels_one_hot: label_map int64 [B,1,H,W] -> onehot fp32 [B,nc,H,W] (EVERY element written) and index int32
+ *       [B,H,W].  A label outside [0, nc) gives an all-zero column and index -1.  1 <= nc <= 32767.
+ *   cocos_label_conv_table: weight [Cout,nc,3,3] -> table [9][nc][Cout] (tap-major; tap = 3 ky + kx).
+ *   cocos_label_conv3x3_fwd: index [B,Hs,Ws] on its source grid; the output grid is (Hs/sample) x (Ws/sample) and output
+ *       pixel (y, x) stands on source pixel (y sample, x sample) — F.interpolate(mode="nearest") for whole ratios
+ *       (Hs, Ws multiples of sample, else COCOS_ERR_UNSUPPORTED).  reflect 0: zero padding 1; 1: ReflectionPad2d(1) of
+ *       the sampled grid (needs a 2x2 grid or more).  bias nullable; relu != 0: y = max(y, 0).  An index of -1 (or any
+ *       value outside [0, nc)) contributes nothing.  y fp32 [B,Cout,H,W], Cout % 16 == 0; table and bias 16-byte aligned.
+ *       y_amax_inout_dev (nullable): *cell = max(*cell, max|y|), the cell holding a finite value >= 0.
+ *   cocos_label_conv3x3_bwd_workspace_floats: floats of `workspace` for _bwd at an OUTPUT grid of H x W (host arithmetic;
+ *       0 for bad dims): per-slice partial sums, at most 64 MiB + the slices of dbias.
+ *   cocos_label_conv3x3_bwd: dweight [Cout,nc,3,3] (every element written: classes that never occur get exact zeros) and
+ *       dbias [Cout] (nullable) from dy [B,Cout,H,W].  y_saved (nullable) = the forward's output when it ran with relu:
+ *       dy is masked where y_saved <= 0.  No atomics; the order of every sum is fixed by the shapes alone: two calls on
+ *       the same inputs give the same bits.  No input gradient exists.
+ * ------------------------------------------------------------------------------------- */
+int cocos_labels_one_hot(const long long* label_map, float* onehot, int* index, int B, int nc, int H, int W, cocos_stream_t stream);
+int cocos_label_conv_table(const float* weight, float* table, int Cout, int nc, cocos_stream_t stream);
+int cocos_label_conv3x3_fwd(const int* index, const float* table, const float* bias, float* y, float* y_amax_inout_dev, int B,
+                            int Hs, int Ws, int sample, int reflect, int relu, int nc, int Cout, cocos_stream_t stream);
+size_t cocos_label_conv3x3_bwd_workspace_floats(int B, int H, int W, int nc, int Cout);
+int cocos_label_conv3x3_bwd(const int* index, const float* dy, const float* y_saved, float* dweight, float* dbias,
+                            float* workspace, int B, int Hs, int Ws, int sample, int reflect, int nc, int Cout,
+                            cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
