@@ -310,6 +310,12 @@ _SIGNATURES = {
     "cocos_label_conv3x3_fwd": (ctypes.c_int, [ctypes.c_void_p] + [_c_float_p] * 4 + [ctypes.c_int] * 8 + [_stream_t]),
     "cocos_label_conv3x3_bwd_workspace_floats": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "cocos_label_conv3x3_bwd": (ctypes.c_int, [ctypes.c_void_p] + [_c_float_p] * 5 + [ctypes.c_int] * 7 + [_stream_t]),
+    # K36: idx is int32 device memory
+    "cocos_corr_match_f16x3": (ctypes.c_int, [ctypes.c_void_p] * 5 + [_c_float_p] * 2 + [ctypes.c_int] * 4
+                               + [ctypes.c_float, ctypes.c_float, ctypes.c_longlong, _stream_t]),
+    "cocos_row_argmax_lse": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p] + [ctypes.c_int] * 3 + [_stream_t]),
+    "cocos_gather_patches": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 5
+                             + [ctypes.c_longlong, _stream_t]),
     "cocos_debug_mfma_probe": (ctypes.c_int, [_c_float_p, _stream_t]),
 }
 

@@ -65,6 +65,9 @@ HIP_SOURCES = [
     "weight_prepare_multi.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
+    "corr_match_f16x3.hip",
+    "row_argmax_lse.hip",
+    "gather_patches.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

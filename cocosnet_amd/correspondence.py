@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import HotPathConfig, correspondence_hot_path
+from .hot_path import HotPathConfig, correspondence_hot_path, correspondence_match
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -268,6 +268,43 @@ class NoVGGCorrespondence(NetworkBase):
             return res
         coor_out.update(res)
         return coor_out
+
+    def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False):
+        """Where each position matched, and how sure the match is — the hard readout of the correlation that
+        `forward(..., return_corr=True)` returns as a [B,HW,HW] matrix (:305-306), without that matrix wherever the fused
+        match_kernel-1 back end runs (hot_path.correspondence_match).  Forward only.
+
+        direction="rows": per content position its best exemplar position; "cols": per exemplar position its best content position.
+        Returns {match_index [B,h,w] int64 (flat position on the other side's grid), match_xy [B,2,h,w] (x, y), match_prob (the
+        match's softmax weight), match_lse} and, with `hard_warp`, warp_hard [B,3,H,W]: every content cell filled with the
+        down x down patch of ref_img at its match (rows only).  `exemplar`: a record of inference.prepare_exemplar in place of
+        ref_img / ref_seg_map (both None)."""
+        if direction not in ("rows", "cols"):
+            raise ValueError(f"match: direction {direction!r}: expected 'rows' or 'cols'")
+        if hard_warp and direction == "cols":
+            raise ValueError("match: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
+        keys = phi_raw = None
+        with torch.no_grad():
+            if exemplar is not None:
+                exemplar = self._check_exemplar(exemplar, seg_map.shape[0])
+                if inference.FROZEN:
+                    theta_raw, keys = self._project_content(seg_map, exemplar, lazy=True)
+                    phi_raw, ref_img = None, exemplar.ref_img
+                    if not isinstance(keys, ops.PreparedKeys):      # CPU / fp64 content: the record's projection itself — the
+                        phi_raw, keys = keys, None                  # readout then refuses the tensors ("no CPU fallback")
+                else:
+                    ref_img, ref_seg_map = _stored_inputs(exemplar, seg_map.shape[0])
+            elif ref_img is None or ref_seg_map is None:
+                raise ValueError("match: ref_img and ref_seg_map are required without a prepared exemplar")
+            if keys is None and phi_raw is None:      # (real_img: project() reads it for the training-time featpair term only)
+                theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
+            cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction)
+            out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse}
+            if hard_warp:
+                fh, fw = m.index.shape[1:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+        return out
 
 
 def _stored_inputs(exemplar, batch):

@@ -558,3 +558,88 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
             if want_two:
                 out["warp_i2r2i"] = o_r2[:, pos:].reshape(B, -1, fh, fw)
     return out
+
+
+# ---- K36: match readout ---------------------------------------------------------------------------------------------------------
+@dataclass
+class MatchReadout:
+    """Where every position matched and how sure the match is (correspondence_match): per position of the [fh, fw] grid of the
+    side that asks, `index` the flat position y * gw + x of its best match on the other side's [gh, gw] grid (int64), `max_logit`
+    the logit of that match (cosine / temperature), `lse` the log-sum-exp of the position's logits and `prob` = exp(max_logit - lse),
+    the match's softmax weight — each [B,fh,fw]."""
+    index: torch.Tensor
+    prob: torch.Tensor
+    max_logit: torch.Tensor
+    lse: torch.Tensor
+    grid: tuple = None      # (gh, gw) of the side the indices point into; None = the same as index.shape[1:]
+
+    def xy(self):
+        """[B,2,fh,fw] int64: (x, y) of the match on the other side's grid — index = y * gw + x"""
+        gw = (self.grid or tuple(self.index.shape[1:]))[1]
+        return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=1)
+
+
+def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows"):
+    """The hard readout of the correlation of correspondence.py:272-304: argmax, maximum and log-sum-exp of every row of the scaled
+    matrix f / temperature that forward(return_corr=True) returns (:305-306) — `direction="rows"`: per CONTENT position over the
+    exemplar positions; "cols": per EXEMPLAR position over the content positions (the rows of f^T).  Returns a MatchReadout.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1, as for correspondence_hot_path; `exemplar`: the ops.PreparedKeys
+    of a prepared exemplar in place of phi_raw (None).  Routes mirror correspondence_hot_path's: where its fused match_kernel-1
+    back end runs (C == 256, PONO_C, the split-precision kernels) the operand planes go to K36a and nothing HWxHW is allocated;
+    everywhere else (match_kernel 3, no PONO_C, COCOS_PRECISION=fp32, odd sizes, ops.MATCH_FUSED = False) the logits are
+    materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad()."""
+    if direction not in ("rows", "cols"):
+        raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
+    if (exemplar is None) == (phi_raw is None):
+        raise ValueError("correspondence_match: pass phi_raw or a prepared exemplar in its place (not both)")
+    B, C, fh, fw = theta_raw.shape
+    N = fh * fw
+    mk, inv_t = cfg.match_kernel, 1.0 / temperature
+    rows = direction == "rows"
+    if exemplar is not None:
+        exemplar.check(B)
+        if exemplar.shape[1:] != theta_raw.shape[1:]:
+            raise ValueError(f"prepared exemplar: feature grid {tuple(exemplar.shape)} does not match the content's {tuple(theta_raw.shape)}")
+    elif isinstance(theta_raw, ops.LazyProj1x1) != isinstance(phi_raw, ops.LazyProj1x1):
+        raise TypeError("correspondence_match: theta and phi must both be tensors or both be ops.LazyProj1x1")
+    gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
+    Nk = gh * gw
+    raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
+    with torch.no_grad():
+        if not _hip_fp32(theta_raw):
+            raise ops._lib.CocosHipError("correspondence_match: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+        fused = (ops.MATCH_FUSED and mk == 1 and C == ops.FUSED_K and cfg.PONO_C and ops.corr_split_ok(B, C, N, Nk, 1, False))
+        if fused and exemplar is not None:
+            # the query side as _attention_with_exemplar makes it; the record's key planes are read in place
+            if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
+                qh, ql, _ = ops.proj_center_l2norm_planes_one(theta_raw, 1)      # K23, theta alone
+            else:
+                qh, ql, _ = ops.center_l2norm_planes_fwd(_flat(raw(theta_raw)), 1)
+            if rows:
+                idx, mx, lse = ops.corr_match_shared(qh, ql, exemplar, inv_t)
+            else:       # the exemplar's positions ask: B different key sets (the contents), so the record's planes are needed per sample
+                kh, kl, _ = exemplar.split_planes(B)
+                idx, mx, lse = ops._corr_match_planes(kh, kl, qh, ql, inv_t)
+        elif fused:
+            planes = ops.OperandPlanes()
+            if (isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
+                    and ops.proj_norm_fused_ok(phi_raw)):
+                qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw.detach(), phi_raw.detach(), 1, planes, want_chan=False)   # K23
+            else:
+                qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
+                kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
+            idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
+        else:
+            th = raw(theta_raw).detach()
+            ph = (exemplar.phi_raw(B) if exemplar is not None else raw(phi_raw)).detach()
+            if mk == 3 and cfg.PONO_C:
+                f = _box3_logits(th, ph, inv_t, transposed=not rows)
+            else:   # f^T is the same matrix with the operands exchanged (centring and normalisation are per tensor)
+                f = _scaled_logits(th, ph, cfg, inv_t, False, 1) if rows else _scaled_logits(ph, th, cfg, inv_t, False, 1)
+            idx, mx, lse = ops.row_argmax_lse(f)
+            del f
+        own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
+        shape = (B,) + own
+        return MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
+                            max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)

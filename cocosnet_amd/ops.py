@@ -61,6 +61,9 @@ VALUE_LO_SKIP = True
 PROJ_STREAM = True
 #: power-of-two pre-scale of the unit-norm operands before the f16 split (keeps the lo plane normal)
 SPLIT_OPERAND_SCALE = 16.0
+#: K36 match readout (hot_path.correspondence_match): True = the fused kernel (K36a: nothing HWxHW in memory) wherever the
+#: split-precision correlation runs; False = every route materialises its logits and reads them with K36b
+MATCH_FUSED = True
 
 
 def _stream():
@@ -873,6 +876,89 @@ def corr_softmax_warp_shared(qh, ql, keys: PreparedKeys, values: PreparedValues,
     _call("corr_softmax_warp_fwd", "cocos_corr_softmax_warp_fwd_f16x3_shared", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(),
           kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(), lse.data_ptr(), None, v_scale.data_ptr(), _ptr(v_lomask),
           B, K, Nq, Nk, Cv, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if dense else 0, Cv * Nk if dense else 0, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# K36  match readout: row maximum, its index and the row log-sum-exp   (correspondence.py:291,:304-307 + the caller's max / argmax)
+# ------------------------------------------------------------------------------------------
+def _corr_match_planes(qh, ql, kh, kl, inv_temperature: float):
+    """K36a on operand planes: qh, ql [B,Nq,256], kh, kl [B or 1,Nk,256] (1: every sample reads the one key set, batch stride 0)
+    -> (idx int32, max, lse), each [B,Nq]."""
+    for t in (qh, ql, kh, kl):
+        if not t.is_cuda:
+            raise _lib.CocosHipError("corr_match: expected CUDA/HIP operand planes; the correspondence hot path has no CPU fallback")
+        if t.dtype != torch.float16 or not t.is_contiguous():
+            raise TypeError("corr_match: operand planes are contiguous float16 tensors")
+    B, Nq, K = qh.shape
+    Be, Nk = kh.shape[0], kh.shape[1]
+    if Be not in (B, 1) or kh.shape[2] != K or ql.shape != qh.shape or kl.shape != kh.shape:
+        raise ValueError(f"corr_match: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)}")
+    idx = torch.empty((B, Nq), device=qh.device, dtype=torch.int32)
+    mx = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("corr_match", "cocos_corr_match_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
+          mx.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if Be == B else 0, _stream())
+    return idx, mx, lse
+
+
+def corr_match(qn, kn, inv_temperature: float, planes: OperandPlanes | None = None):
+    """(idx int32, max, lse), each [B,Nq]: max[b,i] = max_j <qn[b,:,i], kn[b,:,j]> * inv_temperature, idx its (lowest) j, lse the
+    row log-sum-exp — corr_softmax_warp's logits without its value tensor (K36a; forward only).  qn [B,256,Nq], kn [B,256,Nk]
+    unit-norm columns, or the handles of producer-made planes registered in `planes` (center_l2norm_planes, K23), as for
+    corr_softmax_warp.  Shapes the kernel does not take (K != 256, Nk % 4 != 0) raise: materialise and use row_argmax_lse."""
+    for t, name in ((qn, "qn"), (kn, "kn")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"corr_match: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if planes is None:
+        planes = OperandPlanes()
+    with torch.no_grad():
+        qn, kn = (t if planes.has(t) else _chk(t.detach(), "corr_match") for t in (qn, kn))
+        return _corr_match_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
+                                  inv_temperature)
+
+
+def corr_match_shared(qh, ql, keys: PreparedKeys, inv_temperature: float):
+    """corr_match with the key planes of a prepared exemplar read in place: qh, ql [B,Nq,256] (this call's query planes), a record
+    of batch B or 1 — with 1 every query batch reads the one key set (batch stride 0: no copies)."""
+    kh, kl, _ = keys.split_planes()
+    with torch.no_grad():
+        return _corr_match_planes(qh, ql, kh, kl, inv_temperature)
+
+
+def row_argmax_lse(f: torch.Tensor):
+    """(idx int32, max, lse), each f.shape[:-1], of the rows of a materialised logit matrix f [..., Nk] in one sweep (K36b):
+    torch.max(f, -1) (the lowest index among equal maxima) and torch.logsumexp(f, -1).  Forward only."""
+    f = _chk(f.detach(), "row_argmax_lse: f")
+    if f.dim() < 2 or f.numel() == 0:
+        raise ValueError(f"row_argmax_lse: expected a non-empty [..., Nq, Nk] tensor, got {tuple(f.shape)}")
+    Nk, Nq = f.shape[-1], f.shape[-2]
+    lead = f.shape[:-1]
+    B = f.numel() // (Nq * Nk)
+    idx = torch.empty(lead, device=f.device, dtype=torch.int32)
+    mx = torch.empty(lead, device=f.device, dtype=torch.float32)
+    lse = torch.empty(lead, device=f.device, dtype=torch.float32)
+    _call("row_argmax_lse", "cocos_row_argmax_lse", f.data_ptr(), idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, Nq, Nk, _stream())
+    return idx, mx, lse
+
+
+def gather_patches(img: torch.Tensor, idx: torch.Tensor, h: int, w: int, down: int):
+    """The hard warp (K36c): out [B,C,H,W] whose cell (y, x) of the h x w grid is the down x down patch of img at the cell idx[b, y*w+x]
+    — a bitwise copy.  img [Be,C,H,W] fp32 with H == h*down, W == w*down and Be == B or 1 (one exemplar for all); idx [B,h*w] or
+    [B,h,w], any integer type (values outside [0, h*w) are clamped into it)."""
+    img = _chk(img.detach(), "gather_patches: img")
+    if not idx.is_cuda:
+        raise _lib.CocosHipError("gather_patches: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise TypeError(f"gather_patches: idx must be an integer tensor, got {idx.dtype}")
+    Be, C, H, W = img.shape
+    B = idx.shape[0]
+    if (H, W) != (h * down, w * down) or idx.numel() != B * h * w or Be not in (B, 1):
+        raise ValueError(f"gather_patches: img{tuple(img.shape)} idx{tuple(idx.shape)} do not fit a {h}x{w} grid with down={down}")
+    idx = idx.reshape(B, h * w).to(torch.int32).contiguous()
+    out = torch.empty((B, C, H, W), device=img.device, dtype=torch.float32)
+    _call("gather_patches", "cocos_gather_patches", img.data_ptr(), idx.data_ptr(), out.data_ptr(), B, C, H, W, int(down),
+          C * H * W if Be == B else 0, _stream())
     return out
 
 

@@ -1163,6 +1163,35 @@ int cocos_label_conv3x3_bwd(const int* index, const float* dy, const float* y_sa
                             float* workspace, int B, int Hs, int Ws, int sample, int reflect, int nc, int Cout,
                             cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K36 match readout: where each content position matched in the exemplar, and how sure the match is — what a caller of the
+ *     reference's forward(return_corr=True) takes with max / argmax over the returned [B,HW,HW] matrix
+ *     (correspondence.py:291, :304-307).
+ *   cocos_corr_match_f16x3 (K36a, corr_match_f16x3.hip): from the operand planes of cocos_corr_softmax_warp_fwd_f16x3
+ *       (qh,ql [B,Nq,256], kh,kl [B,Nk,256]: position-major f16 hi / lo planes of unit-norm columns x operand_scale) and with
+ *       that kernel's QK arithmetic (three f16 MFMA terms, fp32 accumulate, same order: the same logits), per query i
+ *         max_out[b,i] = max_j inv_temperature <q_i, k_j>            (natural units)
+ *         idx_out[b,i] = the j of that maximum, the lowest one among equals; always in [0, Nk), also for non-finite input
+ *         lse_out[b,i] = log sum_j exp(inv_temperature <q_i, k_j>)   (confidence of the match: exp(max - lse))
+ *       Nothing Nq x Nk reaches memory.  k_batch_stride (halfs): Nk * 256, or 0 = every sample reads the ONE key set at kh, kl
+ *       (a prepared exemplar); anything else is COCOS_ERR_INVALID.  Supported: K == 256, Nk % 4 == 0, any Nq >= 1
+ *       (otherwise COCOS_ERR_UNSUPPORTED; nothing is launched).  Planes 16-byte aligned.
+ *   cocos_row_argmax_lse (K36b, row_argmax_lse.hip): the same three results from a materialised matrix logits [B,Nq,Nk] in one
+ *       sweep (16-byte loads when Nk % 4 == 0 and the base is 16-byte aligned): max is an element of the row, bit for bit;
+ *       same tie and range rules.  Any Nq, Nk >= 1.  For every route that holds its logits in memory anyway.
+ *   cocos_gather_patches (K36c, gather_patches.hip): the hard warp at full resolution, a bitwise copy:
+ *         out[b,c,y down+dy,x down+dx] = img[b_e,c,(j / w) down+dy,(j % w) down+dx],  j = idx[b, y w + x],  h = H / down, w = W / down
+ *       img [Be,C,H,W] with img_batch_stride = C H W (b_e = b) or 0 (Be = 1: b_e = 0; anything else is COCOS_ERR_INVALID),
+ *       idx [B,h w] int32, out [B,C,H,W].  An index outside [0, h w) is clamped into it.  H, W multiples of down
+ *       (else COCOS_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------- */
+int cocos_corr_match_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out, float* max_out,
+                           float* lse_out, int B, int K, int Nq, int Nk, float inv_temperature, float operand_scale,
+                           long long k_batch_stride, cocos_stream_t stream);
+int cocos_row_argmax_lse(const float* logits, int* idx, float* max, float* lse, int B, int Nq, int Nk, cocos_stream_t stream);
+int cocos_gather_patches(const float* img, const int* idx, float* out, int B, int C, int H, int W, int down,
+                         long long img_batch_stride, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
