@@ -35,10 +35,6 @@ _VGG_LEVEL_WEIGHTS = (1.0 / 32, 1.0 / 16, 1.0 / 8, 1.0 / 4, 1.0)
 _VGG_KEYS = ["r12", "r22", "r32", "r42", "r52"]
 
 
-def _unsupported(e: Exception) -> bool:
-    return getattr(e, "code", 0) == -2          # COCOS_ERR_UNSUPPORTED (include/cocos_hip.h)
-
-
 def _gpu_f32(t) -> bool:
     return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
 
@@ -60,7 +56,7 @@ def _try(fused, framework):
     try:
         return fused()
     except _lib.CocosHipError as e:
-        if not _unsupported(e):
+        if not e.unsupported:
             raise
     return framework()
 
@@ -127,7 +123,7 @@ def _gan_fused(gan_mode, real_label, fake_label, input, target_is_real, for_disc
     try:
         out = ops.gan_loss(preds, mode, label)
     except _lib.CocosHipError as e:
-        if not _unsupported(e):
+        if not e.unsupported:
             raise
         return None
     return out if isinstance(input, list) else out.reshape(())      # a list gives the reference's [1], a tensor its 0-dim mean

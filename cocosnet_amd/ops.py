@@ -17,6 +17,9 @@ import torch
 
 from . import _lib
 
+_C = _lib.CONSTANTS      # the integer #defines of include/cocos_hip.h
+#: K1's `center_over_channels`: the mean over the positions of a channel, over the channels of a position (PONO_C), or none
+CENTER_POSITIONS, CENTER_CHANNELS, CENTER_NONE = _C["COCOS_CENTER_POSITIONS"], _C["COCOS_CENTER_CHANNELS"], _C["COCOS_CENTER_NONE"]
 #: `sys.float_info.epsilon`, the constant the reference adds to the norm (correspondence.py:279,288)
 NORM_EPS = sys.float_info.epsilon
 #: widest V the fused kernel takes in one launch (5 blocks of 32 channels)
@@ -135,8 +138,8 @@ class _CenterL2Norm(torch.autograd.Function):
         B, K, N = x.shape
         y = torch.empty_like(x)
         norm = torch.empty((B, N), device=x.device, dtype=torch.float32)
-        center_over_channels = int(center_over_channels)      # 0 positions, 1 channels (PONO_C), 2 none
-        row_ws = None if center_over_channels else torch.empty((B, K), device=x.device,
+        center_over_channels = int(center_over_channels)      # CENTER_*
+        row_ws = None if center_over_channels != CENTER_POSITIONS else torch.empty((B, K), device=x.device,
                                                                 dtype=torch.float32)
         _call("center_l2norm_fwd", "cocos_center_l2norm_fwd", x.data_ptr(), y.data_ptr(), norm.data_ptr(),
                   _ptr(row_ws), B, K, N, int(center_over_channels), float(eps), _stream())
@@ -152,12 +155,12 @@ class _CenterL2Norm(torch.autograd.Function):
         B, K, N = y.shape
         dx = torch.empty_like(y)
         col_ws = row_ws = None
-        if not center_over_channels:
+        if center_over_channels == CENTER_POSITIONS:
             col_ws = torch.empty((B, N), device=y.device, dtype=torch.float32)
             row_ws = torch.empty((B, K), device=y.device, dtype=torch.float32)
         # max|dx| as a by-product: K0's backward (the consumer on the theta/phi path) needs it.  Mode 2
         # (feature_normalize) feeds MIOpen convolutions: nobody would pick the value up
-        if PROJ_PRECISION == "f16x3" and center_over_channels != 2:
+        if PROJ_PRECISION == "f16x3" and center_over_channels != CENTER_NONE:
             cell = _zero_cell(dx.device)
             _call("center_l2norm_bwd", "cocos_center_l2norm_bwd_amax", y.data_ptr(), norm.data_ptr(), dy.data_ptr(),
                   dx.data_ptr(), _ptr(col_ws), _ptr(row_ws), B, K, N, int(center_over_channels), eps,
@@ -172,7 +175,7 @@ class _CenterL2Norm(torch.autograd.Function):
 
 def center_l2norm(x: torch.Tensor, center_over_channels, eps: float = NORM_EPS):
     """x [B,K,N] -> (x - mean) / (||x - mean||_2 over K + eps); mean over K (True / 1: PONO_C), over N
-    (False / 0) or no centring at all (2)."""
+    (False / 0) or no centring at all (2): CENTER_CHANNELS, CENTER_POSITIONS, CENTER_NONE."""
     return _CenterL2Norm.apply(x, int(center_over_channels), eps)
 
 
@@ -180,7 +183,7 @@ def feature_normalize(x: torch.Tensor, eps: float = NORM_EPS):
     """util.feature_normalize (util/util.py:31-34): x [B,C,h,w] / (||x||_2 over C + eps) — K1 without
     the centring; used on the adaptor outputs right before the ResidualBlocks (correspondence.py:247-248)."""
     B, C = x.shape[:2]
-    return _CenterL2Norm.apply(x.reshape(B, C, -1), 2, eps).reshape(x.shape)
+    return _CenterL2Norm.apply(x.reshape(B, C, -1), CENTER_NONE, eps).reshape(x.shape)
 
 
 
@@ -2478,14 +2481,14 @@ class _Box3SoftmaxWarp(torch.autograd.Function):
         d_pre = _rowdot_cached(dout, out) if BWD_D_PRECOMPUTED else None
         (gph, gpl, gs), (vph, vpl, v_scale) = _split_pair_transposed(dout, g_amax, v, ctx.v_amax, cvp)
         f32 = dict(device=v.device, dtype=torch.float32)
-        sink, flags = ctx.sink, (1 if ctx.transposed else 0)
+        sink, flags = ctx.sink, (_C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
         if not ctx.needs_input_grad[0]:
             sink = None          # nobody differentiates T through this pass (autograd.grad(..., inputs=[v])): its G is scratch and must
                                  # not become — or be added into — the shared buffer
         if sink is not None and sink.buf is not None:      # another pass over this T has written its G: add ours to it
             g, g_ret = sink.buf, None
             gmax = sink.gmax = _zero_cell(v.device)        # ... and max|G| becomes that of the sum (a fresh zero cell)
-            flags |= 2
+            flags |= _C["COCOS_BOX3_G_ACCUMULATE"]
         else:
             g = g_ret = torch.empty(B * N * N, **f32)
             gmax = _zero_cell(v.device)
@@ -2506,7 +2509,7 @@ class _Box3SoftmaxWarp(torch.autograd.Function):
               v_scale.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), g.data_ptr(), dmu.data_ptr(),
               da.data_ptr(), dnu.data_ptr(), db.data_ptr(), colpart.data_ptr(), gmax.data_ptr(), _ptr(psh), _ptr(psl),
               _ptr(ctx.v_lomask), B, N, N, Cv, cvp, h, w, kc, scale, _ptr(d_pre), flags, _stream())
-        if flags & 2:
+        if flags & _C["COCOS_BOX3_G_ACCUMULATE"]:
             # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand, so that whatever
             # was derived from the buffer as it was (the first pass's max|G| cell among them) is void
             torch.autograd.graph.increment_version(g)
@@ -3062,7 +3065,7 @@ class _WarpHead(torch.autograd.Function):
         return dout, None, None, None, None
 
 
-_HEAD_MODES = {"nearest": 0, "bilinear": 1, "patch": 2}      # COCOS_WARP_HEAD_* of cocos_hip.h
+_HEAD_MODES = {m: _C["COCOS_WARP_HEAD_" + m.upper()] for m in ("nearest", "bilinear", "patch")}
 
 
 class _WarpHeadModes(torch.autograd.Function):
@@ -3706,10 +3709,10 @@ def relu_pool2(y: torch.Tensor, mode: str = "max", keep_r: bool = False):
 #      (pix2pix_model.py:205-296, util/util.py:36-43, networks/loss.py:15-97)
 # ------------------------------------------------------------------------------------------
 #: widest group one launch takes (COCOS_PAIR_LOSS_MAX_SEGMENTS / COCOS_GAN_LOSS_MAX_TENSORS of include/cocos_hip.h)
-PAIR_LOSS_MAX_SEGMENTS = 16
-GAN_LOSS_MAX_TENSORS = 8
+PAIR_LOSS_MAX_SEGMENTS = _C["COCOS_PAIR_LOSS_MAX_SEGMENTS"]
+GAN_LOSS_MAX_TENSORS = _C["COCOS_GAN_LOSS_MAX_TENSORS"]
 #: GANLoss.loss's cases -> the kernel's mode (COCOS_GAN_* of include/cocos_hip.h)
-GAN_MODES = {"hinge_d_real": 0, "hinge_d_fake": 1, "neg_mean": 2, "mean": 3, "ls": 4, "bce": 5}
+GAN_MODES = {m: _C["COCOS_GAN_" + m.upper()] for m in ("hinge_d_real", "hinge_d_fake", "neg_mean", "mean", "ls", "bce")}
 
 
 def _loss_chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
@@ -3962,7 +3965,7 @@ def ema_multi_update(shadows, params, mu: float) -> int:
 # K32  weight preparation for frozen-weight inference: many weights per launch   (inference.py; weight_prepare_multi.hip)
 # ------------------------------------------------------------------------------------------
 #: layout name -> COCOS_WPREP_* (include/cocos_hip.h)
-WPREP_LAYOUTS = {"conv_fwd": 0, "conv_dgrad": 1, "conv_fwd_bf16": 2, "conv_dgrad_bf16": 3, "rows": 4, "frag": 5}
+WPREP_LAYOUTS = {m: _C["COCOS_WPREP_" + m.upper()] for m in ("conv_fwd", "conv_dgrad", "conv_fwd_bf16", "conv_dgrad_bf16", "rows", "frag")}
 
 
 def weight_prepare_constants() -> dict:

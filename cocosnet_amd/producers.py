@@ -91,7 +91,7 @@ class Conv2d(nn.Conv2d):
                 # kernel-side limits (a tensor of 2 GiB or more, a grid too large for the 32-bit index arithmetic: the
                 # discriminator / VGG at very large batch or resolution) are not part of the check above: they take the
                 # framework path instead of failing the training step.  Anything else is a real error.
-                if getattr(e, "code", 0) != -2:          # COCOS_ERR_UNSUPPORTED (include/cocos_hip.h)
+                if not e.unsupported:
                     raise
         if reflect:
             input = nn.functional.pad(input, (reflect,) * 4, mode="reflect")

@@ -47,10 +47,6 @@ def vgg_preprocess_torch(x, vgg_normal_correct: bool = False):
     return (bgr - torch.Tensor(list(_VGG_MEAN_BGR)).type_as(bgr).view(1, 3, 1, 1)) * 255
 
 
-def _unsupported(e: Exception) -> bool:
-    return getattr(e, "code", 0) == -2          # COCOS_ERR_UNSUPPORTED (include/cocos_hip.h)
-
-
 class VGG19_feature_color_torchversion(nn.Module):
     """The reference's VGG19 feature extractor; input RGB in [0, 1] (in [-1, 1] with vgg_normal_correct)."""
 
@@ -88,7 +84,7 @@ class VGG19_feature_color_torchversion(nn.Module):
             try:
                 return ops.vgg_preprocess(x, bool(self.vgg_normal_correct))
             except _lib.CocosHipError as e:
-                if not _unsupported(e):
+                if not e.unsupported:
                     raise
         return vgg_preprocess_torch(x, self.vgg_normal_correct)
 
@@ -97,7 +93,7 @@ class VGG19_feature_color_torchversion(nn.Module):
             try:
                 return ops.relu(y)
             except _lib.CocosHipError as e:
-                if not _unsupported(e):
+                if not e.unsupported:
                     raise
         return F.relu(y)
 
@@ -122,7 +118,7 @@ class VGG19_feature_color_torchversion(nn.Module):
                 out = ops.relu_pool2(y, mode, keep_r)
                 return out if keep_r else (None, out)
             except _lib.CocosHipError as e:
-                if not _unsupported(e):
+                if not e.unsupported:
                     raise
         r = F.relu(y)
         return (r if keep_r else None), pool(r)

@@ -3,10 +3,12 @@ with a record against the ordinary route (OUT_TOL, the bound tests/test_gpu_pari
 import pytest
 import torch
 
+from cocosnet_amd._lib import CONSTANTS
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 OUT_TOL = 2e-4
-COCOS_ERR_INVALID, COCOS_ERR_UNSUPPORTED = -1, -2      # include/cocos_hip.h
+COCOS_ERR_INVALID, COCOS_ERR_UNSUPPORTED = CONSTANTS["COCOS_ERR_INVALID"], CONSTANTS["COCOS_ERR_UNSUPPORTED"]
 
 
 # ---- kernel level -----------------------------------------------------------------------------------------------------------------

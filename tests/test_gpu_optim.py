@@ -206,11 +206,8 @@ def _expected_launches(numels, rows=None):
 
 
 def _header_constants():
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cocos_hip.h")).read()
-    get = lambda name: int(eval(re.search(r"#define\s+" + name + r"\s+(\([^)]*\)|\d+)", src).group(1)))  # "(1 << 24)" or "64"
-    return {n: get("COCOS_OPTIM_" + n) for n in ("TABLE_ENTRIES", "TABLE_GROUPS", "CHUNK_ELEMS", "ENTRY_ELEMS")}
+    from cocosnet_amd import _lib
+    return {n: _lib.CONSTANTS["COCOS_OPTIM_" + n] for n in ("TABLE_ENTRIES", "TABLE_GROUPS", "CHUNK_ELEMS", "ENTRY_ELEMS")}
 
 
 @pytest.mark.parametrize("which", ["G", "D"])
