@@ -272,7 +272,8 @@ class NoVGGCorrespondence(NetworkBase):
     def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False):
         """Where each position matched, and how sure the match is — the hard readout of the correlation that
         `forward(..., return_corr=True)` returns as a [B,HW,HW] matrix (:305-306), without that matrix wherever the fused
-        match_kernel-1 back end runs (hot_path.correspondence_match).  Forward only.
+        match_kernel-1 back end runs, and with one HWxHW tensor (the x-box correlation T, read once) instead of two logit matrices
+        wherever the fused match_kernel-3 back end runs (hot_path.correspondence_match).  Forward only.
 
         direction="rows": per content position its best exemplar position; "cols": per exemplar position its best content position.
         Returns {match_index [B,h,w] int64 (flat position on the other side's grid), match_xy [B,2,h,w] (x, y), match_prob (the

@@ -352,6 +352,126 @@ __global__ __launch_bounds__(256, 1) void box3_sw_fwd_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// K37: match readout of the same logits — the forward kernel's T / statistics path and nothing else
+// ---------------------------------------------------------------------------------------------------------
+// Per query the row maximum of z, its key index and the row log-sum-exp (what a caller of return_corr takes with max / argmax /
+// logsumexp over the matrix), from the T the forward kernel reads: BxGeom, bx_fetch two tiles ahead, bx_logits, the transposed
+// read and the chunk ring are the forward's; there is no V tile, no P split, no MFMA and no accumulator.  LDS is the statistics
+// (<= 32 KB) plus, transposed, the four per-wave images (18 KB): two workgroups share a CU (171 / 182 VGPRs, no scratch; a bound
+// of three spills) and hide each other's T latency.
+// Per lane (c = query, h = which 16 of the tile's 32 keys) the state is the EXACT maximum of tt (a2 > 0: the argmax of tt is the
+// argmax of z), its key index (lowest among equals: keys ascend with the register index and with the tile, so only a strictly
+// larger value replaces it) and sum 2^(tt a2 - m a2), rescaled whenever m moves; the two half-waves merge once, after the loop.
+// Barriers: one after the statistics are staged; the chunk ring needs one where a chunk opens (t % BX_TCH == 0, t > 0) — behind
+// it every wave has finished reading chunk c - 1 (whose buffer chunk c + 1 is staged into during this tile) and every wave's
+// part of chunk c (staged during the first tile of chunk c - 1) is in LDS.  The forward had both from its per-tile V barrier.
+// The sum's reference r = m * a2 is STATE, formed once per move of the maximum and carried: every term is 2^(tt a2 - r) with the r in
+// the register, the rescale 2^(r_old - r_new) and the result r + log2 l use the same two numbers, so the rounding of m * a2 cancels.
+// (Forming it again per tile as `m a2 - ref` lets the compiler contract the product into an fma: exact(m a2) - round(m a2) != 0 makes
+//  alpha = 1 +- 1e-6 on EVERY tile with the same sign — measured 2e-4 on the lse at 160 tiles.)
+__device__ __forceinline__ float bx_match_ref(float m, float a2) {
+#pragma clang fp contract(off)
+    return m * a2;
+}
+
+template <bool CHUNKED>
+__global__ __launch_bounds__(256, 2) void box3_match_kernel(
+    const float* __restrict__ T, const float* __restrict__ mu_q, const float* __restrict__ a_q,
+    const float* __restrict__ nu_k, const float* __restrict__ b_k, int* __restrict__ idx_out, float* __restrict__ max_out,
+    float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char bx_smem[];
+    float* const kstat = reinterpret_cast<float*>(bx_smem);      // [b | kn][Nk] (x 2 buffers when chunked), then the XT images
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform for the compiler too: see the forward)
+    const int h = lane >> 5, c = lane & 31;
+    const int nqb = Nq / 128;
+    const int vb = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = vb / nqb, q0 = (vb % nqb) * 128;
+    const int i_lane = q0 + wave * 32 + c;
+    const float* const bk_b = b_k + (size_t)b * Nk;
+    const float* const nu_b = nu_k + (size_t)b * Nk;
+    bx_stage_stats(kstat, bk_b, nu_b, CHUNKED ? BX_KCH : Nk, CHUNKED ? BX_KCH : Nk, kc, tid);
+
+    BxGeom gm;
+    gm.t_rs = make_rsrc(T + (size_t)b * Nk * Nq, (size_t)Nk * Nq * 4);
+    gm.kstat = kstat;
+    gm.nk = CHUNKED ? BX_KCH : Nk;
+    gm.tpr = wimg / 32;
+    gm.tpr_log2 = gm.tpr == 4 ? 2 : 1;
+    gm.qblk = (q0 >> 5) + wave;
+    gm.py = gm.qblk >> gm.tpr_log2;
+    gm.himg = himg;
+    gm.nqblk = Nq >> 5;
+    gm.lane_off = (unsigned)lane * 16u;
+    gm.xt = (flags & BX_FLAG_TRANSPOSED) ? kstat + (CHUNKED ? 4 * BX_KCH : 2 * Nk) + wave * BX_XT_FLOATS : nullptr;
+
+    const float mu_p = mu_q[(size_t)b * Nq + i_lane];
+    const float a_n = a_q[(size_t)b * Nq + i_lane] * scale;      // natural-domain factor: z = tt * a_n
+    const float a2 = a_n * kLog2e;
+
+    float m_run = -INFINITY, r_run = 0.f, l_run = 0.f;      // r_run = m_run * a2 (0 while nothing was seen)
+    int i_run = 0;
+
+    const int ntiles = Nk / 32;
+    BxTile tl0, tl1;        // tiles t and t + 1 in flight, as in the forward
+    bx_fetch(tl0, gm, 0, ntiles);
+    bx_fetch(tl1, gm, 1, ntiles);
+    __syncthreads();
+
+    auto do_tile = [&](int t, BxTile& tl) __attribute__((always_inline)) {
+        if (CHUNKED && t > 0 && (t & (BX_TCH - 1)) == 0) __syncthreads();      // a chunk opens: see above
+        bx_stage_next_chunk<CHUNKED>(kstat, bk_b, nu_b, t, ntiles, kc, tid);
+        float tt[16], bq[16], kn[16];
+        bx_logits<CHUNKED>(tl, gm, t, h, mu_p, tt, bq, kn, c);
+        bx_fetch(tl, gm, t + 2, ntiles);
+        float tmax = tt[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, tt[r]);
+        if (tmax > m_run) {           // strictly: an equal value in a later tile has a higher index (a NaN never passes)
+            int at = 15;
+#pragma unroll
+            for (int r = 14; r >= 0; --r) at = tt[r] == tmax ? r : at;
+            i_run = t * 32 + 8 * (at >> 2) + 4 * h + (at & 3);      // register r = 4g + e of lane (h, c) is key 32t + 8g + 4h + e
+            const float r_new = bx_match_ref(tmax, a2);
+            l_run *= fast_exp2(r_run - r_new);                      // (the first move: l_run is 0)
+            m_run = tmax;
+            r_run = r_new;
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += fast_exp2(__builtin_fmaf(tt[r], a2, -r_run));
+        l_run += sum;
+    };
+    {
+        int t = 0;
+        for (; t + 1 < ntiles; t += 2) {
+            do_tile(t, tl0);
+            do_tile(t + 1, tl1);
+        }
+        if (t < ntiles) do_tile(t, tl0);
+    }
+
+    // ---- one merge per query with the other half-wave (executed by ALL lanes): the larger maximum, the lowest index among equals
+    {
+        const float om = swap_half(m_run), orr = swap_half(r_run), ol = swap_half(l_run);
+        const int oi = __shfl_xor(i_run, 32, 64);
+        const bool take_o = om > m_run || (om == m_run && oi < i_run);
+        const float ref = om > m_run ? orr : r_run;               // (equal maxima have equal references: a2 is the query's)
+        l_run = l_run * fast_exp2(r_run - ref) + ol * fast_exp2(orr - ref);      // (a side that saw nothing has l = 0, r = 0)
+        i_run = take_o ? oi : i_run;
+        m_run = fmaxf(m_run, om);
+        r_run = ref;
+    }
+    if (h == 0) {
+        const size_t at = (size_t)b * Nq + i_lane;
+        idx_out[at] = min(max(i_run, 0), Nk - 1);      // always a valid key position, also for non-finite input
+        max_out[at] = m_run * a_n;
+        lse_out[at] = (r_run + log2f(l_run)) * kLn2;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // K19 backward
 // ---------------------------------------------------------------------------------------------------------
 // Column sums (over queries) of two 32 x 32 accumulator images per tile — d b and d nu are sums over ALL queries of a key.
@@ -987,6 +1107,31 @@ extern "C" int cocos_box3_softmax_warp_fwd_f16x3(const float* t_blocked, const f
         default: return bx_fwd_launch<5>(COCOS_ARGS);
     }
 #undef COCOS_ARGS
+}
+
+extern "C" int cocos_box3_match_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
+                                      const float* b_k, int* idx_out, float* max_out, float* lse_out, int B, int Nq, int Nk,
+                                      int grid_h, int grid_w, float k_unfolded, float scale, int flags, cocos_stream_t stream) {
+    using namespace cocos;
+    COCOS_REQUIRE(t_blocked && mu_q && a_q && nu_k && b_k && idx_out && max_out && lse_out, COCOS_ERR_INVALID,
+                  "box3_match_f16x3: null pointer");
+    COCOS_REQUIRE((flags & ~BX_FLAG_TRANSPOSED) == 0, COCOS_ERR_INVALID, "box3_match_f16x3: flags=%d (bit 0: T transposed)", flags);
+    COCOS_REQUIRE(B >= 1 && scale > 0.f, COCOS_ERR_INVALID, "box3_match_f16x3: bad B=%d / scale", B);
+    COCOS_REQUIRE(bx_shape_ok(Nq, Nk, 1, grid_h, grid_w), COCOS_ERR_UNSUPPORTED,
+                  "box3_match_f16x3: needs a 64- or 128-wide grid with Nq == Nk == h*w, Nq %% 256 == 0 (Nq=%d Nk=%d grid %dx%d)",
+                  Nq, Nk, grid_h, grid_w);
+    COCOS_REQUIRE(aligned16(t_blocked) && aligned16(nu_k) && aligned16(b_k), COCOS_ERR_INVALID,
+                  "box3_match_f16x3: T / nu / b must be 16-byte aligned");
+    COCOS_REQUIRE((long long)B * (Nq / 128) < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "box3_match_f16x3: grid too large");
+    const bool chunked = Nk > 2 * BX_KCH;
+    const size_t smem = (size_t)(chunked ? 4 * BX_KCH : 2 * Nk) * sizeof(float) +
+                        ((flags & BX_FLAG_TRANSPOSED) ? (size_t)4 * BX_XT_FLOATS * sizeof(float) : 0);
+    auto kern = chunked ? box3_match_kernel<true> : box3_match_kernel<false>;
+    COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kern, dim3(B * (Nq / 128)), dim3(256), smem, as_stream(stream), t_blocked, mu_q, a_q, nu_k, b_k, idx_out,
+                       max_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags);
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
 }
 
 extern "C" size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk) {

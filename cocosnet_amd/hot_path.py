@@ -252,6 +252,16 @@ class _BoxedCorr:
         t = self._get("t_cols", lambda: ops.box3_corr_xbox(self.ph, self.th, None, self._raw_planes))
         return ops.box3_softmax_warp(t, nu, b, mu, a, v, self.fh, self.fw, self.kc, self.inv_t)
 
+    def match(self, rows: bool):
+        """(idx int32, max, lse) [B,N] of the rows of the logits (rows) or of their transpose (not rows): K37 on the row pass's T —
+        read transposed for the column direction, with or without a gradient sink (nothing is differentiated)."""
+        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
+        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
+        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+        if rows:
+            return ops.box3_match(t, mu, a, nu, b, self.fh, self.fw, self.kc, self.inv_t)
+        return ops.box3_match(t, nu, b, mu, a, self.fh, self.fw, self.kc, self.inv_t, transposed=True)
+
 
 def _box_sum3(x):
     """zero-padded 3x3 box SUM of a [B,1,h,w] map."""
@@ -587,8 +597,11 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1, as for correspondence_hot_path; `exemplar`: the ops.PreparedKeys
     of a prepared exemplar in place of phi_raw (None).  Routes mirror correspondence_hot_path's: where its fused match_kernel-1
     back end runs (C == 256, PONO_C, the split-precision kernels) the operand planes go to K36a and nothing HWxHW is allocated;
-    everywhere else (match_kernel 3, no PONO_C, COCOS_PRECISION=fp32, odd sizes, ops.MATCH_FUSED = False) the logits are
-    materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad()."""
+    where its fused match_kernel-3 back end runs (PONO_C, equal 64- or 128-wide grids: ops.box3_fused_ok) the one HWxHW tensor is
+    T = xbox(C) from the correlation GEMM's epilogue, which K37 reads once (the column direction reads the same T transposed; a
+    prepared exemplar brings its key planes and statistics);
+    everywhere else (other match_kernel-3 shapes, no PONO_C, COCOS_PRECISION=fp32, odd sizes, ops.MATCH_FUSED = False) the logits
+    are materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad()."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
     if (exemplar is None) == (phi_raw is None):
@@ -630,6 +643,18 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
                 kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
             idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
+        elif ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw) and ops.box3_fused_ok(B, C, fh, fw):
+            # the reference's default on the fused family's shapes: ONE HWxHW tensor (T, from the x-box GEMM's epilogue), read once
+            # by K37 — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
+            if exemplar is not None:       # the record's planes and (nu, b): the key side is not recomputed
+                th = raw(theta_raw).detach()
+                boxed = _BoxedCorr(th, th.view_as(th), inv_t, prepared_k=exemplar.box_planes(B))
+            elif isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:      # K25 / proj_unfold3_stats inside _BoxedCorr
+                boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
+            else:
+                boxed = _BoxedCorr(raw(theta_raw).detach(), raw(phi_raw).detach(), inv_t)
+            idx, mx, lse = boxed.match(rows)
+            del boxed
         else:
             th = raw(theta_raw).detach()
             ph = (exemplar.phi_raw(B) if exemplar is not None else raw(phi_raw)).detach()

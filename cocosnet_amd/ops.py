@@ -2537,6 +2537,30 @@ def box3_softmax_warp(t, mu, a, nu, b, v, h, w, k_unfolded, scale, transposed: b
                       for c0 in range(0, Cv, MAX_FUSED_CV)], dim=1)
 
 
+def box3_match(t, mu, a, nu, b, h, w, k_unfolded, scale, transposed: bool = False):
+    """(idx int32, max, lse), each [B,N]: row maximum, its (lowest) key index and the row log-sum-exp of box3_softmax_warp's logits
+    z[p,q] = scale * a_p b_q (ybox(T)[p,q] - k mu_p nu_q), with T from box3_corr_xbox — that pass without its value tensor (K37;
+    forward only: the inputs are detached and no autograd node is made).  `transposed` as for box3_softmax_warp.  Shapes outside
+    cocos_box3_fused_supported raise: materialise the logits and use row_argmax_lse."""
+    for x, name in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
+        if not x.is_cuda:
+            raise _lib.CocosHipError(f"box3_match: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    with torch.no_grad():
+        t, mu, a, nu, b = (_chk(x.detach(), f"box3_match: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
+        if mu.dim() != 2:
+            raise ValueError("box3_match: mu is [B,N]")
+        B, N = mu.shape
+        if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
+            raise ValueError("box3_match: shape mismatch")
+        idx = torch.empty((B, N), device=t.device, dtype=torch.int32)
+        mx = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        _call("box3_match", "cocos_box3_match_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+              idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale),
+              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+    return idx, mx, lse
+
+
 # ------------------------------------------------------------------------------------------
 # K12 statistics of the 3x3-unfolded vectors without unfolding   (correspondence.py:276-280, match_kernel 3)
 # ------------------------------------------------------------------------------------------

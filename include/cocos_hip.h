@@ -1045,6 +1045,17 @@ int cocos_box3_softmax_warp_fwd_f16x3(const float* t_blocked, const float* mu_q,
                                       const unsigned* v_lo_mask_dev /* nullable: as for cocos_corr_softmax_warp_fwd_f16x3 */,
                                       int B, int Nq, int Nk, int Cv, int grid_h, int grid_w, float k_unfolded, float scale,
                                       int flags, cocos_stream_t stream);
+/* K37 — the match readout (K36) of these logits: from the T of cocos_box3_corr_xbox_f16x3 and the K12 statistics, per query p
+ *         max_out[b,p] = max_q z[p,q]                  (natural units; z exactly as cocos_box3_softmax_warp_fwd_f16x3 forms it)
+ *         idx_out[b,p] = the q of that maximum, the lowest one among equals; always in [0, Nk), also for non-finite input
+ *         lse_out[b,p] = log sum_q exp z[p,q]
+ *     The forward kernel's T / statistics path without a value tensor: three blocks of T per tile, nothing else of size HWxHW,
+ *     no box-filtered logits.  Supported: exactly cocos_box3_fused_supported(Nq, Nk, 1, grid_h, grid_w) (else
+ *     COCOS_ERR_UNSUPPORTED; nothing is launched).  flags: COCOS_BOX3_T_TRANSPOSED only (the column direction on the row pass's
+ *     T: mu / a then belong to T's keys, nu / b to its queries); any other bit is COCOS_ERR_INVALID.  T, nu, b 16-byte aligned. */
+int cocos_box3_match_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                           int* idx_out, float* max_out, float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w,
+                           float k_unfolded, float scale, int flags, cocos_stream_t stream);
 size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk);
 int cocos_box3_softmax_warp_bwd_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
                                       const float* b_k, const void* vph, const void* vpl, const void* gph, const void* gpl,
