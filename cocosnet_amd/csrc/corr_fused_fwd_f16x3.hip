@@ -31,6 +31,7 @@
 //     stores (and the backward loads) its 32x32 tile as four fully contiguous 1 KB instructions instead of
 //     sixteen 4-byte-per-lane ones (the store tail of round 1 was instruction-bound, not bandwidth-bound).
 #include "common.h"
+#include <atomic>
 #include <type_traits>
 
 namespace cocos {
@@ -103,7 +104,13 @@ __device__ long long g_phase_fwd_h[8];
 // difference is taken between s * scale and a ROUNDED m * scale: at |logit| ~ 1e10 (a randomly initialised SPADE generator's
 // Attention block: theta ~ 4e5) one ulp is ~700 in the exponent — p overflowed f16 or vanished and the output was NaN.
 // Same instruction count per element; extra work only where m changes (rare) and in the training forward's logits store.
-template <int CVB, bool STORE_S, bool RAGGED, bool VLO0, bool RAWM = false, int KST = SP_KD / 16>
+//
+// QKA ("QK ahead"): the schedule of the tile loop.  false: QK(t) -> barrier -> softmax(t) -> P.V(t), the softmax running with the
+// matrix pipe idle.  true: QK(t+1) is issued right after the barrier of tile t into a second accumulator set, with the softmax of
+// tile t sliced into its MFMA gaps (see the loop header).  Same arithmetic in the same order either way: out, lse and the saved
+// logits are bit-identical.  Only the flavour the correspondence runs (not RAWM — its accumulators start at -m of the previous
+// tile's softmax — and not RAGGED) has the skewed form; the host picks the kernel (cocos_corr_fwd_f16x3_qk_ahead).
+template <int CVB, bool STORE_S, bool RAGGED, bool VLO0, bool RAWM = false, int KST = SP_KD / 16, bool QKA = false>
 __device__ __forceinline__ void corr_fwd_f16x3_body(
     const _Float16* __restrict__ qh, const _Float16* __restrict__ ql, const _Float16* __restrict__ kh,
     const _Float16* __restrict__ kl, const _Float16* __restrict__ vh, const _Float16* __restrict__ vl,
@@ -118,6 +125,7 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
     // KST = 2 / 4 / 8 instantiations (K <= 32 / 64 / 128).  (A run-time step count was tried first: 48 scalar branches per tile cost more than the MFMAs
     // they skipped — QK phase 3250 cycles per tile against 2320 without them, tools/phase_timing_attention.py.)
     static_assert(KST >= 1 && KST <= SP_KD / 16 && (RAWM || KST == SP_KD / 16), "KST < 16 belongs to the magnitude-free flavour");
+    static_assert(!QKA || (!RAWM && !RAGGED), "the QK-ahead schedule exists for the unit-norm, whole-tile flavour only");
     constexpr int CVP = CVB * 32;
     constexpr int KPLANE = SP_BK * SP_KROW;          // halfs per K plane per buffer
     constexpr int VPLANE = CVP * SP_VROW;
@@ -277,9 +285,11 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
 
     // Operand rings (A fragments from LDS): requested RA - 1 steps ahead; with four waves on the LDS pipe a
     // ds_read_b128 takes several hundred cycles to come back, far more than the 96 cycles of one step's MFMAs.
-    // The rings live ACROSS the tile loop: the first fragments of tile t+1's key tile are requested at the end of
+    // QKA = false: the rings live ACROSS the tile loop: the first fragments of tile t+1's key tile are requested at the end of
     // tile t's P.V loop, so the QK loop never starts cold (round 1 / step 1 read them right after the barrier:
     // ~450 cycles of every tile's QK phase were that bubble — profiles/r02_ablation_fwd.txt).
+    // QKA = true: QK(t+1) starts right after the barrier that makes its key tile visible, so its first fragments can only be
+    // requested there; the head of the softmax (row maximum, rescale decision) runs between the request and the first MFMA.
     constexpr int RA = 4, NS = SP_KD / 16;
     f16x8 ah[RA], al[RA];
     auto prefetch_k = [&](int buf) {
@@ -292,192 +302,238 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
     };
     prefetch_k(0);
 
-    // One barrier per tile, BETWEEN the two MFMA loops.  Key tile t+1 is committed during QK(t) and read from QK(t+1)
-    // on (and by the prefetch at the end of P.V(t)): every wave has passed this barrier in between.  Value tile t+1 is
-    // committed during P.V(t) into the buffer P.V(t-1) read: every wave finished P.V(t-1) before it reached this
-    // barrier in tile t; it is read in P.V(t+1), after the barrier of tile t+1.
+    // One barrier per tile, barrier(t), in front of softmax(t); kbuf / vbuf[i] are the two key / value buffers.
+    //
+    // QKA = false: QK(t) -> barrier(t) -> softmax(t) -> P.V(t).
+    //   key tile t+1 : written to kbuf[(t+1)&1] by the pieces in QK(t); read by QK(t+1) (and by the prefetch at the end of P.V(t)),
+    //                  after barrier(t).  The buffer held tile t-1: every wave finished QK(t-1) before it reached barrier(t-1).
+    //   value tile t+1: written to vbuf[(t+1)&1] by the pieces in P.V(t); read by P.V(t+1), after barrier(t+1).  The buffer held
+    //                  tile t-1: every wave finished P.V(t-1) before it reached barrier(t).
+    //
+    // QKA = true: QK(0) -> { barrier(t) -> [softmax(t) sliced into QK(t+1)] -> P.V(t) } for every t; the last tile has no QK.
+    //   key tile t+2 : written to kbuf[t&1] by the pieces in QK(t+1), i.e. AFTER barrier(t).  The buffer held tile t: every wave
+    //                  finished QK(t) — in iteration t-1, or in the prologue — before it reached barrier(t).  Read by the prefetch
+    //                  and QK(t+2), after barrier(t+1); the writes precede barrier(t+1) in program order.
+    //                  (Prologue: tile 0 is committed before the barrier in front of the loop, QK(0) writes tile 1 to kbuf[1],
+    //                  which nobody reads before barrier(0).)
+    //   value tile t+1: exactly as above — P.V(t) still sits between barrier(t) and barrier(t+1).
+    //   The staging registers hold key tile t+2 when QK(t+1) starts and take the loads of tile min(t+3, last): the look-ahead
+    //   clamp re-reads the last tile, and what it commits is never read (there is no QK past tile ntiles - 1).
+    //
     // VLO0 (template): only value block 0 has a non-zero lo plane (one-hot label channels are exact in f16: `v_lo_mask`,
     // cocos_f16_plane_block_mask) — the V_lo * P_hi term, its fragment reads and its staging are skipped for the other
     // blocks: same result, 8 of 30 P.V MFMAs fewer.  The kernel (below) holds both flavours of this body and picks one
     // from the mask before anything else (a choice further inside — per tile or per loop copy — cost registers: measured slower).
     const std::integral_constant<bool, VLO0> vlo0_tag{};
-    for (int t = 0; t < ntiles; ++t) {
-        const int j0 = t * SP_BK, buf = t & 1;
-        const bool ragged = RAGGED && (j0 + SP_BK > Nk);
-        _Float16* const kw = kt + (buf ^ 1) * 2 * KPLANE;
-        _Float16* const vw = vt + (buf ^ 1) * 3 * VPLANE;
-        const int jn = j0 + 2 * SP_BK;
-        // One staged piece of tile t+1 to the other LDS buffer, and its register immediately takes the load for tile
-        // t+2 — memory instructions are never issued as a burst.  i < 8: key-tile pieces (plane i & 1, chunk i >> 1),
-        // issued in the QK loop; 8 <= i < 8 + 2*CVB: value-tile pieces, issued in the P.V loop.
-        auto piece = [&](int i, auto vlo0_piece_tag) __attribute__((always_inline)) {
-            constexpr bool PLO0 = decltype(vlo0_piece_tag)::value;     // value blocks >= 1 have an all-zero lo plane: not staged
-            if (!RAGGED) {
-                const int jc = min(jn, Nk - SP_BK);       // look-ahead past the end re-reads the last tile
-                if (i < 8) {
-                    const int pl_ = i & 1, u = i >> 1;
-                    *reinterpret_cast<u32x4*>(kw + pl_ * KPLANE + k_lds[u]) = kst[pl_][u];
-                    kst[pl_][u] = buf_load_u4s(pl_ ? kl_rs : kh_rs, k_voff[u], (unsigned)jc * (unsigned)(SP_KD * 2));
-                } else if (i - 8 < 2 * CVB) {
-                    const int pl_ = (i - 8) & 1, u = (i - 8) >> 1;
-                    if (PLO0 && pl_ == 1 && u >= 1) return;
-                    const bool ones = pl_ == 0 && u == CVB - 1 && ones_thread;
-                    *reinterpret_cast<u32x2*>(vw + pl_ * VPLANE + v_lds[u]) = ones ? kOnes2 : vst[pl_][u];
-                    if (pl_ == 0) *reinterpret_cast<u32x2*>(vw + 2 * VPLANE + v_lds[u]) = ones ? kOnesS2 : unshift2(vst[0][u]);
-                    vst[pl_][u] = buf_load_u2s(pl_ ? vl_rs : vh_rs, v_voff[u], (unsigned)jc * 2u);
-                }
-                return;
-            }
+    // One staged piece of the look-ahead tile to the other LDS buffer `w`, and its register immediately takes the load for the
+    // tile at key `jn` — memory instructions are never issued as a burst.  i < 8: key-tile pieces (plane i & 1, chunk i >> 1),
+    // issued in the QK loop; 8 <= i < 8 + 2*CVB: value-tile pieces, issued in the P.V loop.
+    auto piece = [&](int i, auto vlo0_piece_tag, _Float16* const w, const int jn) __attribute__((always_inline)) {
+        constexpr bool PLO0 = decltype(vlo0_piece_tag)::value;     // value blocks >= 1 have an all-zero lo plane: not staged
+        if (!RAGGED) {
+            const int jc = min(jn, Nk - SP_BK);       // look-ahead past the end re-reads the last tile
             if (i < 8) {
                 const int pl_ = i & 1, u = i >> 1;
-                const int g = u * 256 + tid, key = g >> 5, cc = g & 31;
-                *reinterpret_cast<u32x4*>(kw + pl_ * KPLANE + key * SP_KROW + cc * 8) = kst[pl_][u];
-                kst[pl_][u] = buf_load_u4(pl_ ? kl_rs : kh_rs, (unsigned)((jn + key) * SP_KD + cc * 8) * 2u);
+                *reinterpret_cast<u32x4*>(w + pl_ * KPLANE + k_lds[u]) = kst[pl_][u];
+                kst[pl_][u] = buf_load_u4s(pl_ ? kl_rs : kh_rs, k_voff[u], (unsigned)jc * (unsigned)(SP_KD * 2));
             } else if (i - 8 < 2 * CVB) {
                 const int pl_ = (i - 8) & 1, u = (i - 8) >> 1;
                 if (PLO0 && pl_ == 1 && u >= 1) return;
-                const int g = u * 256 + tid, row = g >> 3, kq = g & 7;
-                const int slot = 16 * (kq >> 2) + 8 * (kq & 1) + 4 * ((kq >> 1) & 1);
                 const bool ones = pl_ == 0 && u == CVB - 1 && ones_thread;
-                *reinterpret_cast<u32x2*>(vw + pl_ * VPLANE + row * SP_VROW + slot) = ones ? kOnes2 : vst[pl_][u];
-                if (pl_ == 0) *reinterpret_cast<u32x2*>(vw + 2 * VPLANE + row * SP_VROW + slot) = ones ? kOnesS2 : unshift2(vst[0][u]);
-                unsigned off = (unsigned)(row * Nk + jn + 4 * kq) * 2u;
-                if (row >= Cv || jn + 4 * kq >= Nk) off = kBufOob;
-                vst[pl_][u] = buf_load_u2(pl_ ? vl_rs : vh_rs, off);
+                *reinterpret_cast<u32x2*>(w + pl_ * VPLANE + v_lds[u]) = ones ? kOnes2 : vst[pl_][u];
+                if (pl_ == 0) *reinterpret_cast<u32x2*>(w + 2 * VPLANE + v_lds[u]) = ones ? kOnesS2 : unshift2(vst[0][u]);
+                vst[pl_][u] = buf_load_u2s(pl_ ? vl_rs : vh_rs, v_voff[u], (unsigned)jc * 2u);
             }
-        };
+            return;
+        }
+        if (i < 8) {
+            const int pl_ = i & 1, u = i >> 1;
+            const int g = u * 256 + tid, key = g >> 5, cc = g & 31;
+            *reinterpret_cast<u32x4*>(w + pl_ * KPLANE + key * SP_KROW + cc * 8) = kst[pl_][u];
+            kst[pl_][u] = buf_load_u4(pl_ ? kl_rs : kh_rs, (unsigned)((jn + key) * SP_KD + cc * 8) * 2u);
+        } else if (i - 8 < 2 * CVB) {
+            const int pl_ = (i - 8) & 1, u = (i - 8) >> 1;
+            if (PLO0 && pl_ == 1 && u >= 1) return;
+            const int g = u * 256 + tid, row = g >> 3, kq = g & 7;
+            const int slot = 16 * (kq >> 2) + 8 * (kq & 1) + 4 * ((kq >> 1) & 1);
+            const bool ones = pl_ == 0 && u == CVB - 1 && ones_thread;
+            *reinterpret_cast<u32x2*>(w + pl_ * VPLANE + row * SP_VROW + slot) = ones ? kOnes2 : vst[pl_][u];
+            if (pl_ == 0) *reinterpret_cast<u32x2*>(w + 2 * VPLANE + row * SP_VROW + slot) = ones ? kOnesS2 : unshift2(vst[0][u]);
+            unsigned off = (unsigned)(row * Nk + jn + 4 * kq) * 2u;
+            if (row >= Cv || jn + 4 * kq >= Nk) off = kBufOob;
+            vst[pl_][u] = buf_load_u2(pl_ ? vl_rs : vh_rs, off);
+        }
+    };
 
-        FPH_T(tp0);
-        // ---- S^T = K_tile . Q : 16 k-steps x 3 terms; three accumulators (one per product term) used round-robin, so
-        //      that consecutive MFMAs never depend on each other and every gap can carry a filler; the key-tile pieces of
-        //      tile t+1 ride in the gaps ------------------------------------------------------------------------------
-        // QK1 (round 6): the three product terms accumulate into ONE register set — a dependent chain of v_mfma_f32_32x32x16_f16 issues at
-        // the full rate on gfx950 (tools/probes/mfma_operand_rate.hip), and the kernel is bound by its VALU instructions, not by MFMA
-        // dependencies: 32 accumulator reads and 16 packed adds fewer per tile, forward 0.311 -> 0.293 ms same box (tools/ab_libs.sh;
-        // the round-2 form is in git history).  The magnitude-free flavour keeps its two chains (they START at -m_hi / -m_lo).
-        constexpr bool QK1 = !RAWM;
-        f32x16 sa, sb, sc;
+    // ---- S^T = K_tile . Q of the key tile in kbuf[rbuf]: 16 k-steps x 3 terms, every gap between two MFMAs closed by a
+    //      sched_barrier so that it can carry a filler: the fragment reads, the key-tile pieces of the look-ahead tile (to kbuf[rbuf ^ 1],
+    //      loads from key `jn`) and whatever `gap(g)`, g = 0 .. 3*NS - 1, puts there ---------------------------------------------
+    // QK1 (round 6): the three product terms accumulate into ONE register set — a dependent chain of v_mfma_f32_32x32x16_f16 issues at
+    // the full rate on gfx950 (tools/probes/mfma_operand_rate.hip), and the kernel is bound by its VALU instructions, not by MFMA
+    // dependencies: 32 accumulator reads and 16 packed adds fewer per tile, forward 0.311 -> 0.293 ms same box (tools/ab_libs.sh;
+    // the round-2 form is in git history).  The magnitude-free flavour keeps its two chains (they START at -m_hi / -m_lo).
+    constexpr bool QK1 = !RAWM;
+    auto qk = [&](f32x16& sa, f32x16& sb, f32x16& sc, const int rbuf, const int jn, auto&& gap) __attribute__((always_inline)) {
+        const _Float16* kb = kt + rbuf * 2 * KPLANE + c * SP_KROW + h * 8;
+        _Float16* const kw = kt + (rbuf ^ 1) * 2 * KPLANE;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sa[r] = RAWM ? -m_run : 0.f; sb[r] = RAWM ? -m_lo : 0.f; sc[r] = 0.f; }
-        {
-            const _Float16* kb = kt + buf * 2 * KPLANE + c * SP_KROW + h * 8;
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int cur = s % RA;
-                const bool live = s < KST;      // (a compile-time fact after unrolling)
-                if (live) sa = mfma16h(ah[cur], qhr[s], sa);
-                if (s + RA - 1 < KST) ah[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + (s + RA - 1) * 16);
-                __builtin_amdgcn_sched_barrier(0);
-                if (live) { if (QK1) sa = mfma16h(ah[cur], qlr[s], sa); else sb = mfma16h(ah[cur], qlr[s], sb); }
-                if (s + RA - 1 < KST) al[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + KPLANE + (s + RA - 1) * 16);
-                __builtin_amdgcn_sched_barrier(0);
-                if (live) { if (QK1) sa = mfma16h(al[cur], qhr[s], sa); else sc = mfma16h(al[cur], qhr[s], sc); }
-                if ((s & 1) == 0) piece(s >> 1, std::false_type{});   // the 8 key-tile pieces, every other step
-                __builtin_amdgcn_sched_barrier(0);
-            }
+        for (int s = 0; s < NS; ++s) {
+            const int cur = s % RA;
+            const bool live = s < KST;      // (a compile-time fact after unrolling)
+            if (live) sa = mfma16h(ah[cur], qhr[s], sa);
+            if (s + RA - 1 < KST) ah[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + (s + RA - 1) * 16);
+            gap(3 * s);
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) { if (QK1) sa = mfma16h(ah[cur], qlr[s], sa); else sb = mfma16h(ah[cur], qlr[s], sb); }
+            if (s + RA - 1 < KST) al[(s + RA - 1) % RA] = *reinterpret_cast<const f16x8*>(kb + KPLANE + (s + RA - 1) * 16);
+            gap(3 * s + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (live) { if (QK1) sa = mfma16h(al[cur], qhr[s], sa); else sc = mfma16h(al[cur], qhr[s], sc); }
+            if ((s & 1) == 0) piece(s >> 1, std::false_type{}, kw, jn);   // the 8 key-tile pieces, every other step
+            gap(3 * s + 2);
+            __builtin_amdgcn_sched_barrier(0);
         }
+    };
+    auto no_filler = [](int) {};
+
+    f32x16 sa, sb, sc;       // the S accumulators whose softmax comes next (QKA: they live across the barrier)
+    // ---- one key tile.  AHEAD (compile time, QKA only): QK(t+1) is issued under softmax(t); the last tile has none -------------
+    auto tile = [&](const int t, auto ahead_tag) __attribute__((always_inline)) {
+        constexpr bool AHEAD = decltype(ahead_tag)::value;
+        const int j0 = t * SP_BK, buf = t & 1;
+        const bool ragged = RAGGED && (j0 + SP_BK > Nk);
+        _Float16* const vw = vt + (buf ^ 1) * 3 * VPLANE;
+        const int jn = j0 + 2 * SP_BK;
+
+        FPH_T(tp0);
+        if (!QKA) qk(sa, sb, sc, buf, jn, no_filler);
         FPH_T(tp1);
         __syncthreads();   // key tile t+1 visible to everyone; value buffer of tile t-1 free (see the loop header)
         FPH_T(tp2);
-        // ---- the P.V loop's first value fragments: their latency hides under the softmax arithmetic ------------------
+        if (AHEAD) prefetch_k(buf ^ 1);
+        // ---- the P.V loop's first value fragments: their latency hides under the softmax arithmetic, or (AHEAD) under the last
+        //      steps of QK(t+1), where the key ring takes no more reads --------------------------------------------------------
         constexpr int NSV = 2 * CVB;                          // P.V step i = tt * CVB + cb
         f16x8 a_h[RA], a_l[RA], a_s[RA];                      // hi, lo and hi * 2^-11 fragments of the value tile
         const _Float16* vbase = vt + buf * 3 * VPLANE + c * SP_VROW + h * 8;
-#pragma unroll
-        for (int i = 0; i < RA - 1 && i < NSV; ++i) {
+        auto vfrag_first = [&](int i) __attribute__((always_inline)) {
+            if (i >= RA - 1 || i >= NSV) return;
             a_h[i] = *reinterpret_cast<const f16x8*>(vbase + (i % CVB) * 32 * SP_VROW + (i / CVB) * 16);
             a_l[i] = *reinterpret_cast<const f16x8*>(vbase + VPLANE + (i % CVB) * 32 * SP_VROW + (i / CVB) * 16);
             a_s[i] = *reinterpret_cast<const f16x8*>(vbase + 2 * VPLANE + (i % CVB) * 32 * SP_VROW + (i / CVB) * 16);
+        };
+        if (!AHEAD) {
+#pragma unroll
+            for (int i = 0; i < RA - 1; ++i) vfrag_first(i);
         }
         // ---- online softmax (log2 domain), lazy rescale as in the fp32 kernel -------------------------
         // The row maximum is taken on the raw accumulator (scale_log2 > 0) and scaled once; the exponent is one
         // fma per element: p = 2^(s * scale_log2 - (m - kPBias)).
+        // In slices, so that they can ride in the MFMA gaps of QK(t+1): sm(-1) = the head (row maximum, rescale decision and the
+        // rare rescale of O: it needs all of S and everything else needs its m); sm(0..15) = one exp2 each, the four 1 KB logits
+        // stores with the first four; sm(16..23) = one hi/lo split of a pair of p each.  Called in this order whatever the schedule.
+        constexpr int NSM = 24;
         f32x16 s0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s0[r] = QK1 ? sa[r] : (sa[r] + sb[r]) + sc[r];
-        if (ragged) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (j0 + acc_row_base(r) + 4 * h >= Nk) s0[r] = -INFINITY;
-        }
-        float tmax = s0[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s0[r]);
-        tmax = fmaxf(tmax, swap_half(tmax));
-        if (!RAWM) tmax *= scale_log2;
-        if (RAWM ? (t == 0 || __any(tmax > thr_raw)) : __any(tmax > m_run + kSplitRescaleThr)) {
-            float alpha;
-            if (RAWM) {
-                // s0 is relative to m = m_run + m_lo already; the row's new maximum moves m by EXACTLY delta >= 0 (tile 0: to the
-                // tile's own maximum, whatever its sign): the element that sets the maximum must come out at exactly 0 — at
-                // |logit| ~ 1e9 one ulp of a single fp32 m is ~2700 in the exponent, its p would overflow f16 or vanish.  m is
-                // therefore carried as an unevaluated sum (two TwoSums per update), the accumulators of the next tiles start at
-                // -m_run (S hi.hi chain) and -m_lo (hi.lo chain), and the current tile moves by delta itself.
-                const float delta = t == 0 ? tmax : fmaxf(tmax, 0.f);
-                alpha = t == 0 ? 1.0f : fast_exp2(-delta * scale_log2);         // (tile 0: O is still zero)
-                const float u = m_lo + delta, ub = u - m_lo;
-                const float e1 = (m_lo - (u - ub)) + (delta - ub);              // TwoSum(m_lo, delta) = u + e1
-                const float hs = m_run + u, hb = hs - m_run;
-                const float e2 = (m_run - (hs - hb)) + (u - hb);                // TwoSum(m_run, u) = hs + e2
-                m_run = hs;
-                m_lo = e2 + e1;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s0[r] -= delta;
-            } else {
-                const float m_new = fmaxf(m_run, tmax);
-                alpha = fast_exp2(m_run - m_new);
-                m_run = m_new;
-            }
-            // (the pins keep the AGPR -> VGPR copies of O inside this rarely taken branch: hipcc otherwise
-            //  hoists all of them above it, i.e. into every tile).  The ones row of V makes l one of O's rows:
-            //  it is rescaled with the rest.
-#pragma unroll
-            for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
-#pragma unroll
-            for (int cb = 0; cb < CVB; ++cb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
-#pragma unroll
-            for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
-        }
-        if (STORE_S) {
-            // the wave's 32x32 tile of raw logits: four contiguous 1 KB stores (registers 4k..4k+3 of every lane)
-            const unsigned soff = (unsigned)(t * nqblk) * 4096u;
-            // RAWM: the saved logits are RELATIVE raw accumulators, s - m_tile, with m_tile (the row's running maximum when the
-            // tile was stored, hi and lo part) in mtile[b][t][0..1][query]: the backward forms s_rel + (m_tile - m_final) — exact differences.  (Absolute
-            // logits s_rel + m would be rounded at |m|: one ulp of 2^27 raw units is ~70 in the exponent at |logit| ~ 1e9, and
-            // P of the row's own maximum came back as 2^+-69.)
-            if (RAWM && mtile && h == 0 && i_lane < Nq) {
-                mtile[(((size_t)b * ntiles + t) * 2 + 0) * Nq + i_lane] = m_run;
-                mtile[(((size_t)b * ntiles + t) * 2 + 1) * Nq + i_lane] = m_lo;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                __builtin_amdgcn_raw_buffer_store_b128(
-                    __builtin_bit_cast(u32x4, f32x4{s0[4 * k], s0[4 * k + 1], s0[4 * k + 2], s0[4 * k + 3]}), lg_rs,
-                    (int)lg_lane_off, (int)(soff + (unsigned)k * 1024u), kStreamAux);
-        }
         float p[16];
-        const float nmb = RAWM ? kPBias : kPBias - m_run;
+        f16x8 ph[2], pl[2];      // P -> f16 hi/lo: registers 8t..8t+7 are the k-slots of P.V step t
+        float nmb = 0.f;
+        auto sm = [&](const int g) __attribute__((always_inline)) {
+            if (g < 0) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) p[r] = fast_exp2(__builtin_fmaf(s0[r], scale_log2, nmb));
-
-        FPH_T(tp3);
-        // P -> f16 hi/lo: registers 8t..8t+7 are the k-slots of P.V step t
-        f16x8 ph[2], pl[2];
+                for (int r = 0; r < 16; ++r) s0[r] = QK1 ? sa[r] : (sa[r] + sb[r]) + sc[r];
+                if (ragged) {
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
+                    for (int r = 0; r < 16; ++r)
+                        if (j0 + acc_row_base(r) + 4 * h >= Nk) s0[r] = -INFINITY;
+                }
+                float tmax = s0[0];
 #pragma unroll
-            for (int j = 0; j < 8; j += 2) {
+                for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s0[r]);
+                tmax = fmaxf(tmax, swap_half(tmax));
+                if (!RAWM) tmax *= scale_log2;
+                if (RAWM ? (t == 0 || __any(tmax > thr_raw)) : __any(tmax > m_run + kSplitRescaleThr)) {
+                    float alpha;
+                    if (RAWM) {
+                        // s0 is relative to m = m_run + m_lo already; the row's new maximum moves m by EXACTLY delta >= 0 (tile 0: to the
+                        // tile's own maximum, whatever its sign): the element that sets the maximum must come out at exactly 0 — at
+                        // |logit| ~ 1e9 one ulp of a single fp32 m is ~2700 in the exponent, its p would overflow f16 or vanish.  m is
+                        // therefore carried as an unevaluated sum (two TwoSums per update), the accumulators of the next tiles start at
+                        // -m_run (S hi.hi chain) and -m_lo (hi.lo chain), and the current tile moves by delta itself.
+                        const float delta = t == 0 ? tmax : fmaxf(tmax, 0.f);
+                        alpha = t == 0 ? 1.0f : fast_exp2(-delta * scale_log2);         // (tile 0: O is still zero)
+                        const float u = m_lo + delta, ub = u - m_lo;
+                        const float e1 = (m_lo - (u - ub)) + (delta - ub);              // TwoSum(m_lo, delta) = u + e1
+                        const float hs = m_run + u, hb = hs - m_run;
+                        const float e2 = (m_run - (hs - hb)) + (u - hb);                // TwoSum(m_run, u) = hs + e2
+                        m_run = hs;
+                        m_lo = e2 + e1;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) s0[r] -= delta;
+                    } else {
+                        const float m_new = fmaxf(m_run, tmax);
+                        alpha = fast_exp2(m_run - m_new);
+                        m_run = m_new;
+                    }
+                    // (the pins keep the AGPR -> VGPR copies of O inside this rarely taken branch: hipcc otherwise
+                    //  hoists all of them above it, i.e. into every tile).  The ones row of V makes l one of O's rows:
+                    //  it is rescaled with the rest.
+#pragma unroll
+                    for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
+#pragma unroll
+                    for (int cb = 0; cb < CVB; ++cb)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
+#pragma unroll
+                    for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
+                }
+                nmb = RAWM ? kPBias : kPBias - m_run;
+                return;
+            }
+            if (STORE_S && g < 4) {
+                // the wave's 32x32 tile of raw logits: four contiguous 1 KB stores (registers 4k..4k+3 of every lane)
+                const unsigned soff = (unsigned)(t * nqblk) * 4096u;
+                // RAWM: the saved logits are RELATIVE raw accumulators, s - m_tile, with m_tile (the row's running maximum when the
+                // tile was stored, hi and lo part) in mtile[b][t][0..1][query]: the backward forms s_rel + (m_tile - m_final) — exact differences.  (Absolute
+                // logits s_rel + m would be rounded at |m|: one ulp of 2^27 raw units is ~70 in the exponent at |logit| ~ 1e9, and
+                // P of the row's own maximum came back as 2^+-69.)
+                if (RAWM && g == 0 && mtile && h == 0 && i_lane < Nq) {
+                    mtile[(((size_t)b * ntiles + t) * 2 + 0) * Nq + i_lane] = m_run;
+                    mtile[(((size_t)b * ntiles + t) * 2 + 1) * Nq + i_lane] = m_lo;
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    __builtin_bit_cast(u32x4, f32x4{s0[4 * g], s0[4 * g + 1], s0[4 * g + 2], s0[4 * g + 3]}), lg_rs,
+                    (int)lg_lane_off, (int)(soff + (unsigned)g * 1024u), kStreamAux);
+            }
+            if (g < 16) {
+                p[g] = fast_exp2(__builtin_fmaf(s0[g], scale_log2, nmb));
+            } else if (g < NSM) {
+                const int tt = (g - 16) >> 2, j = ((g - 16) & 3) * 2;
                 f16x2 a, bq;
                 split_pair(p[8 * tt + j], p[8 * tt + j + 1], a, bq);
                 ph[tt][j] = a[0]; ph[tt][j + 1] = a[1];
                 pl[tt][j] = bq[0]; pl[tt][j + 1] = bq[1];
             }
+        };
+        sm(-1);
+        FPH_T(tp3);
+        f32x16 sn, snb, snc;     // (AHEAD) the S accumulators of tile t+1
+        if (AHEAD) {
+            // QK(t+1), reading kbuf[buf ^ 1] and staging tile t+2 into kbuf[buf]; one softmax slice per gap for the first half of
+            // the loop, the value fragments in the last three steps
+            qk(sn, snb, snc, buf ^ 1, j0 + 3 * SP_BK, [&](const int g) __attribute__((always_inline)) {
+                if (g < NSM) sm(g);
+                if (g % 3 == 2 && g / 3 >= NS - (RA - 1)) vfrag_first(g / 3 - (NS - (RA - 1)));
+            });
+        } else {
+#pragma unroll
+            for (int g = 0; g < NSM; ++g) sm(g);
+        }
 
         FPH_T(tp4);
         // ---- O^T += V . P : A = V tile rows (channels) with permuted keys, B = P.  Riding in the gaps: the value-tile
-        //      pieces of tile t+1 (one per step) and, in the last steps, the first key fragments of tile t+1 ----------------
+        //      pieces of tile t+1 (one per step) and (QKA = false), in the last steps, the first key fragments of tile t+1 ----------
         {
 #pragma unroll
             for (int i = 0; i < NSV; ++i) {
@@ -491,8 +547,9 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
                 o[cb] = mfma16h(a_h[cur], ph[tt], o[cb]);
                 o[cb] = mfma16h(a_s[cur], pl[tt], o[cb]);      // (2^-11 V_hi) . (2^11 P_lo)
                 if (!VLO0 || cb == 0) o[cb] = mfma16h(a_l[cur], ph[tt], o[cb]);
-                piece(8 + i, vlo0_tag);
-                if (i == NSV - 1) prefetch_k(buf ^ 1);      // (NSV = 2: both in the same step)
+                piece(8 + i, vlo0_tag, vw, jn);
+                if (!QKA && i == NSV - 1) prefetch_k(buf ^ 1);      // (NSV = 2: both in the same step)
+                if (AHEAD && i == 0) sa = sn;                       // tile t+1's accumulators become "the tile whose softmax comes next"
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -501,8 +558,16 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
 #pragma unroll
         for (int cb = 0; cb < CVB; ++cb) asm volatile("" : "+a"(o[cb]));
         FPH_T(tp5);
+        // (QKA: phase 0 is empty, phase 2 the head of the softmax, phase 3 QK(t+1) with the softmax slices in its gaps)
         FPH_ADD(0, tp0, tp1); FPH_ADD(1, tp1, tp2); FPH_ADD(2, tp2, tp3); FPH_ADD(3, tp3, tp4);
         FPH_ADD(4, tp4, tp5);
+    };
+    if (QKA) {
+        qk(sa, sb, sc, 0, 2 * SP_BK, no_filler);      // QK(0); it stages key tile 1 like QK(0) of the other schedule
+        for (int t = 0; t + 1 < ntiles; ++t) tile(t, std::true_type{});
+        tile(ntiles - 1, std::false_type{});
+    } else {
+        for (int t = 0; t < ntiles; ++t) tile(t, std::false_type{});
     }
 
     // ---- epilogue: normalise, store channel-major [B,Cv,Nq], store row LSE --------------------------
@@ -536,7 +601,8 @@ __device__ __forceinline__ void corr_fwd_f16x3_body(
 // workgroup-uniform choice is the first thing it does — data on the device (cocos_f16_plane_block_mask), no host round
 // trip, and no second launch whose workgroups only look at the mask and leave (that cost 5-8 us per call).
 // DUAL = false: no mask / a single value block — only the general flavour is compiled in.
-template <int CVB, bool STORE_S, bool RAGGED, bool DUAL>
+// QKA: the QK-ahead schedule of the tile loop (see the body); the host launches it for whole-tile key counts of the unit-norm flavour only.
+template <int CVB, bool STORE_S, bool RAGGED, bool DUAL, bool QKA>
 __global__ __launch_bounds__(256, 1) void corr_fwd_f16x3_kernel(
     const _Float16* __restrict__ qh, const _Float16* __restrict__ ql, const _Float16* __restrict__ kh,
     const _Float16* __restrict__ kl, const _Float16* __restrict__ vh, const _Float16* __restrict__ vl,
@@ -549,9 +615,11 @@ __global__ __launch_bounds__(256, 1) void corr_fwd_f16x3_kernel(
     if (q_scale_dev) scale_log2 = scale_log2 / (*q_scale_dev * *k_scale_dev);
     if constexpr (DUAL) {
         if ((__builtin_amdgcn_readfirstlane(*v_lo_mask) & ~1u) == 0u)
-            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, true>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
+            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, true, false, SP_KD / 16, QKA>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
         else
-            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
+            corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false, false, SP_KD / 16, QKA>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
+    } else if constexpr (QKA) {
+        corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false, false, SP_KD / 16, true>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, v_lo_mask, B, Nq, Nk, Cv, scale_log2, k_bstride, v_bstride);
     } else {
         if (q_scale_dev) {        // the magnitude-free flavour (host side: no lo mask together with device-side operand scales)
 #define COCOS_RAWM_BODY(KST_) corr_fwd_f16x3_body<CVB, STORE_S, RAGGED, false, true, KST_>(qh, ql, kh, kl, vh, vl, out, lse, lg, v_scale, \
@@ -570,13 +638,13 @@ __global__ __launch_bounds__(256, 1) void corr_fwd_f16x3_kernel(
     }
 }
 
-template <int CVB, bool STORE_S, bool RAGGED, bool VLO0>
+template <int CVB, bool STORE_S, bool RAGGED, bool VLO0, bool QKA>
 static int launch_f16x3_k(const _Float16* qh, const _Float16* ql, const _Float16* kh, const _Float16* kl,
                           const _Float16* vh, const _Float16* vl, float* out, float* lse, float* lg,
                           const float* v_scale, const unsigned* v_lo_mask, int B, int Nq, int Nk, int Cv, float scale_log2,
                           const float* qsd, const float* ksd, float* rowstat, float* mtile, int ksteps, size_t k_bstride, size_t v_bstride,
                           hipStream_t stream) {
-    auto kern = corr_fwd_f16x3_kernel<CVB, STORE_S, RAGGED, VLO0>;
+    auto kern = corr_fwd_f16x3_kernel<CVB, STORE_S, RAGGED, VLO0, QKA>;
     const size_t smem = (size_t)2 * (2 * SP_BK * SP_KROW + 3 * CVB * 32 * SP_VROW) * sizeof(_Float16);
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -602,14 +670,22 @@ extern "C" int cocos_debug_read_timing_fwd_f16x3(long long* host8, int reset) {
 }
 #endif
 
-template <int CVB, bool ST, bool RG, typename... A>
+template <int CVB, bool ST, bool RG, bool QKA, typename... A>
 static int cocos_go_both(const _Float16* a, const _Float16* b2, const _Float16* c2, const _Float16* d, const _Float16* e,
                          const _Float16* f, float* out, float* lse, float* lgp, const float* v_scale_dev,
                          const unsigned* v_lo_mask_dev, A... rest) {
     using namespace cocos;
     if (CVB > 1 && v_lo_mask_dev)
-        return launch_f16x3_k<CVB, ST, RG, (CVB > 1)>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, v_lo_mask_dev, rest...);
-    return launch_f16x3_k<CVB, ST, RG, false>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, nullptr, rest...);
+        return launch_f16x3_k<CVB, ST, RG, (CVB > 1), QKA>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, v_lo_mask_dev, rest...);
+    return launch_f16x3_k<CVB, ST, RG, false, QKA>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, nullptr, rest...);
+}
+
+// Process-wide choice between the two schedules of the forward's tile loop (same results bit for bit; see the body's QKA).
+static std::atomic<int> g_fwd_qk_ahead{COCOS_FWD_QK_AHEAD_DEFAULT};
+
+extern "C" int cocos_corr_fwd_f16x3_qk_ahead(int mode) {
+    if (mode == 0 || mode == 1) return g_fwd_qk_ahead.exchange(mode, std::memory_order_relaxed);
+    return g_fwd_qk_ahead.load(std::memory_order_relaxed);
 }
 
 extern "C" size_t cocos_corr_softmax_warp_saved_logits_bytes(int B, int Nq, int Nk) {
@@ -673,19 +749,21 @@ static int corr_softmax_warp_fwd_f16x3_impl(const void* qh, const void* ql, cons
                   "corr_softmax_warp_fwd_f16x3: the device-side operand scales come as a pair");
     const float scale_log2 = q_scale_dev ? inv_temperature * kLog2e : inv_temperature * kLog2e / (operand_scale * operand_scale);
     const bool ragged = (Nk % SP_BK) != 0;
+    // the schedule of the tile loop (cocos_corr_fwd_f16x3_qk_ahead): the skewed form exists for whole tiles of unit-norm operands
+    const bool qka = g_fwd_qk_ahead.load(std::memory_order_relaxed) != 0 && !ragged && !q_scale_dev;
     const size_t k_bstride = dense_kv ? (size_t)Nk * SP_KD : 0, v_bstride = dense_kv ? (size_t)Cv * Nk : 0;
     float* lgp = static_cast<float*>(saved_logits);
     const _Float16 *a = static_cast<const _Float16*>(qh), *b2 = static_cast<const _Float16*>(ql),
                    *c2 = static_cast<const _Float16*>(kh), *d = static_cast<const _Float16*>(kl),
                    *e = static_cast<const _Float16*>(vh), *f = static_cast<const _Float16*>(vl);
     // with a mask and more than one value block the kernel holds both flavours and picks one from the device-side mask
-#define COCOS_GO(CVB, ST, RG) \
-    cocos_go_both<CVB, ST, RG>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, v_lo_mask_dev, B, Nq, Nk, Cv, scale_log2, \
+#define COCOS_GO(CVB, ST, RG, QKA) \
+    cocos_go_both<CVB, ST, RG, QKA>(a, b2, c2, d, e, f, out, lse, lgp, v_scale_dev, v_lo_mask_dev, B, Nq, Nk, Cv, scale_log2, \
                                q_scale_dev, k_scale_dev, rowstat_out, mtile_out, ksteps, k_bstride, v_bstride, s)
 #define COCOS_CVB(CVB)                                                           \
     case CVB:                                                                    \
-        if (lgp) return ragged ? COCOS_GO(CVB, true, true) : COCOS_GO(CVB, true, false); \
-        return ragged ? COCOS_GO(CVB, false, true) : COCOS_GO(CVB, false, false);
+        if (lgp) return ragged ? COCOS_GO(CVB, true, true, false) : qka ? COCOS_GO(CVB, true, false, true) : COCOS_GO(CVB, true, false, false); \
+        return ragged ? COCOS_GO(CVB, false, true, false) : qka ? COCOS_GO(CVB, false, false, true) : COCOS_GO(CVB, false, false, false);
     switch (Cv / 32 + 1) {       // one more channel than Cv: the ones row (see the kernel header)
         COCOS_CVB(1) COCOS_CVB(2) COCOS_CVB(3) COCOS_CVB(4)
         default: COCOS_CVB(5)

@@ -58,6 +58,10 @@ PROJ_PRECISION = os.environ.get("COCOS_PROJ_PRECISION", "f16x3")
 # ---- COCOS_CONV, COCOS_MAX_SAVED_LOGITS_BYTES, COCOS_RECOMPUTE_CHUNK_BYTES and COCOS_LIB_PATH)
 #: K2 split kernels: test V's f16 lo plane per 32-channel block and skip all-zero blocks (exact label / mask channels)
 VALUE_LO_SKIP = True
+#: K2 split forward: True = the QK MFMAs of key tile t+1 run under the softmax arithmetic of tile t ("QK ahead", whole-tile key counts
+#: of the unit-norm flavour); False = QK, softmax, P.V of a tile in turn.  Bit-identical results (tests/test_gpu_fwd_qk_ahead.py); the
+#: default is the library's (COCOS_FWD_QK_AHEAD_DEFAULT), the selection is handed to it before every forward call
+FWD_QK_AHEAD = bool(_lib.CONSTANTS["COCOS_FWD_QK_AHEAD_DEFAULT"])
 #: K0 at the reference's own shapes (<= 416 input channels, HW % 64 == 0): y = W x and dx = W^T dy on the streaming
 #: kernel (proj_stream_f16x3.hip: weight planes resident in the accumulator file, x / y touched once), dw + db as one
 #: streaming reduction (proj_dw_f16x3.hip).  "0" = the general split GEMM everywhere (A/B, tests).
@@ -71,6 +75,11 @@ MATCH_FUSED = True
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _select_fwd_schedule():
+    """FWD_QK_AHEAD -> the library's process-wide selection (a host-side store: no launch, no device memory)"""
+    _lib.load().cocos_corr_fwd_f16x3_qk_ahead(1 if FWD_QK_AHEAD else 0)
 
 
 class KernelTimer:
@@ -461,6 +470,7 @@ class _CorrSoftmaxWarp(torch.autograd.Function):
             # ... and, with saved logits (which this flavour stores RELATIVE to the running maximum), that maximum per 32-key tile
             ctx.mtile = (torch.empty((B, (Nk + 31) // 32, 2, Nq), device=qn.device, dtype=torch.float32)
                          if (qk_scales and logits_t is not None) else None)
+            _select_fwd_schedule()
             _call("corr_softmax_warp_fwd", "cocos_corr_softmax_warp_fwd_f16x3_ex", qh.data_ptr(), ql.data_ptr(),
                   kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(), lse.data_ptr(),
                   _ptr(logits_t), v_scale.data_ptr(), _ptr(v_lomask), B, Kp, Nq, Nk, Cv, float(inv_temperature),
@@ -611,6 +621,7 @@ def _corr_bwd_recompute(ctx, qn, kn, v, out, lse, dout, dqn, dkn, dv, need_k):
         lg = torch.empty(lib.cocos_corr_softmax_warp_saved_logits_bytes(B, Nq, n) // 4, device=dev, dtype=torch.float32)
         rowstat = getattr(ctx, "rowstat", None)           # magnitude-free flavour: relative logits + their per-tile reference
         mt = torch.empty((B, (n + 31) // 32, 2, Nq), device=dev, dtype=torch.float32) if rowstat is not None else None
+        _select_fwd_schedule()
         _call("corr_softmax_warp_recompute", "cocos_corr_softmax_warp_fwd_f16x3_ex", qh.data_ptr(), ql.data_ptr(), khc.data_ptr(),
               klc.data_ptr(), vz.data_ptr(), vz.data_ptr(), o1.data_ptr(), l1.data_ptr(), lg.data_ptr(), None, None, B, Kp, Nq, n, 1,
               ctx.inv_t, SPLIT_OPERAND_SCALE, _ptr(qks[0] if qks else None), _ptr(qks[1] if qks else None), None, _ptr(mt), ka, st)
@@ -876,6 +887,7 @@ def corr_softmax_warp_shared(qh, ql, keys: PreparedKeys, values: PreparedValues,
     dense = Be == B
     out = torch.empty((B, Cv, Nq), device=qh.device, dtype=torch.float32)
     lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _select_fwd_schedule()
     _call("corr_softmax_warp_fwd", "cocos_corr_softmax_warp_fwd_f16x3_shared", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(),
           kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(), lse.data_ptr(), None, v_scale.data_ptr(), _ptr(v_lomask),
           B, K, Nq, Nk, Cv, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if dense else 0, Cv * Nk if dense else 0, _stream())

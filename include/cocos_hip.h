@@ -168,6 +168,13 @@ int cocos_corr_softmax_warp_fwd_f16x3_shared(const void* qh, const void* ql, con
                                              const unsigned* v_lo_mask_dev /* nullable */, int B, int K, int Nq, int Nk, int Cv,
                                              float inv_temperature, float operand_scale, long long k_batch_stride,
                                              long long v_batch_stride, cocos_stream_t stream);
+/* The schedule of the split-precision forward's key-tile loop, process-wide, for the three entry points above.  1 = "QK ahead": the
+ * QK MFMAs of tile t+1 are issued under the softmax arithmetic of tile t (second accumulator set); 0 = QK(t), softmax(t), P.V(t) in
+ * turn.  Same arithmetic in the same order: out, lse and saved_logits are bit-identical.  Only whole-tile key counts (Nk % 32 == 0)
+ * of the unit-norm flavour have the skewed form; every other call runs schedule 0 whatever is selected.  mode 0 / 1 selects and
+ * returns the previous selection; any other mode only returns the current one.  Launches no kernel, touches no device memory. */
+#define COCOS_FWD_QK_AHEAD_DEFAULT 1
+int cocos_corr_fwd_f16x3_qk_ahead(int mode);
 /* bit (c >> 5) of *mask_inout_dev |= (channel c of the channel-major f16 plane [B,C,N] has a non-zero element); the
  * cell must hold 0 (or an earlier partial mask) on entry; C <= 1024.  Run on the LO plane of V: value channels that
  * are exact in f16 (one-hot labels, masks) have an all-zero lo plane, and when every 32-channel block but the first

@@ -14,12 +14,18 @@ q = nrm(torch.randn(B, 256, N, device="cuda", generator=g)).requires_grad_(train
 k = nrm(0.2 * q.detach() + torch.randn(B, 256, N, device="cuda", generator=g))
 v = torch.rand(B, Cv, N, device="cuda", generator=g) * 2 - 1
 buf = (ctypes.c_longlong * 8)()
-names = ["QK", "commit+fetch", "softmax", "split P", "PV", "barrier"]
-for it in range(3):
-    ops.corr_softmax_warp(q, k, v, 100.0)
-    lib.cocos_debug_read_timing_fwd_f16x3(buf, 1)
-    t = list(buf)[:6]
-    print(" | ".join(f"{n} {x / 128:.0f}" for n, x in zip(names, t)), f"| total {sum(t) / 128:.0f} ticks/tile  (MFMA ideal: QK 1536, PV {32 * 6 * ((Cv + 31) // 32)})")
+# the forward under both schedules of its tile loop (ops.FWD_QK_AHEAD).  In turn: QK | barrier | softmax head (maximum, rescale
+# decision) | exp2 + hi/lo split | P.V.  QK ahead: QK(t+1) sits in the fourth phase with the exp2 / split slices in its gaps and the
+# first phase is empty (QK(0) runs in front of the loop; the last tile has no QK: 127 QK loops over 128 tiles).
+for ahead, names in ((False, ["QK", "barrier", "softmax head", "exp2 + split P", "PV"]),
+                     (True, ["-", "barrier", "softmax head", "QK(t+1) + exp2 + split P", "PV"])):
+    ops.FWD_QK_AHEAD = ahead
+    for it in range(3):
+        ops.corr_softmax_warp(q, k, v, 100.0)
+        lib.cocos_debug_read_timing_fwd_f16x3(buf, 1)
+        t = list(buf)[:5]
+        print(f"fwd qk_ahead={int(ahead)}: " + " | ".join(f"{n} {x / 128:.0f}" for n, x in zip(names, t)),
+              f"| total {sum(t) / 128:.0f} ticks/tile  (MFMA ideal: QK 1536, PV {32 * 6 * ((Cv + 31) // 32)})")
 
 # ---- backward (query side) ----
 q2 = q.detach().requires_grad_(True)
