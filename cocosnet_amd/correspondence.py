@@ -269,7 +269,8 @@ class NoVGGCorrespondence(NetworkBase):
         coor_out.update(res)
         return coor_out
 
-    def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False):
+    def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False, topk=1,
+              blend="topk"):
         """Where each position matched, and how sure the match is — the hard readout of the correlation that
         `forward(..., return_corr=True)` returns as a [B,HW,HW] matrix (:305-306), without that matrix wherever the fused
         match_kernel-1 back end runs, and with one HWxHW tensor (the x-box correlation T, read once) instead of two logit matrices
@@ -279,9 +280,21 @@ class NoVGGCorrespondence(NetworkBase):
         Returns {match_index [B,h,w] int64 (flat position on the other side's grid), match_xy [B,2,h,w] (x, y), match_prob (the
         match's softmax weight), match_lse} and, with `hard_warp`, warp_hard [B,3,H,W]: every content cell filled with the
         down x down patch of ref_img at its match (rows only).  `exemplar`: a record of inference.prepare_exemplar in place of
-        ref_img / ref_seg_map (both None)."""
+        ref_img / ref_seg_map (both None).
+
+        `topk` = k in 2..8 (at most the number of positions; else ValueError) returns the k best candidates per position, best
+        first, ties in favour of the lower index: match_index [B,k,h,w], match_xy [B,k,2,h,w], match_prob [B,k,h,w] (each
+        candidate's softmax weight among ALL positions), match_lse [B,h,w]; nothing HWxHW on the fused match_kernel-1 route,
+        the logits matrix read once everywhere else.  With `hard_warp` also warp_hard (the rank-0 gather, as with topk = 1)
+        and warp_topk [B,3,H,W]: per cell the blend of the k candidates' full-resolution patches, weighted by `blend` =
+        "topk" (softmax over the k logits: the weights sum to 1 — a k-sparse softmax) or "full" (match_prob itself: the true
+        softmax weights, which sum to <= 1).  An unknown `blend` raises ValueError."""
         if direction not in ("rows", "cols"):
             raise ValueError(f"match: direction {direction!r}: expected 'rows' or 'cols'")
+        if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
+            raise ValueError(f"match: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+        if blend not in ("topk", "full"):
+            raise ValueError(f"match: blend {blend!r}: expected 'topk' or 'full'")
         if hard_warp and direction == "cols":
             raise ValueError("match: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
         keys = phi_raw = None
@@ -300,11 +313,16 @@ class NoVGGCorrespondence(NetworkBase):
             if keys is None and phi_raw is None:      # (real_img: project() reads it for the training-time featpair term only)
                 theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
             cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction)
+            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk)
             out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse}
-            if hard_warp:
+            if hard_warp and topk == 1:
                 fh, fw = m.index.shape[1:]
                 out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+            elif hard_warp:
+                fh, fw = m.index.shape[2:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)
+                weights = torch.softmax(m.logit, dim=1) if blend == "topk" else m.prob
+                out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
         return out
 
 

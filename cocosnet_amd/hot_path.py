@@ -589,7 +589,26 @@ class MatchReadout:
         return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=1)
 
 
-def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows"):
+@dataclass
+class TopkMatchReadout:
+    """The k best candidates of every position (correspondence_match with topk = k > 1), best first — logit descending and, among
+    bitwise-equal logits, the lower index first: `index` [B,k,fh,fw] int64 the flat positions y * gw + x on the other side's
+    [gh, gw] grid (pairwise distinct per position for finite input), `logit` [B,k,fh,fw] their logits (cosine / temperature),
+    `prob` = exp(logit - lse) their softmax weights (they sum to <= 1 over k), `lse` [B,fh,fw] the log-sum-exp of ALL of the
+    position's logits.  Rank 0 is what MatchReadout holds."""
+    index: torch.Tensor
+    prob: torch.Tensor
+    logit: torch.Tensor
+    lse: torch.Tensor
+    grid: tuple = None      # (gh, gw) of the side the indices point into; None = the same as index.shape[2:]
+
+    def xy(self):
+        """[B,k,2,fh,fw] int64: (x, y) of every candidate on the other side's grid — index = y * gw + x"""
+        gw = (self.grid or tuple(self.index.shape[2:]))[1]
+        return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=2)
+
+
+def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows", topk=1):
     """The hard readout of the correlation of correspondence.py:272-304: argmax, maximum and log-sum-exp of every row of the scaled
     matrix f / temperature that forward(return_corr=True) returns (:305-306) — `direction="rows"`: per CONTENT position over the
     exemplar positions; "cols": per EXEMPLAR position over the content positions (the rows of f^T).  Returns a MatchReadout.
@@ -601,15 +620,23 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     T = xbox(C) from the correlation GEMM's epilogue, which K37 reads once (the column direction reads the same T transposed; a
     prepared exemplar brings its key planes and statistics);
     everywhere else (other match_kernel-3 shapes, no PONO_C, COCOS_PRECISION=fp32, odd sizes, ops.MATCH_FUSED = False) the logits
-    are materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad()."""
+    are materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad().
+
+    `topk` = k > 1 (at most ops.MATCH_TOPK_MAX and the number of positions asked about, else ValueError) returns a TopkMatchReadout:
+    the k best candidates per position.  The fused match_kernel-1 route then runs K39a (ops.corr_topk_ok(k); still nothing HWxHW);
+    every other route, the fused match_kernel-3 one included (K37's reader of T finds one maximum), materialises its logits and
+    reads them in one sweep with K39b."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
+        raise ValueError(f"correspondence_match: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
     if (exemplar is None) == (phi_raw is None):
         raise ValueError("correspondence_match: pass phi_raw or a prepared exemplar in its place (not both)")
     B, C, fh, fw = theta_raw.shape
     N = fh * fw
     mk, inv_t = cfg.match_kernel, 1.0 / temperature
     rows = direction == "rows"
+    k = topk
     if exemplar is not None:
         exemplar.check(B)
         if exemplar.shape[1:] != theta_raw.shape[1:]:
@@ -619,10 +646,13 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
     Nk = gh * gw
     raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
+    if k > (Nk if rows else N):
+        raise ValueError(f"correspondence_match: topk={k} exceeds the {Nk if rows else N} positions each row of direction={direction!r} ranges over")
     with torch.no_grad():
         if not _hip_fp32(theta_raw):
             raise ops._lib.CocosHipError("correspondence_match: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
-        fused = (ops.MATCH_FUSED and mk == 1 and C == ops.FUSED_K and cfg.PONO_C and ops.corr_split_ok(B, C, N, Nk, 1, False))
+        fused = (ops.MATCH_FUSED and mk == 1 and C == ops.FUSED_K and cfg.PONO_C and ops.corr_split_ok(B, C, N, Nk, 1, False)
+                 and (k == 1 or ops.corr_topk_ok(k)))
         if fused and exemplar is not None:
             # the query side as _attention_with_exemplar makes it; the record's key planes are read in place
             if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
@@ -630,10 +660,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             else:
                 qh, ql, _ = ops.center_l2norm_planes_fwd(_flat(raw(theta_raw)), 1)
             if rows:
-                idx, mx, lse = ops.corr_match_shared(qh, ql, exemplar, inv_t)
+                idx, mx, lse = ops.corr_match_shared(qh, ql, exemplar, inv_t) if k == 1 else ops.corr_topk_shared(qh, ql, exemplar, inv_t, k)
             else:       # the exemplar's positions ask: B different key sets (the contents), so the record's planes are needed per sample
                 kh, kl, _ = exemplar.split_planes(B)
-                idx, mx, lse = ops._corr_match_planes(kh, kl, qh, ql, inv_t)
+                idx, mx, lse = ops._corr_match_planes(kh, kl, qh, ql, inv_t) if k == 1 else ops._corr_topk_planes(kh, kl, qh, ql, inv_t, k)
         elif fused:
             planes = ops.OperandPlanes()
             if (isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
@@ -642,8 +672,11 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             else:
                 qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
                 kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
-            idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
-        elif ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw) and ops.box3_fused_ok(B, C, fh, fw):
+            if k == 1:
+                idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
+            else:
+                idx, mx, lse = ops.corr_topk(qn, kn, inv_t, k, planes) if rows else ops.corr_topk(kn, qn, inv_t, k, planes)
+        elif k == 1 and ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw) and ops.box3_fused_ok(B, C, fh, fw):
             # the reference's default on the fused family's shapes: ONE HWxHW tensor (T, from the x-box GEMM's epilogue), read once
             # by K37 — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
             if exemplar is not None:       # the record's planes and (nu, b): the key side is not recomputed
@@ -662,9 +695,15 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 f = _box3_logits(th, ph, inv_t, transposed=not rows)
             else:   # f^T is the same matrix with the operands exchanged (centring and normalisation are per tensor)
                 f = _scaled_logits(th, ph, cfg, inv_t, False, 1) if rows else _scaled_logits(ph, th, cfg, inv_t, False, 1)
-            idx, mx, lse = ops.row_argmax_lse(f)
+            idx, mx, lse = ops.row_argmax_lse(f) if k == 1 else ops.row_topk_lse(f, k)
             del f
         own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
         shape = (B,) + own
+        if k > 1:      # the [B,N,k] kernel outputs (tiny) with the rank in front of the grid
+            rank_first = lambda t: t.reshape(shape + (k,)).permute(0, 3, 1, 2).contiguous()
+            lse = lse.reshape(shape)
+            val = rank_first(mx)
+            return TopkMatchReadout(index=rank_first(idx.to(torch.int64)), prob=torch.exp(val - lse.unsqueeze(1)), logit=val, lse=lse,
+                                    grid=other)
         return MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
                             max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)

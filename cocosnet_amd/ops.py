@@ -978,7 +978,113 @@ def gather_patches(img: torch.Tensor, idx: torch.Tensor, h: int, w: int, down: i
 
 
 # ------------------------------------------------------------------------------------------
-# K3  materialised correlation          (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
+# K39  top-k match readout: the k best candidates per position and the row log-sum-exp   (:304-307 + the caller's topk / logsumexp)
+# ------------------------------------------------------------------------------------------
+#: the largest k of the readout (COCOS_MATCH_TOPK_MAX of cocos_hip.h)
+MATCH_TOPK_MAX = _lib.CONSTANTS["COCOS_MATCH_TOPK_MAX"]
+
+
+def _check_topk(name: str, k, Nk: int) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MATCH_TOPK_MAX or k > Nk:
+        raise ValueError(f"{name}: k={k!r}: expected an integer in 1..{MATCH_TOPK_MAX} that does not exceed the {Nk} keys")
+    return k
+
+
+def corr_topk_ok(k: int) -> bool:
+    """K39a ships a fused instantiation that serves k candidates (one ships only with zero scratch at two waves per SIMD and when it
+    beats materialise + row_topk_lse at the benchmark shape: DESIGN.md 3.24); above it the readout materialises (K39b)."""
+    return 1 <= k <= _lib.load().cocos_corr_topk_max_k()
+
+
+def _corr_topk_planes(qh, ql, kh, kl, inv_temperature: float, k: int):
+    """K39a on operand planes (as _corr_match_planes) -> (idx int32 [B,Nq,k], val [B,Nq,k], lse [B,Nq])."""
+    for t in (qh, ql, kh, kl):
+        if not t.is_cuda:
+            raise _lib.CocosHipError("corr_topk: expected CUDA/HIP operand planes; the correspondence hot path has no CPU fallback")
+        if t.dtype != torch.float16 or not t.is_contiguous():
+            raise TypeError("corr_topk: operand planes are contiguous float16 tensors")
+    B, Nq, K = qh.shape
+    Be, Nk = kh.shape[0], kh.shape[1]
+    if Be not in (B, 1) or kh.shape[2] != K or ql.shape != qh.shape or kl.shape != kh.shape:
+        raise ValueError(f"corr_topk: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)}")
+    k = _check_topk("corr_topk", k, Nk)
+    idx = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
+    val = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
+    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("corr_topk", "cocos_corr_topk_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
+          val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if Be == B else 0,
+          _stream())
+    return idx, val, lse
+
+
+def corr_topk(qn, kn, inv_temperature: float, k: int, planes: OperandPlanes | None = None):
+    """(idx int32 [B,Nq,k], val [B,Nq,k], lse [B,Nq]): per query the k largest logits <qn[b,:,i], kn[b,:,j]> * inv_temperature, in
+    descending order (the lower j first among bitwise-equal logits), their j, and the row log-sum-exp (K39a; forward only).  Rank 0
+    and lse are corr_match's outputs bit for bit.  Operands as corr_match.  1 <= k <= MATCH_TOPK_MAX, k <= Nk (ValueError); a k that
+    corr_topk_ok refuses and the shapes corr_match refuses raise: materialise and use row_topk_lse."""
+    for t, name in ((qn, "qn"), (kn, "kn")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"corr_topk: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if planes is None:
+        planes = OperandPlanes()
+    with torch.no_grad():
+        qn, kn = (t if planes.has(t) else _chk(t.detach(), "corr_topk") for t in (qn, kn))
+        return _corr_topk_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
+                                 inv_temperature, k)
+
+
+def corr_topk_shared(qh, ql, keys: PreparedKeys, inv_temperature: float, k: int):
+    """corr_topk with the key planes of a prepared exemplar read in place (as corr_match_shared)."""
+    kh, kl, _ = keys.split_planes()
+    with torch.no_grad():
+        return _corr_topk_planes(qh, ql, kh, kl, inv_temperature, k)
+
+
+def row_topk_lse(f: torch.Tensor, k: int):
+    """(idx int32 [..., k], val [..., k], lse [...]) of the rows of a materialised logit matrix f [..., Nk] in one sweep (K39b):
+    torch.topk(f, k, -1) with the lower index first among equal values, and torch.logsumexp(f, -1).  Rank 0 and lse are
+    row_argmax_lse's outputs bit for bit.  Any Nk >= k, 1 <= k <= MATCH_TOPK_MAX (ValueError).  Forward only."""
+    f = _chk(f.detach(), "row_topk_lse: f")
+    if f.dim() < 2 or f.numel() == 0:
+        raise ValueError(f"row_topk_lse: expected a non-empty [..., Nq, Nk] tensor, got {tuple(f.shape)}")
+    Nk, Nq = f.shape[-1], f.shape[-2]
+    k = _check_topk("row_topk_lse", k, Nk)
+    lead = f.shape[:-1]
+    B = f.numel() // (Nq * Nk)
+    idx = torch.empty(lead + (k,), device=f.device, dtype=torch.int32)
+    val = torch.empty(lead + (k,), device=f.device, dtype=torch.float32)
+    lse = torch.empty(lead, device=f.device, dtype=torch.float32)
+    _call("row_topk_lse", "cocos_row_topk_lse", f.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, Nq, Nk, k, _stream())
+    return idx, val, lse
+
+
+def gather_blend_patches(img: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, h: int, w_grid: int, down: int):
+    """The k-sparse warp (K39c): out [B,C,H,W] whose cell (y, x) of the h x w_grid grid is sum_r w[b,r,y,x] * (the down x down patch of
+    img at the cell idx[b,r,y,x]), accumulated in fp32 in the order r = 0, 1, ... — with k = 1 and w = 1 gather_patches bit for bit.
+    img [Be,C,H,W] fp32 with H == h*down, W == w_grid*down and Be == B or 1; idx [B,k,h,w_grid] (or [B,k,h*w_grid]), any integer
+    type (values outside [0, h*w_grid) are clamped into it); w fp32 of idx's shape; 1 <= k <= MATCH_TOPK_MAX."""
+    img = _chk(img.detach(), "gather_blend_patches: img")
+    if not idx.is_cuda:
+        raise _lib.CocosHipError("gather_blend_patches: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise TypeError(f"gather_blend_patches: idx must be an integer tensor, got {idx.dtype}")
+    w = _chk(w.detach(), "gather_blend_patches: w")
+    Be, C, H, W = img.shape
+    B = idx.shape[0]
+    k = idx.shape[1] if idx.dim() >= 3 else 0
+    if ((H, W) != (h * down, w_grid * down) or not 1 <= k <= MATCH_TOPK_MAX or idx.numel() != B * k * h * w_grid
+            or w.numel() != idx.numel() or w.shape[:2] != idx.shape[:2] or Be not in (B, 1)):
+        raise ValueError(f"gather_blend_patches: img{tuple(img.shape)} idx{tuple(idx.shape)} w{tuple(w.shape)} do not fit k <= "
+                         f"{MATCH_TOPK_MAX} candidates on a {h}x{w_grid} grid with down={down}")
+    idx = idx.reshape(B, k, h * w_grid).to(torch.int32).contiguous()
+    out = torch.empty((B, C, H, W), device=img.device, dtype=torch.float32)
+    _call("gather_blend_patches", "cocos_gather_blend_patches", img.data_ptr(), idx.data_ptr(), w.data_ptr(), out.data_ptr(), B, C, H, W,
+          int(down), k, C * H * W if Be == B else 0, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# K3  materialised correlation         (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
 # ------------------------------------------------------------------------------------------
 class _CorrMaterialize(torch.autograd.Function):
     @staticmethod

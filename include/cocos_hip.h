@@ -1210,6 +1210,35 @@ int cocos_row_argmax_lse(const float* logits, int* idx, float* max, float* lse, 
 int cocos_gather_patches(const float* img, const int* idx, float* out, int B, int C, int H, int W, int down,
                          long long img_batch_stride, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K39 top-k match readout: per position the k best candidates instead of the one — what a caller of the reference's
+ *     forward(return_corr=True) takes with topk / logsumexp over the returned [B,HW,HW] matrix (correspondence.py:291, :304-307).
+ *     Order (all three): logit descending and, among bitwise-equal logits, key index ascending.  The k indices of a row are
+ *     pairwise distinct for finite input; for non-finite input they are clamped into [0, Nk) as K36 does and may repeat.
+ *     1 <= k <= COCOS_MATCH_TOPK_MAX and k <= Nk, else COCOS_ERR_INVALID before any launch.
+ *   cocos_corr_topk_f16x3 (K39a, corr_topk_f16x3.hip): operands, arithmetic and limits of cocos_corr_match_f16x3;
+ *         idx [B,Nq,k] int32, val [B,Nq,k] (the logits, natural units), lse [B,Nq].
+ *       idx[..,0], val[..,0] and lse are cocos_corr_match_f16x3's three outputs bit for bit.  Nothing Nq x Nk reaches memory.
+ *       k above cocos_corr_topk_max_k() (the largest fused instantiation that ships), K != 256, Nk % 4 != 0: COCOS_ERR_UNSUPPORTED
+ *       (use cocos_row_topk_lse).
+ *   cocos_row_topk_lse (K39b, row_topk_lse.hip): the same from a materialised matrix logits [B,Nq,Nk] in one sweep; val holds
+ *       elements of the row, bit for bit; idx[..,0], val[..,0], lse are cocos_row_argmax_lse's outputs bit for bit.  Any Nq >= 1,
+ *       any Nk >= k.
+ *   cocos_gather_blend_patches (K39c, gather_blend_patches.hip): the k-sparse warp at full resolution,
+ *         out[b,c,y down+dy,x down+dx] = sum_r w[b,r,y,x] img[b_e,c,(j_r / wg) down+dy,(j_r % wg) down+dx],  j_r = idx[b,r,y,x],
+ *       hg = H / down, wg = W / down; idx [B,k,hg,wg] int32 (clamped into [0, hg wg)), w [B,k,hg,wg] fp32, img / out /
+ *       img_batch_stride as cocos_gather_patches.  fp32, fixed order: acc = w_0 p_0, then acc = fma(w_r, p_r, acc), r = 1 .. k-1;
+ *       k = 1 with w = 1 is cocos_gather_patches bit for bit.
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_MATCH_TOPK_MAX 8
+int cocos_corr_topk_max_k(void);
+int cocos_corr_topk_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out, float* val_out,
+                          float* lse_out, int B, int K, int Nq, int Nk, int k, float inv_temperature, float operand_scale,
+                          long long k_batch_stride, cocos_stream_t stream);
+int cocos_row_topk_lse(const float* logits, int* idx, float* val, float* lse, int B, int Nq, int Nk, int k, cocos_stream_t stream);
+int cocos_gather_blend_patches(const float* img, const int* idx, const float* w, float* out, int B, int C, int H, int W, int down,
+                               int k, long long img_batch_stride, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
