@@ -65,8 +65,6 @@ HIP_SOURCES = [
     "weight_prepare_multi.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
-    "corr_match_f16x3.hip",
-    "row_argmax_lse.hip",
     "gather_patches.hip",
     "corr_topk_f16x3.hip",
     "row_topk_lse.hip",

@@ -1,18 +1,23 @@
-// K39a: top-k match readout of the split-precision correlation — per query the k largest logits, their key indices and the row
+// K36a / K39a: match readout of the split-precision correlation — per query the k largest logits, their key indices and the row
 // log-sum-exp, without a value tensor and without anything HWxHW in HBM (correspondence.py:291, :304-307 followed by the caller's
-// topk / logsumexp over the returned matrix).
+// max / argmax or topk / logsumexp over the returned matrix).  One kernel template, K = 1, 2, 4, 8 candidates per lane: K = 1 is the
+// hard match (cocos_corr_match_f16x3), the same instantiation serves cocos_corr_topk_f16x3 at k = 1.
 //
-// Tiling, staging, QK arithmetic and accumulation order are corr_match_f16x3.hip's (K36a), statement for statement: 8 waves = 128
-// queries per workgroup, waves w and w + 4 own the same 32 queries and take the even / the odd 32-key tile of each 64-key stage, the
-// three terms hi.hi, hi.lo, lo.hi go into one fp32 accumulator in the forward kernel's order.  The logits are the forward's bit for
-// bit, and rank 0, its logit and the lse are K36a's outputs bit for bit.
+// Operands and QK arithmetic are those of corr_fused_fwd_f16x3.hip: position-major f16 hi/lo planes [B,N,256] of unit-norm
+// columns x operand_scale, S^T (32 keys x 32 queries) = K_tile . Q on v_mfma_f32_32x32x16_f16 with the three terms hi.hi, hi.lo,
+// lo.hi accumulated into one fp32 register set in the same order: the logits are the forward's logits bit for bit.
 //
-// What is different: beside the (m, l) pair of the online log-sum-exp a lane keeps a sorted list of K (logit, key) pairs
-// (topk_list.h); m is the list's head.  A lane meets its keys in ascending index, so a strict compare keeps the lower index among
-// equal logits.  A tile's values are offered to the list only when the tile maximum exceeds the list's tail, and then only the
-// elements that exceed it are inserted.  The four partial lists of a query (two half-waves x two wave groups) are merged ONCE after
-// the last stage, comparing (logit, index): cross-lane for the half-waves, through LDS (free after the loop's last barrier) for the
-// wave groups — 128 x (2K + 2) words.  Padded keys are -inf and never enter a list.
+// What is different from the forward: no V tile, no P split, no O accumulators — 16 accumulator registers instead of up to 96, 33 KB
+// of LDS per key tile instead of up to 72.  The room goes into a second wave per SIMD: a workgroup is 8 waves = 128 queries; waves w
+// and w + 4 own the SAME 32 queries and take the even / the odd 32-key tile of each 64-key stage, so while one wave of a SIMD runs
+// its max / exp arithmetic the other one has the matrix pipe.
+//
+// Per lane (lane & 31 = query, lane >> 5 = which 16 of the tile's 32 keys) the state is the (m, l) pair of the online log-sum-exp and
+// a sorted list of K (logit, key) pairs (topk_list.h); m is the list's head.  A lane meets its keys in ascending index, so a strict
+// compare keeps the lower index among equal logits.  A tile's values are offered to the list only when the tile maximum exceeds the
+// list's tail, and then only the elements that exceed it are inserted.  The four partial states of a query (two half-waves x two wave
+// groups) are merged ONCE after the last stage, comparing (logit, index): cross-lane for the half-waves, through LDS (free after the
+// loop's last barrier) for the wave groups — 128 x (2K + 2) words.  Padded keys are -inf and never enter a list.
 #include "common.h"
 #include "topk_list.h"
 
@@ -29,14 +34,14 @@ constexpr int CT_THREADS = 512;
 constexpr int CT_PLANE = CT_STAGE * CT_KROW;                         // halfs per plane per stage
 constexpr size_t CT_SMEM = (size_t)2 * 2 * CT_PLANE * sizeof(_Float16);   // [2 stages][hi|lo]: 135168 B
 
-// ref(m) = m * scale_log2, 0 while m is -inf (nothing seen): the reference of the sum of exponentials, as in K36a
+// ref(m) = m * scale_log2, 0 while m is -inf (nothing seen): the reference of the sum of exponentials
 __device__ __forceinline__ float topk_ref(float m, float scale_log2) { return m == -INFINITY ? 0.f : m * scale_log2; }
 
-// (m, l) <- merged with (bm, bl): K36a's match_merge without the index (the lists carry it).  The lse has to come out with K36a's
-// bits, so the two merges spell out, operation by operation, what hipcc makes of K36a's one `l * fa + bl * fb` at its two call
-// sites (contraction is switched off here; every fused multiply-add is written as one): after the half-wave exchange both
-// products are rounded before the add, after the LDS exchange bl * fb is fused into the rounded l * fa and the own exponent is
-// the rounded product m * scale_log2 minus the reference.  tests/test_gpu_match_topk.py holds the two kernels to equal bits.
+// (m, l) <- merged with (bm, bl): the larger maximum becomes the common reference and both sums are brought to it (the lists carry
+// the indices).  These two functions DEFINE the rounding of the lse, for every K: contraction is switched off and every fused
+// multiply-add is written as one, so no compiler heuristic has a say.  After the half-wave exchange both products are rounded
+// before the add; after the LDS exchange bl * fb is fused into the rounded l * fa and the own exponent is the rounded product
+// m * scale_log2 minus the reference.
 __device__ __forceinline__ void topk_merge_sum_halves(float& m, float& l, float bm, float bl, float scale_log2) {
 #pragma clang fp contract(off)
     const float mm = fmaxf(m, bm);
@@ -70,7 +75,9 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform for the compiler too (see K36a)
+    // wave-uniform by construction, but only a readfirstlane makes that a fact for the compiler (anything derived from threadIdx
+    // is divergent to it: branches on `grp` would be lane-masked and its LDS offsets per-lane arithmetic)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;                        // 0: even tiles, 1: odd tiles
     const int h = lane >> 5, c = lane & 31;
 
@@ -174,9 +181,17 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
         for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sa[r]);
         const float m_old = best.head();
         if (tmax > best.tail()) {     // strictly: an equal value in a later tile has a higher index and stays behind
+            if constexpr (K == 1) {   // one slot takes the tile maximum at its lowest row: 15 compare / selects where 16 insertions
+                int at = acc_row_base(15);      // cost 48 (most tiles come here: one of a wave's 64 lanes suffices) — 0.5 % of the kernel
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (sa[r] > best.tail()) best.push_ascending(sa[r], j0 + acc_row_base(r) + 4 * h);
+                for (int r = 14; r >= 0; --r) at = sa[r] == tmax ? acc_row_base(r) : at;
+                best.v[0] = tmax;
+                best.i[0] = j0 + at + 4 * h;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (sa[r] > best.tail()) best.push_ascending(sa[r], j0 + acc_row_base(r) + 4 * h);
+            }
         }
         const float m_new = fmaxf(m_old, tmax);              // = best.head()
         const float ref = topk_ref(m_new, scale_log2);
@@ -248,33 +263,55 @@ static int launch_corr_topk(const void* qh, const void* ql, const void* kh, cons
 // the largest k a shipped instantiation serves (an instantiation ships only with zero scratch at two waves per SIMD)
 constexpr int CT_MAX_K = 8;
 
+// what both entry points ask of their arguments; `name` is the entry's prefix in the messages, `fallback` the one-sweep reader of
+// a materialised matrix that takes the shapes this kernel does not
+static int check_corr_readout(const char* name, const char* fallback, const void* qh, const void* ql, const void* kh, const void* kl,
+                              const void* idx_out, const void* val_out, const void* lse_out, int B, int K, int Nq, int Nk, int k,
+                              float inv_temperature, float operand_scale, long long k_batch_stride) {
+    COCOS_REQUIRE(qh && ql && kh && kl && idx_out && val_out && lse_out, COCOS_ERR_INVALID, "%s: null pointer", name);
+    COCOS_REQUIRE(B >= 1 && Nq >= 1 && Nk >= 1 && operand_scale > 0.f && inv_temperature > 0.f, COCOS_ERR_INVALID,
+                  "%s: bad dims B=%d Nq=%d Nk=%d", name, B, Nq, Nk);
+    COCOS_REQUIRE(k >= 1 && k <= COCOS_MATCH_TOPK_MAX && k <= Nk, COCOS_ERR_INVALID, "%s: k=%d: expected 1 <= k <= min(%d, Nk=%d)", name,
+                  k, COCOS_MATCH_TOPK_MAX, Nk);
+    COCOS_REQUIRE(K == CT_KD, COCOS_ERR_UNSUPPORTED, "%s: needs K == 256 (got %d)", name, K);
+    COCOS_REQUIRE(Nk % 4 == 0, COCOS_ERR_UNSUPPORTED, "%s: Nk=%d must be a multiple of 4 (use %s)", name, Nk, fallback);
+    COCOS_REQUIRE(k <= CT_MAX_K, COCOS_ERR_UNSUPPORTED, "%s: k=%d: no fused instantiation above %d (use %s)", name, k, CT_MAX_K, fallback);
+    COCOS_REQUIRE((size_t)K * Nq * 2 < 0x7fffffffull && (size_t)K * ((size_t)Nk + 2 * CT_STAGE) * 2 < 0x7fffffffull,
+                  COCOS_ERR_UNSUPPORTED, "%s: per-sample tensor exceeds 2 GiB", name);
+    COCOS_REQUIRE(k_batch_stride == 0 || k_batch_stride == (long long)Nk * K, COCOS_ERR_INVALID,
+                  "%s: k_batch_stride %lld: expected 0 (one key set for all samples) or the dense %lld", name, k_batch_stride,
+                  (long long)Nk * K);
+    for (const void* p : {qh, ql, kh, kl})
+        COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: q/k planes must be 16-byte aligned", name);
+    COCOS_REQUIRE((long long)B * ((Nq + CT_BQ - 1) / CT_BQ) < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "%s: grid too large", name);
+    return COCOS_OK;
+}
+
 }  // namespace cocos
 
 extern "C" int cocos_corr_topk_max_k(void) { return cocos::CT_MAX_K; }
+
+// idx_out / max_out [B,Nq] is the same memory as the [B,Nq,1] of the K = 1 instantiation
+extern "C" int cocos_corr_match_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out,
+                                      float* max_out, float* lse_out, int B, int K, int Nq, int Nk, float inv_temperature,
+                                      float operand_scale, long long k_batch_stride, cocos_stream_t stream) {
+    using namespace cocos;
+    if (const int rc = check_corr_readout("corr_match_f16x3", "cocos_row_argmax_lse", qh, ql, kh, kl, idx_out, max_out, lse_out, B, K, Nq,
+                                          Nk, 1, inv_temperature, operand_scale, k_batch_stride))
+        return rc;
+    return launch_corr_topk<1>(qh, ql, kh, kl, idx_out, max_out, lse_out, B, Nq, Nk, 1, inv_temperature, operand_scale, k_batch_stride, stream);
+}
 
 extern "C" int cocos_corr_topk_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out, float* val_out,
                                      float* lse_out, int B, int K, int Nq, int Nk, int k, float inv_temperature,
                                      float operand_scale, long long k_batch_stride, cocos_stream_t stream) {
     using namespace cocos;
-    COCOS_REQUIRE(qh && ql && kh && kl && idx_out && val_out && lse_out, COCOS_ERR_INVALID, "corr_topk_f16x3: null pointer");
-    COCOS_REQUIRE(B >= 1 && Nq >= 1 && Nk >= 1 && operand_scale > 0.f && inv_temperature > 0.f, COCOS_ERR_INVALID,
-                  "corr_topk_f16x3: bad dims B=%d Nq=%d Nk=%d", B, Nq, Nk);
-    COCOS_REQUIRE(k >= 1 && k <= COCOS_MATCH_TOPK_MAX && k <= Nk, COCOS_ERR_INVALID,
-                  "corr_topk_f16x3: k=%d: expected 1 <= k <= min(%d, Nk=%d)", k, COCOS_MATCH_TOPK_MAX, Nk);
-    COCOS_REQUIRE(K == CT_KD, COCOS_ERR_UNSUPPORTED, "corr_topk_f16x3: needs K == 256 (got %d)", K);
-    COCOS_REQUIRE(Nk % 4 == 0, COCOS_ERR_UNSUPPORTED, "corr_topk_f16x3: Nk=%d must be a multiple of 4 (use cocos_row_topk_lse)", Nk);
-    COCOS_REQUIRE(k <= CT_MAX_K, COCOS_ERR_UNSUPPORTED, "corr_topk_f16x3: k=%d: no fused instantiation above %d (use cocos_row_topk_lse)",
-                  k, CT_MAX_K);
-    COCOS_REQUIRE((size_t)K * Nq * 2 < 0x7fffffffull && (size_t)K * ((size_t)Nk + 2 * CT_STAGE) * 2 < 0x7fffffffull,
-                  COCOS_ERR_UNSUPPORTED, "corr_topk_f16x3: per-sample tensor exceeds 2 GiB");
-    COCOS_REQUIRE(k_batch_stride == 0 || k_batch_stride == (long long)Nk * K, COCOS_ERR_INVALID,
-                  "corr_topk_f16x3: k_batch_stride %lld: expected 0 (one key set for all samples) or the dense %lld",
-                  k_batch_stride, (long long)Nk * K);
-    for (const void* p : {qh, ql, kh, kl})
-        COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "corr_topk_f16x3: q/k planes must be 16-byte aligned");
-    const int nqb = (Nq + CT_BQ - 1) / CT_BQ;
-    COCOS_REQUIRE((long long)B * nqb < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "corr_topk_f16x3: grid too large");
-    if (k <= 2)
+    if (const int rc = check_corr_readout("corr_topk_f16x3", "cocos_row_topk_lse", qh, ql, kh, kl, idx_out, val_out, lse_out, B, K, Nq, Nk,
+                                          k, inv_temperature, operand_scale, k_batch_stride))
+        return rc;
+    if (k == 1)
+        return launch_corr_topk<1>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride, stream);
+    if (k == 2)
         return launch_corr_topk<2>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride, stream);
     if (k <= 4)
         return launch_corr_topk<4>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride, stream);

@@ -897,23 +897,29 @@ def corr_softmax_warp_shared(qh, ql, keys: PreparedKeys, values: PreparedValues,
 # ------------------------------------------------------------------------------------------
 # K36  match readout: row maximum, its index and the row log-sum-exp   (correspondence.py:291,:304-307 + the caller's max / argmax)
 # ------------------------------------------------------------------------------------------
-def _corr_match_planes(qh, ql, kh, kl, inv_temperature: float):
-    """K36a on operand planes: qh, ql [B,Nq,256], kh, kl [B or 1,Nk,256] (1: every sample reads the one key set, batch stride 0)
-    -> (idx int32, max, lse), each [B,Nq]."""
+def _readout_planes(name: str, qh, ql, kh, kl):
+    """what K36a and K39a ask of their operand planes -> (B, K, Nq, Nk, key batch stride: 0 = one key set for all samples)"""
     for t in (qh, ql, kh, kl):
         if not t.is_cuda:
-            raise _lib.CocosHipError("corr_match: expected CUDA/HIP operand planes; the correspondence hot path has no CPU fallback")
+            raise _lib.CocosHipError(f"{name}: expected CUDA/HIP operand planes; the correspondence hot path has no CPU fallback")
         if t.dtype != torch.float16 or not t.is_contiguous():
-            raise TypeError("corr_match: operand planes are contiguous float16 tensors")
+            raise TypeError(f"{name}: operand planes are contiguous float16 tensors")
     B, Nq, K = qh.shape
     Be, Nk = kh.shape[0], kh.shape[1]
     if Be not in (B, 1) or kh.shape[2] != K or ql.shape != qh.shape or kl.shape != kh.shape:
-        raise ValueError(f"corr_match: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)}")
+        raise ValueError(f"{name}: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)}")
+    return B, K, Nq, Nk, Nk * K if Be == B else 0
+
+
+def _corr_match_planes(qh, ql, kh, kl, inv_temperature: float):
+    """K36a on operand planes: qh, ql [B,Nq,256], kh, kl [B or 1,Nk,256] (1: every sample reads the one key set, batch stride 0)
+    -> (idx int32, max, lse), each [B,Nq]."""
+    B, K, Nq, Nk, k_stride = _readout_planes("corr_match", qh, ql, kh, kl)
     idx = torch.empty((B, Nq), device=qh.device, dtype=torch.int32)
     mx = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
     lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
     _call("corr_match", "cocos_corr_match_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
-          mx.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if Be == B else 0, _stream())
+          mx.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, k_stride, _stream())
     return idx, mx, lse
 
 
@@ -941,15 +947,19 @@ def corr_match_shared(qh, ql, keys: PreparedKeys, inv_temperature: float):
         return _corr_match_planes(qh, ql, kh, kl, inv_temperature)
 
 
+def _readout_rows(name: str, f: torch.Tensor):
+    """what K36b and K39b ask of a logit matrix -> (f, its leading shape, B, Nq, Nk)"""
+    f = _chk(f.detach(), f"{name}: f")
+    if f.dim() < 2 or f.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [..., Nq, Nk] tensor, got {tuple(f.shape)}")
+    Nk, Nq = f.shape[-1], f.shape[-2]
+    return f, f.shape[:-1], f.numel() // (Nq * Nk), Nq, Nk
+
+
 def row_argmax_lse(f: torch.Tensor):
     """(idx int32, max, lse), each f.shape[:-1], of the rows of a materialised logit matrix f [..., Nk] in one sweep (K36b):
     torch.max(f, -1) (the lowest index among equal maxima) and torch.logsumexp(f, -1).  Forward only."""
-    f = _chk(f.detach(), "row_argmax_lse: f")
-    if f.dim() < 2 or f.numel() == 0:
-        raise ValueError(f"row_argmax_lse: expected a non-empty [..., Nq, Nk] tensor, got {tuple(f.shape)}")
-    Nk, Nq = f.shape[-1], f.shape[-2]
-    lead = f.shape[:-1]
-    B = f.numel() // (Nq * Nk)
+    f, lead, B, Nq, Nk = _readout_rows("row_argmax_lse", f)
     idx = torch.empty(lead, device=f.device, dtype=torch.int32)
     mx = torch.empty(lead, device=f.device, dtype=torch.float32)
     lse = torch.empty(lead, device=f.device, dtype=torch.float32)
@@ -998,22 +1008,13 @@ def corr_topk_ok(k: int) -> bool:
 
 def _corr_topk_planes(qh, ql, kh, kl, inv_temperature: float, k: int):
     """K39a on operand planes (as _corr_match_planes) -> (idx int32 [B,Nq,k], val [B,Nq,k], lse [B,Nq])."""
-    for t in (qh, ql, kh, kl):
-        if not t.is_cuda:
-            raise _lib.CocosHipError("corr_topk: expected CUDA/HIP operand planes; the correspondence hot path has no CPU fallback")
-        if t.dtype != torch.float16 or not t.is_contiguous():
-            raise TypeError("corr_topk: operand planes are contiguous float16 tensors")
-    B, Nq, K = qh.shape
-    Be, Nk = kh.shape[0], kh.shape[1]
-    if Be not in (B, 1) or kh.shape[2] != K or ql.shape != qh.shape or kl.shape != kh.shape:
-        raise ValueError(f"corr_topk: shape mismatch q{tuple(qh.shape)} k{tuple(kh.shape)}")
+    B, K, Nq, Nk, k_stride = _readout_planes("corr_topk", qh, ql, kh, kl)
     k = _check_topk("corr_topk", k, Nk)
     idx = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
     val = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
     lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
     _call("corr_topk", "cocos_corr_topk_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
-          val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature), SPLIT_OPERAND_SCALE, Nk * K if Be == B else 0,
-          _stream())
+          val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature), SPLIT_OPERAND_SCALE, k_stride, _stream())
     return idx, val, lse
 
 
@@ -1044,13 +1045,8 @@ def row_topk_lse(f: torch.Tensor, k: int):
     """(idx int32 [..., k], val [..., k], lse [...]) of the rows of a materialised logit matrix f [..., Nk] in one sweep (K39b):
     torch.topk(f, k, -1) with the lower index first among equal values, and torch.logsumexp(f, -1).  Rank 0 and lse are
     row_argmax_lse's outputs bit for bit.  Any Nk >= k, 1 <= k <= MATCH_TOPK_MAX (ValueError).  Forward only."""
-    f = _chk(f.detach(), "row_topk_lse: f")
-    if f.dim() < 2 or f.numel() == 0:
-        raise ValueError(f"row_topk_lse: expected a non-empty [..., Nq, Nk] tensor, got {tuple(f.shape)}")
-    Nk, Nq = f.shape[-1], f.shape[-2]
+    f, lead, B, Nq, Nk = _readout_rows("row_topk_lse", f)
     k = _check_topk("row_topk_lse", k, Nk)
-    lead = f.shape[:-1]
-    B = f.numel() // (Nq * Nk)
     idx = torch.empty(lead + (k,), device=f.device, dtype=torch.int32)
     val = torch.empty(lead + (k,), device=f.device, dtype=torch.float32)
     lse = torch.empty(lead, device=f.device, dtype=torch.float32)

@@ -1185,7 +1185,7 @@ int cocos_label_conv3x3_bwd(const int* index, const float* dy, const float* y_sa
  * K36 match readout: where each content position matched in the exemplar, and how sure the match is — what a caller of the
  *     reference's forward(return_corr=True) takes with max / argmax over the returned [B,HW,HW] matrix
  *     (correspondence.py:291, :304-307).
- *   cocos_corr_match_f16x3 (K36a, corr_match_f16x3.hip): from the operand planes of cocos_corr_softmax_warp_fwd_f16x3
+ *   cocos_corr_match_f16x3 (K36a, corr_topk_f16x3.hip at K = 1): from the operand planes of cocos_corr_softmax_warp_fwd_f16x3
  *       (qh,ql [B,Nq,256], kh,kl [B,Nk,256]: position-major f16 hi / lo planes of unit-norm columns x operand_scale) and with
  *       that kernel's QK arithmetic (three f16 MFMA terms, fp32 accumulate, same order: the same logits), per query i
  *         max_out[b,i] = max_j inv_temperature <q_i, k_j>            (natural units)
@@ -1194,7 +1194,7 @@ int cocos_label_conv3x3_bwd(const int* index, const float* dy, const float* y_sa
  *       Nothing Nq x Nk reaches memory.  k_batch_stride (halfs): Nk * 256, or 0 = every sample reads the ONE key set at kh, kl
  *       (a prepared exemplar); anything else is COCOS_ERR_INVALID.  Supported: K == 256, Nk % 4 == 0, any Nq >= 1
  *       (otherwise COCOS_ERR_UNSUPPORTED; nothing is launched).  Planes 16-byte aligned.
- *   cocos_row_argmax_lse (K36b, row_argmax_lse.hip): the same three results from a materialised matrix logits [B,Nq,Nk] in one
+ *   cocos_row_argmax_lse (K36b, row_topk_lse.hip at K = 1): the same three results from a materialised matrix logits [B,Nq,Nk] in one
  *       sweep (16-byte loads when Nk % 4 == 0 and the base is 16-byte aligned): max is an element of the row, bit for bit;
  *       same tie and range rules.  Any Nq, Nk >= 1.  For every route that holds its logits in memory anyway.
  *   cocos_gather_patches (K36c, gather_patches.hip): the hard warp at full resolution, a bitwise copy:
@@ -1216,12 +1216,12 @@ int cocos_gather_patches(const float* img, const int* idx, float* out, int B, in
  *     Order (all three): logit descending and, among bitwise-equal logits, key index ascending.  The k indices of a row are
  *     pairwise distinct for finite input; for non-finite input they are clamped into [0, Nk) as K36 does and may repeat.
  *     1 <= k <= COCOS_MATCH_TOPK_MAX and k <= Nk, else COCOS_ERR_INVALID before any launch.
- *   cocos_corr_topk_f16x3 (K39a, corr_topk_f16x3.hip): operands, arithmetic and limits of cocos_corr_match_f16x3;
+ *   cocos_corr_topk_f16x3 (K39a, corr_topk_f16x3.hip, K = 1, 2, 4, 8): operands, arithmetic and limits of cocos_corr_match_f16x3;
  *         idx [B,Nq,k] int32, val [B,Nq,k] (the logits, natural units), lse [B,Nq].
  *       idx[..,0], val[..,0] and lse are cocos_corr_match_f16x3's three outputs bit for bit.  Nothing Nq x Nk reaches memory.
  *       k above cocos_corr_topk_max_k() (the largest fused instantiation that ships), K != 256, Nk % 4 != 0: COCOS_ERR_UNSUPPORTED
  *       (use cocos_row_topk_lse).
- *   cocos_row_topk_lse (K39b, row_topk_lse.hip): the same from a materialised matrix logits [B,Nq,Nk] in one sweep; val holds
+ *   cocos_row_topk_lse (K39b, row_topk_lse.hip, K = 1, 2, 4, 8): the same from a materialised matrix logits [B,Nq,Nk] in one sweep; val holds
  *       elements of the row, bit for bit; idx[..,0], val[..,0], lse are cocos_row_argmax_lse's outputs bit for bit.  Any Nq >= 1,
  *       any Nk >= k.
  *   cocos_gather_blend_patches (K39c, gather_blend_patches.hip): the k-sparse warp at full resolution,

@@ -22,7 +22,7 @@ from test_gpu_match import B, DEV, FP32_EPS, INV_T, TOL, _arbiter, _case, _gathe
 
 pytestmark = pytest.mark.gpu
 SHAPES = tm.SHAPES + [(36, 8)]      # (36, 8): k = 8 = Nk, every key is returned
-KS = [2, 3, 4, 8]
+KS = [1, 2, 3, 4, 8]
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -54,23 +54,23 @@ def _peak(fn):
 
 
 def register_table():
-    """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of corr_topk_f16x3.hip and corr_match_f16x3.hip from hipcc's
-    kernel-resource-usage remarks (device code only, a few seconds); None without hipcc"""
+    """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of every instantiation in corr_topk_f16x3.hip (K = 1 is K36a) from
+    hipcc's kernel-resource-usage remarks (device code only, a few seconds); None without hipcc"""
     from cocosnet_amd import build
     hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
     if hipcc is None:
         return None
     rows = []
     with tempfile.TemporaryDirectory(prefix="cocos_k39_") as tmp:
-        for unit in ("corr_match_f16x3.hip", "corr_topk_f16x3.hip"):
-            cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                   os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-            text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-            for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-                get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-                k = re.search(r"kernelILi(\d+)E", name)
-                rows.append((f"K39a K = {k.group(1)}" if k else "K36a", get(r" VGPRs"), get("AGPRs"), get("ScratchSize"), get("Occupancy")))
-    return rows
+        unit = "corr_topk_f16x3.hip"
+        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
+        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
+        for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
+            get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
+            k = int(re.search(r"kernelILi(\d+)E", name).group(1))
+            rows.append((k, get(r" VGPRs"), get("AGPRs"), get("ScratchSize"), get("Occupancy")))
+    return [("K36a (K = 1)" if k == 1 else f"K39a K = {k}", *rest) for k, *rest in sorted(rows)]
 
 
 def main():
