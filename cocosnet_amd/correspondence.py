@@ -285,7 +285,7 @@ class NoVGGCorrespondence(NetworkBase):
         `topk` = k in 2..8 (at most the number of positions; else ValueError) returns the k best candidates per position, best
         first, ties in favour of the lower index: match_index [B,k,h,w], match_xy [B,k,2,h,w], match_prob [B,k,h,w] (each
         candidate's softmax weight among ALL positions), match_lse [B,h,w]; nothing HWxHW on the fused match_kernel-1 route,
-        the logits matrix read once everywhere else.  With `hard_warp` also warp_hard (the rank-0 gather, as with topk = 1)
+        the one T = xbox(C) read once on the fused match_kernel-3 route (K41), the logits matrix read once everywhere else.  With `hard_warp` also warp_hard (the rank-0 gather, as with topk = 1)
         and warp_topk [B,3,H,W]: per cell the blend of the k candidates' full-resolution patches, weighted by `blend` =
         "topk" (softmax over the k logits: the weights sum to 1 — a k-sparse softmax) or "full" (match_prob itself: the true
         softmax weights, which sum to <= 1).  An unknown `blend` raises ValueError."""

@@ -20,6 +20,7 @@
 // mu / a (queries) and nu / b (keys) are the statistics of the unfolded, centred vectors (K12, unfold3_stats.hip):
 // mean over the 9*256 entries and 1 / (norm + eps).  kc = 2304.
 #include "box3_common.h"
+#include "topk_list.h"
 
 namespace cocos {
 
@@ -374,11 +375,34 @@ __device__ __forceinline__ float bx_match_ref(float m, float a2) {
     return m * a2;
 }
 
-template <bool CHUNKED>
-__global__ __launch_bounds__(256, 2) void box3_match_kernel(
+// K41: the K best candidates per query from the same T — one kernel template, K = 1, 2, 4, 8 candidates per lane.  K = 1 is K37 as it
+// was (cocos_box3_match_f16x3: every K = 1 statement below is K37's, in K37's order, and the compiler's resource report for the two
+// K = 1 instantiations is unchanged: 171 / 182 VGPRs, no scratch); K = 2, 4, 8 serve cocos_box3_topk_f16x3, a request for k running the
+// next instantiation up and writing k columns.
+// K > 1: next to (m_run, r_run, l_run) a lane keeps a sorted list of K (tt, key) pairs (topk_list.h) whose head is m_run.  A lane meets
+// its keys in ascending index (register r = 4g + e of lane (h, c) in tile t is key 32t + 8g + 4h + e), so push_ascending's strict
+// compare keeps the lower index in front among equals; a tile is offered only when its maximum exceeds the list's tail, and inside that
+// branch only the elements that exceed the tail are inserted.  The log-sum-exp does not know about the list: its statements are the
+// K = 1 ones (the rescale on a move of the head, bx_match_ref, the 16-term sum, the half-wave merge), so idx[..,0], val[..,0] and lse
+// are K37's bits.  After the loop the other half-wave's list arrives through from_lane_xor(32) and merge (all lanes execute both).
+// ORDER of the k candidates of a query: tt descending and, among bitwise-equal tt, the lower key index first.  val = tt * a_n with the
+// query's a_n > 0 is therefore non-increasing; two unequal tt that round to the same val keep their tt order (their indices need not
+// ascend).  For finite input the k indices are pairwise distinct (the two half-waves hold disjoint keys); for non-finite input they are
+// clamped into [0, Nk) and may repeat (a NaN never enters a list: an empty slot is (-inf, key 0)).
+// l e + ol oe of the half-wave merge with BOTH products rounded before the addition — what K37's build has always computed (two
+// multiplies and an add).  Left to the compiler either product may be fused into the addition, and it chooses per instantiation:
+// measured, the K > 1 kernels then differed from K = 1 in the last bit of the lse of about 1 % of the queries of a 64 x 64 grid.
+__device__ __forceinline__ float bx_match_sum2(float l, float e, float ol, float oe) {
+#pragma clang fp contract(off)
+    const float x = l * e, y = ol * oe;
+    return x + y;
+}
+
+template <int K, bool CHUNKED>
+__global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const float* __restrict__ T, const float* __restrict__ mu_q, const float* __restrict__ a_q,
     const float* __restrict__ nu_k, const float* __restrict__ b_k, int* __restrict__ idx_out, float* __restrict__ max_out,
-    float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags) {
+    float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags, int k_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char bx_smem[];
     float* const kstat = reinterpret_cast<float*>(bx_smem);      // [b | kn][Nk] (x 2 buffers when chunked), then the XT images
 
@@ -411,7 +435,9 @@ __global__ __launch_bounds__(256, 2) void box3_match_kernel(
     const float a2 = a_n * kLog2e;
 
     float m_run = -INFINITY, r_run = 0.f, l_run = 0.f;      // r_run = m_run * a2 (0 while nothing was seen)
-    int i_run = 0;
+    int i_run = 0;                // K == 1
+    TopkList<K> best;             // K > 1: tt values; best.head() == m_run
+    best.clear();
 
     const int ntiles = Nk / 32;
     BxTile tl0, tl1;        // tiles t and t + 1 in flight, as in the forward
@@ -428,11 +454,20 @@ __global__ __launch_bounds__(256, 2) void box3_match_kernel(
         float tmax = tt[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, tt[r]);
-        if (tmax > m_run) {           // strictly: an equal value in a later tile has a higher index (a NaN never passes)
-            int at = 15;
+        if constexpr (K > 1) {
+            if (tmax > best.tail()) {     // strictly: an equal value in a later tile has a higher index and stays behind
 #pragma unroll
-            for (int r = 14; r >= 0; --r) at = tt[r] == tmax ? r : at;
-            i_run = t * 32 + 8 * (at >> 2) + 4 * h + (at & 3);      // register r = 4g + e of lane (h, c) is key 32t + 8g + 4h + e
+                for (int r = 0; r < 16; ++r)
+                    if (tt[r] > best.tail()) best.push_ascending(tt[r], t * 32 + 8 * (r >> 2) + 4 * h + (r & 3));
+            }
+        }
+        if (tmax > m_run) {           // strictly: an equal value in a later tile has a higher index (a NaN never passes)
+            if constexpr (K == 1) {
+                int at = 15;
+#pragma unroll
+                for (int r = 14; r >= 0; --r) at = tt[r] == tmax ? r : at;
+                i_run = t * 32 + 8 * (at >> 2) + 4 * h + (at & 3);      // register r = 4g + e of lane (h, c) is key 32t + 8g + 4h + e
+            }
             const float r_new = bx_match_ref(tmax, a2);
             l_run *= fast_exp2(r_run - r_new);                      // (the first move: l_run is 0)
             m_run = tmax;
@@ -458,15 +493,26 @@ __global__ __launch_bounds__(256, 2) void box3_match_kernel(
         const int oi = __shfl_xor(i_run, 32, 64);
         const bool take_o = om > m_run || (om == m_run && oi < i_run);
         const float ref = om > m_run ? orr : r_run;               // (equal maxima have equal references: a2 is the query's)
-        l_run = l_run * fast_exp2(r_run - ref) + ol * fast_exp2(orr - ref);      // (a side that saw nothing has l = 0, r = 0)
+        l_run = bx_match_sum2(l_run, fast_exp2(r_run - ref), ol, fast_exp2(orr - ref));      // (a side that saw nothing has l = 0, r = 0)
         i_run = take_o ? oi : i_run;
         m_run = fmaxf(m_run, om);
         r_run = ref;
+        if constexpr (K > 1) best.merge(best.from_lane_xor(32));      // the same rule per rank: topk_before
     }
     if (h == 0) {
         const size_t at = (size_t)b * Nq + i_lane;
-        idx_out[at] = min(max(i_run, 0), Nk - 1);      // always a valid key position, also for non-finite input
-        max_out[at] = m_run * a_n;
+        if constexpr (K == 1) {
+            idx_out[at] = min(max(i_run, 0), Nk - 1);      // always a valid key position, also for non-finite input
+            max_out[at] = m_run * a_n;
+        } else {
+#pragma unroll
+            for (int p = 0; p < K; ++p) {
+                if (p < k_out) {
+                    idx_out[at * k_out + p] = min(max(best.i[p], 0), Nk - 1);
+                    max_out[at * k_out + p] = best.v[p] * a_n;
+                }
+            }
+        }
         lse_out[at] = (r_run + log2f(l_run)) * kLn2;
     }
 }
@@ -1071,6 +1117,45 @@ static bool bx_shape_ok(int Nq, int Nk, int Cv, int himg, int wimg) {
            Cv >= 1 && Cv <= 160 && (size_t)Nq * Nk * 4 < 0x7fffffffull;
 }
 
+// the largest K of box3_topk_kernel that ships: every instantiation has zero scratch at __launch_bounds__(256, 2) and the route beats
+// materialise + cocos_row_topk_lse at both benchmark shapes
+constexpr int BX_TOPK_MAX_K = 8;
+
+// what both readout entry points ask of their arguments; `name` is the entry's prefix in the messages
+static int check_box3_readout(const char* name, const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
+                              const float* b_k, const void* idx_out, const void* val_out, const void* lse_out, int B, int Nq, int Nk,
+                              int grid_h, int grid_w, float scale, int k, int flags) {
+    COCOS_REQUIRE(t_blocked && mu_q && a_q && nu_k && b_k && idx_out && val_out && lse_out, COCOS_ERR_INVALID, "%s: null pointer", name);
+    COCOS_REQUIRE((flags & ~BX_FLAG_TRANSPOSED) == 0, COCOS_ERR_INVALID, "%s: flags=%d (bit 0: T transposed)", name, flags);
+    COCOS_REQUIRE(B >= 1 && scale > 0.f, COCOS_ERR_INVALID, "%s: bad B=%d / scale", name, B);
+    COCOS_REQUIRE(k >= 1 && k <= COCOS_MATCH_TOPK_MAX && k <= Nk, COCOS_ERR_INVALID, "%s: k=%d: expected 1 <= k <= min(%d, Nk=%d)", name,
+                  k, COCOS_MATCH_TOPK_MAX, Nk);
+    COCOS_REQUIRE(bx_shape_ok(Nq, Nk, 1, grid_h, grid_w), COCOS_ERR_UNSUPPORTED,
+                  "%s: needs a 64- or 128-wide grid with Nq == Nk == h*w, Nq %% 256 == 0 (Nq=%d Nk=%d grid %dx%d)", name, Nq, Nk, grid_h,
+                  grid_w);
+    COCOS_REQUIRE(k <= BX_TOPK_MAX_K, COCOS_ERR_UNSUPPORTED, "%s: k=%d: no instantiation above %d (use cocos_row_topk_lse)", name, k,
+                  BX_TOPK_MAX_K);
+    COCOS_REQUIRE(aligned16(t_blocked) && aligned16(nu_k) && aligned16(b_k), COCOS_ERR_INVALID, "%s: T / nu / b must be 16-byte aligned",
+                  name);
+    COCOS_REQUIRE((long long)B * (Nq / 128) < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "%s: grid too large", name);
+    return COCOS_OK;
+}
+
+template <int K>
+static int launch_box3_readout(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                               int* idx_out, float* val_out, float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w,
+                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream) {
+    const bool chunked = Nk > 2 * BX_KCH;
+    const size_t smem = (size_t)(chunked ? 4 * BX_KCH : 2 * Nk) * sizeof(float) +
+                        ((flags & BX_FLAG_TRANSPOSED) ? (size_t)4 * BX_XT_FLOATS * sizeof(float) : 0);
+    auto kern = chunked ? box3_topk_kernel<K, true> : box3_topk_kernel<K, false>;
+    COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kern, dim3(B * (Nq / 128)), dim3(256), smem, as_stream(stream), t_blocked, mu_q, a_q, nu_k, b_k, idx_out,
+                       val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags, k);
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
+
 }  // namespace cocos
 
 extern "C" int cocos_box3_fused_supported(int Nq, int Nk, int Cv, int grid_h, int grid_w) {
@@ -1109,29 +1194,33 @@ extern "C" int cocos_box3_softmax_warp_fwd_f16x3(const float* t_blocked, const f
 #undef COCOS_ARGS
 }
 
+// idx_out / max_out [B,Nq] is the same memory as the [B,Nq,1] of the K = 1 instantiation
 extern "C" int cocos_box3_match_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
                                       const float* b_k, int* idx_out, float* max_out, float* lse_out, int B, int Nq, int Nk,
                                       int grid_h, int grid_w, float k_unfolded, float scale, int flags, cocos_stream_t stream) {
     using namespace cocos;
-    COCOS_REQUIRE(t_blocked && mu_q && a_q && nu_k && b_k && idx_out && max_out && lse_out, COCOS_ERR_INVALID,
-                  "box3_match_f16x3: null pointer");
-    COCOS_REQUIRE((flags & ~BX_FLAG_TRANSPOSED) == 0, COCOS_ERR_INVALID, "box3_match_f16x3: flags=%d (bit 0: T transposed)", flags);
-    COCOS_REQUIRE(B >= 1 && scale > 0.f, COCOS_ERR_INVALID, "box3_match_f16x3: bad B=%d / scale", B);
-    COCOS_REQUIRE(bx_shape_ok(Nq, Nk, 1, grid_h, grid_w), COCOS_ERR_UNSUPPORTED,
-                  "box3_match_f16x3: needs a 64- or 128-wide grid with Nq == Nk == h*w, Nq %% 256 == 0 (Nq=%d Nk=%d grid %dx%d)",
-                  Nq, Nk, grid_h, grid_w);
-    COCOS_REQUIRE(aligned16(t_blocked) && aligned16(nu_k) && aligned16(b_k), COCOS_ERR_INVALID,
-                  "box3_match_f16x3: T / nu / b must be 16-byte aligned");
-    COCOS_REQUIRE((long long)B * (Nq / 128) < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "box3_match_f16x3: grid too large");
-    const bool chunked = Nk > 2 * BX_KCH;
-    const size_t smem = (size_t)(chunked ? 4 * BX_KCH : 2 * Nk) * sizeof(float) +
-                        ((flags & BX_FLAG_TRANSPOSED) ? (size_t)4 * BX_XT_FLOATS * sizeof(float) : 0);
-    auto kern = chunked ? box3_match_kernel<true> : box3_match_kernel<false>;
-    COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kern, dim3(B * (Nq / 128)), dim3(256), smem, as_stream(stream), t_blocked, mu_q, a_q, nu_k, b_k, idx_out,
-                       max_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags);
-    COCOS_HIP_CHECK(hipGetLastError());
-    return COCOS_OK;
+    if (const int rc = check_box3_readout("box3_match_f16x3", t_blocked, mu_q, a_q, nu_k, b_k, idx_out, max_out, lse_out, B, Nq, Nk, grid_h,
+                                          grid_w, scale, 1, flags))
+        return rc;
+    return launch_box3_readout<1>(t_blocked, mu_q, a_q, nu_k, b_k, idx_out, max_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale,
+                                  1, flags, stream);
+}
+
+extern "C" int cocos_box3_topk_max_k(void) { return cocos::BX_TOPK_MAX_K; }
+
+extern "C" int cocos_box3_topk_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
+                                     const float* b_k, int* idx_out, float* val_out, float* lse_out, int B, int Nq, int Nk,
+                                     int grid_h, int grid_w, float k_unfolded, float scale, int k, int flags, cocos_stream_t stream) {
+    using namespace cocos;
+    if (const int rc = check_box3_readout("box3_topk_f16x3", t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h,
+                                          grid_w, scale, k, flags))
+        return rc;
+#define COCOS_ARGS t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, k, flags, stream
+    if (k == 1) return launch_box3_readout<1>(COCOS_ARGS);
+    if (k == 2) return launch_box3_readout<2>(COCOS_ARGS);
+    if (k <= 4) return launch_box3_readout<4>(COCOS_ARGS);
+    return launch_box3_readout<8>(COCOS_ARGS);
+#undef COCOS_ARGS
 }
 
 extern "C" size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk) {

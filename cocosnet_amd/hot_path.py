@@ -252,15 +252,17 @@ class _BoxedCorr:
         t = self._get("t_cols", lambda: ops.box3_corr_xbox(self.ph, self.th, None, self._raw_planes))
         return ops.box3_softmax_warp(t, nu, b, mu, a, v, self.fh, self.fw, self.kc, self.inv_t)
 
-    def match(self, rows: bool):
+    def match(self, rows: bool, k: int = 1):
         """(idx int32, max, lse) [B,N] of the rows of the logits (rows) or of their transpose (not rows): K37 on the row pass's T —
-        read transposed for the column direction, with or without a gradient sink (nothing is differentiated)."""
+        read transposed for the column direction, with or without a gradient sink (nothing is differentiated).  k > 1: the k best
+        per row, (idx [B,N,k], val [B,N,k], lse [B,N]), from K41 on the same T and the same cached statistics."""
         mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
         nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
         t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        if rows:
-            return ops.box3_match(t, mu, a, nu, b, self.fh, self.fw, self.kc, self.inv_t)
-        return ops.box3_match(t, nu, b, mu, a, self.fh, self.fw, self.kc, self.inv_t, transposed=True)
+        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        if k == 1:
+            return ops.box3_match(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows)
+        return ops.box3_topk(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
 
 
 def _box_sum3(x):
@@ -623,9 +625,9 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     are materialised as for return_corr and read in one sweep by K36b.  Forward only: runs under torch.no_grad().
 
     `topk` = k > 1 (at most ops.MATCH_TOPK_MAX and the number of positions asked about, else ValueError) returns a TopkMatchReadout:
-    the k best candidates per position.  The fused match_kernel-1 route then runs K39a (ops.corr_topk_ok(k); still nothing HWxHW);
-    every other route, the fused match_kernel-3 one included (K37's reader of T finds one maximum), materialises its logits and
-    reads them in one sweep with K39b."""
+    the k best candidates per position.  The fused match_kernel-1 route then runs K39a (ops.corr_topk_ok(k); still nothing HWxHW)
+    and the fused match_kernel-3 route K41 (ops.box3_topk_ok(k): the same one T, read once, K37's kernel with a candidate list per
+    lane); every other route materialises its logits and reads them in one sweep with K39b."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
@@ -676,9 +678,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
             else:
                 idx, mx, lse = ops.corr_topk(qn, kn, inv_t, k, planes) if rows else ops.corr_topk(kn, qn, inv_t, k, planes)
-        elif k == 1 and ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw) and ops.box3_fused_ok(B, C, fh, fw):
+        elif ((k == 1 or ops.box3_topk_ok(k)) and ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw)
+              and ops.box3_fused_ok(B, C, fh, fw)):
             # the reference's default on the fused family's shapes: ONE HWxHW tensor (T, from the x-box GEMM's epilogue), read once
-            # by K37 — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
+            # by K37 (k > 1: K41) — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
             if exemplar is not None:       # the record's planes and (nu, b): the key side is not recomputed
                 th = raw(theta_raw).detach()
                 boxed = _BoxedCorr(th, th.view_as(th), inv_t, prepared_k=exemplar.box_planes(B))
@@ -686,7 +689,7 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
             else:
                 boxed = _BoxedCorr(raw(theta_raw).detach(), raw(phi_raw).detach(), inv_t)
-            idx, mx, lse = boxed.match(rows)
+            idx, mx, lse = boxed.match(rows, k)
             del boxed
         else:
             th = raw(theta_raw).detach()

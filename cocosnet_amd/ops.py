@@ -2675,6 +2675,39 @@ def box3_match(t, mu, a, nu, b, h, w, k_unfolded, scale, transposed: bool = Fals
     return idx, mx, lse
 
 
+def box3_topk_ok(k: int) -> bool:
+    """K41 ships an instantiation that serves k candidates (one ships only with zero scratch at two waves per SIMD and when the route
+    beats materialise + row_topk_lse at both benchmark shapes: DESIGN.md 3.25); above it the readout materialises (K39b)."""
+    return 1 <= k <= _lib.load().cocos_box3_topk_max_k()
+
+
+def box3_topk(t, mu, a, nu, b, h, w, k_unfolded, scale, k: int, transposed: bool = False):
+    """(idx int32 [B,N,k], val [B,N,k], lse [B,N]): per query the k largest of box3_match's logits z[p,q], their key indices and the
+    row log-sum-exp (K41; forward only: the inputs are detached and no autograd node is made).  Order: by the logit without its
+    per-query factor (z = tt * scale * a_p, scale * a_p > 0) descending and, among bitwise-equal tt, the lower index first — val is
+    non-increasing, and two unequal tt that round to the same val keep their tt order.  Rank 0 and lse are box3_match's outputs bit
+    for bit.  1 <= k <= MATCH_TOPK_MAX, k <= N (ValueError); a k that box3_topk_ok refuses and the shapes box3_match refuses
+    raise: materialise the logits and use row_topk_lse."""
+    for x, name in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
+        if not x.is_cuda:
+            raise _lib.CocosHipError(f"box3_topk: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    with torch.no_grad():
+        t, mu, a, nu, b = (_chk(x.detach(), f"box3_topk: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
+        if mu.dim() != 2:
+            raise ValueError("box3_topk: mu is [B,N]")
+        B, N = mu.shape
+        if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
+            raise ValueError("box3_topk: shape mismatch")
+        k = _check_topk("box3_topk", k, N)
+        idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
+        val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
+        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        _call("box3_topk", "cocos_box3_topk_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+              idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale), k,
+              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+    return idx, val, lse
+
+
 # ------------------------------------------------------------------------------------------
 # K12 statistics of the 3x3-unfolded vectors without unfolding   (correspondence.py:276-280, match_kernel 3)
 # ------------------------------------------------------------------------------------------

@@ -1063,6 +1063,22 @@ int cocos_box3_softmax_warp_fwd_f16x3(const float* t_blocked, const float* mu_q,
 int cocos_box3_match_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
                            int* idx_out, float* max_out, float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w,
                            float k_unfolded, float scale, int flags, cocos_stream_t stream);
+/* K41 — the top-k match readout (K39) of these logits, from the same T and statistics: per query p the k largest z[p,q]
+ *         idx[b,p,r], val[b,p,r] = the key index and the logit (natural units) of rank r = 0 .. k-1;  lse[b,p] = log sum_q exp z[p,q]
+ *     (idx [B,Nq,k] int32, val [B,Nq,k], lse [B,Nq]).  One kernel template with cocos_box3_match_f16x3 (K = 1, 2, 4, 8 candidates per
+ *     lane; a request for k runs the next one up): idx[..,0], val[..,0] and lse are cocos_box3_match_f16x3's three outputs bit for bit,
+ *     and k = 1 IS that call.  Nothing of size HWxHW besides T.
+ *     Order: a query's logit is z = tt * a_n with a_n = scale * a_p > 0 its own factor; the candidates are ordered by tt descending and,
+ *     among bitwise-equal tt, the lower key index first.  val is therefore non-increasing; two unequal tt whose products round to the
+ *     same val keep their tt order.  The k indices of a row are pairwise distinct for finite input; for non-finite input they are
+ *     clamped into [0, Nk) as K36 / K37 do and may repeat.
+ *     Arguments, supported shapes, flags and alignment as cocos_box3_match_f16x3; k outside 1..COCOS_MATCH_TOPK_MAX or above Nk is
+ *     COCOS_ERR_INVALID before any launch; k above cocos_box3_topk_max_k() (the largest instantiation that ships) is
+ *     COCOS_ERR_UNSUPPORTED (materialise and use cocos_row_topk_lse). */
+int cocos_box3_topk_max_k(void);
+int cocos_box3_topk_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                          int* idx, float* val, float* lse, int B, int Nq, int Nk, int grid_h, int grid_w, float k_unfolded,
+                          float scale, int k, int flags, cocos_stream_t stream);
 size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk);
 int cocos_box3_softmax_warp_bwd_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
                                       const float* b_k, const void* vph, const void* vpl, const void* gph, const void* gpl,
