@@ -69,6 +69,7 @@ HIP_SOURCES = [
     "corr_topk_f16x3.hip",
     "row_topk_lse.hip",
     "gather_blend_patches.hip",
+    "sparse_warp_f16x3.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

@@ -710,3 +710,84 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                                     grid=other)
         return MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
                             max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)
+
+
+# ---- K42: differentiable k-sparse warp over the top-k matches ---------------------------------------------------------------------
+def _sparse_scope(cfg: HotPathConfig, topk):
+    """ValueError for every flag outside correspondence_sparse's scope (checked before any tensor is looked at) -> k"""
+    name = "correspondence_sparse"
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
+        raise ValueError(f"{name}: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+    if cfg.match_kernel != 1:
+        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope (the sparse warp runs on the fused match_kernel 1 route)")
+    if not cfg.PONO_C:
+        raise ValueError(f"{name}: needs PONO_C (centring over the channels, as the fused match_kernel 1 route)")
+    for flag in ("warp_patch", "warp_bilinear"):
+        if getattr(cfg, flag):
+            raise ValueError(f"{name}: {flag} is out of scope (the sparse warp up-samples the pooled exemplar by nearest neighbour)")
+    if cfg.warp_cycle_w > 0 or cfg.two_cycle or cfg.warp_mask_losstype == "cycle":
+        raise ValueError(f"{name}: the cycle terms (warp_cycle_w, two_cycle, warp_mask_losstype='cycle') are out of scope: they need the "
+                         "column softmax over all positions")
+    if ops.PRECISION != "f16x3":
+        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope (the candidates come from the split-precision readout)")
+    return topk
+
+
+def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
+                          exemplar=None):
+    """The k-sparse, trainable variant of correspondence_hot_path's row pass (CoCosNet-v2 style): per content position the `topk` best
+    exemplar positions are SELECTED without gradient by the match readout (K23 / K1 planes -> K39a, as correspondence_match), then a
+    softmax over those k logits alone blends their values — ops.sparse_softmax_warp (K42), with gradients to theta_raw and phi_raw
+    through ops.center_l2norm_planes (K1, whose planes serve both steps).  Nothing HWxHW is allocated, forward or backward.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 (or ops.LazyProj1x1, projected here).  Returns {warp_out [B,3,H,W] (nearest
+    up-sampling of the blend of the pooled exemplar), warp_mask [B,nc,h,w] when cfg.warp_mask_losstype == "direct" (or show_warpmask),
+    match_index [B,k,h,w] int64, match_weight [B,k,h,w] (the k-sparse softmax weights; no gradient)}.
+
+    Scope: match_kernel 1, PONO_C, 256 channels, shapes ops.corr_split_ok and ops.corr_topk_ok(k) accept, COCOS_PRECISION=f16x3, plain
+    flag set (no warp_patch / warp_bilinear / cycle terms), no prepared exemplar: everything else raises ValueError — there is no
+    fall-back route.  CPU tensors raise CocosHipError."""
+    k = _sparse_scope(cfg, topk)
+    if exemplar is not None:
+        raise ValueError("correspondence_sparse: a prepared exemplar is out of scope (it is forward-only; the sparse warp differentiates phi)")
+    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
+    if lazy[0] != lazy[1]:
+        raise TypeError("correspondence_sparse: theta and phi must both be tensors or both be ops.LazyProj1x1")
+    B, C, fh, fw = theta_raw.shape
+    N, Nk, down = fh * fw, phi_raw.shape[2] * phi_raw.shape[3], cfg.down
+    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
+        raise ValueError(f"correspondence_sparse: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
+                         f"{tuple(phi_raw.shape)}")
+    if k > Nk:
+        raise ValueError(f"correspondence_sparse: topk={k} exceeds the {Nk} exemplar positions")
+    if tuple(ref_img.shape[2:]) != (phi_raw.shape[2] * down, phi_raw.shape[3] * down) or ref_img.shape[3] % 4 != 0:
+        raise ValueError(f"correspondence_sparse: ref_img {tuple(ref_img.shape)} is not down={down} times the exemplar grid "
+                         f"{tuple(phi_raw.shape[2:])} (width a multiple of 4)")
+    if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
+        raise ops._lib.CocosHipError("correspondence_sparse: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(k):
+        raise ValueError(f"correspondence_sparse: the fused top-k readout does not take B={B}, {N} x {Nk} positions, k={k} "
+                         "(positions must be multiples of 4)")
+    if all(lazy):
+        theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
+    # K1 with autograd, in the flavour correspondence_match selects from: the position-major operand planes are written once and serve
+    # the selection and the warp alike (the same planes, so the same candidates as correspondence_match, bit for bit); qn / kn are the
+    # handles of those planes, and each keeps its channel-major planes for its own backward when it is differentiated
+    planes = ops.OperandPlanes()
+    qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
+    kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    inv_t = 1.0 / temperature
+    direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
+    with torch.no_grad():
+        idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                    # selection: no gradient
+        v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
+    o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True)
+    n_ref = ref_img.shape[1]
+    y, o_mask = _split_channels(o, n_ref) if direct_mask else (o, None)
+    out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
+    if direct_mask:
+        out["warp_mask"] = o_mask.reshape(B, -1, fh, fw)
+    rank_first = lambda t: t.reshape(B, fh, fw, k).permute(0, 3, 1, 2).contiguous()
+    out["match_index"] = rank_first(idx.to(torch.int64))
+    out["match_weight"] = rank_first(w)
+    return out

@@ -1080,6 +1080,116 @@ def gather_blend_patches(img: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, 
 
 
 # ------------------------------------------------------------------------------------------
+# K42  k-sparse correspondence warp with gradients: attention over the k selected keys of every query
+# ------------------------------------------------------------------------------------------
+def _transpose(x: torch.Tensor) -> torch.Tensor:
+    """x [B,R,C] fp32 -> [B,C,R], a copy (cocos_transpose_f32): between the channel-major tensors of the ops and the position-major
+    rows the K42 kernels gather"""
+    B, R, C = x.shape
+    out = torch.empty((B, C, R), device=x.device, dtype=torch.float32)
+    _call("transpose", "cocos_transpose_f32", x.data_ptr(), out.data_ptr(), B, R, C, _stream())
+    return out
+
+
+def _inverse_index_table(idx: torch.Tensor, Nk: int):
+    """idx [B,Nq,k] int32 with values in [0, Nk) -> (entries [B*Nq*k] int32, offsets [B*Nk+1] int32): the flat positions of idx grouped
+    by the key b * Nk + j they name, ascending inside a group (a STABLE sort of the keys), and the group boundaries — what turns the
+    key-side scatter into a gather in a fixed order.  Index plumbing on B*Nq*k integers; the arithmetic stays in the kernel."""
+    B = idx.shape[0]
+    key = (idx.long() + (torch.arange(B, device=idx.device) * Nk).view(B, 1, 1)).reshape(-1)
+    entries = torch.sort(key, stable=True).indices.to(torch.int32)
+    offsets = torch.zeros(B * Nk + 1, device=idx.device, dtype=torch.int32)
+    offsets[1:] = torch.cumsum(torch.bincount(key, minlength=B * Nk), 0)
+    return entries, offsets
+
+
+class _SparseSoftmaxWarp(torch.autograd.Function):
+    """K42.  qn / kn are only the autograd inputs (fp32 tensors or producer handles): the kernels read their position-major operand
+    planes qh, ql, kh, kl.  Saved for the backward: the four planes, v^T, idx and w [B,Nq,k] — nothing with an Nq x Nk extent."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, v, idx, inv_t: float, qh, ql, kh, kl):
+        B, Nq, K = qh.shape
+        Nk, Cv, k = kh.shape[1], v.shape[1], idx.shape[2]
+        vt = _transpose(v)
+        out_t = torch.empty((B, Nq, Cv), device=v.device, dtype=torch.float32)
+        w = torch.empty((B, Nq, k), device=v.device, dtype=torch.float32)
+        _call("sparse_softmax_warp_fwd", "cocos_sparse_softmax_warp_fwd_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+              vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), B, K, Nq, Nk, Cv, k, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+        ctx.save_for_backward(qh, ql, kh, kl, vt, idx, w)
+        ctx.inv_t = float(inv_t)
+        ctx.mark_non_differentiable(w)
+        return _transpose(out_t), w
+
+    @staticmethod
+    def backward(ctx, dout, _dw):
+        qh, ql, kh, kl, vt, idx, w = ctx.saved_tensors
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        B, Nq, K = qh.shape
+        Nk, Cv, k = kh.shape[1], vt.shape[2], idx.shape[2]
+        dout_t = _transpose(_chk(dout, "sparse_softmax_warp: dout"))
+        dims = (B, K, Nq, Nk, Cv, k, ctx.inv_t, SPLIT_OPERAND_SCALE, _stream())
+        dqn = dkn = dv = ds = None
+        if need_q or need_k:
+            ds = torch.empty((B, Nq, k), device=dout.device, dtype=torch.float32)
+            dq_t = torch.empty((B, Nq, K), device=dout.device, dtype=torch.float32) if need_q else None
+            _call("sparse_softmax_warp_bwd_query", "cocos_sparse_softmax_warp_bwd_query_f16x3", kh.data_ptr(), kl.data_ptr(), vt.data_ptr(),
+                  dout_t.data_ptr(), idx.data_ptr(), w.data_ptr(), ds.data_ptr(), _ptr(dq_t), *dims)
+            if need_q:
+                dqn = _transpose(dq_t)
+                del dq_t
+        if need_k or need_v:
+            entries, offsets = _inverse_index_table(idx, Nk)
+            dk_t = torch.empty((B, Nk, K), device=dout.device, dtype=torch.float32) if need_k else None
+            dv_t = torch.empty((B, Nk, Cv), device=dout.device, dtype=torch.float32) if need_v else None
+            _call("sparse_softmax_warp_bwd_key", "cocos_sparse_softmax_warp_bwd_key_f16x3", qh.data_ptr(), ql.data_ptr(), dout_t.data_ptr(),
+                  _ptr(ds), w.data_ptr(), entries.data_ptr(), offsets.data_ptr(), _ptr(dk_t), _ptr(dv_t), *dims)
+            if need_k:
+                dkn = _transpose(dk_t)
+                del dk_t
+            if need_v:
+                dv = _transpose(dv_t)
+        return dqn, dkn, dv, None, None, None, None, None, None
+
+
+def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandPlanes | None = None, return_weights: bool = False):
+    """out [B,Cv,Nq] = sum_r w[b,i,r] * v[b,:,idx[b,i,r]] with w = softmax over r of inv_temperature * <qn[b,:,i], kn[b,:,idx[b,i,r]]>:
+    attention over the k keys per query that a top-k readout selected (K42) — the k-sparse softmax of match(blend="topk"), with
+    gradients for qn, kn and v (each computed only when needed; idx is data).  qn [B,256,Nq], kn [B,256,Nk] fp32 with unit-norm
+    columns, or the handles of producer-made planes registered in `planes`, as corr_topk takes them (the logits come from the same
+    operand planes that chose the candidates); v [B,Cv,Nk] fp32; idx [B,Nq,k] int32 / int64 with 1 <= k <= MATCH_TOPK_MAX, k <= Nk —
+    any values: repeats inside a row are legal, values outside [0, Nk) are clamped into it.  Nothing Nq x Nk is allocated, forward or
+    backward; dkn and dv are gathered over the inverse table of idx in a fixed order (no atomics: bitwise reproducible).
+    `return_weights`: also return w [B,Nq,k] (no gradient)."""
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"sparse_softmax_warp: idx must be int32 or int64, got {idx.dtype}")
+    if qn.dim() != 3 or kn.dim() != 3 or v.dim() != 3 or idx.dim() != 3:
+        raise ValueError(f"sparse_softmax_warp: expected qn [B,256,Nq], kn [B,256,Nk], v [B,Cv,Nk], idx [B,Nq,k]; got {tuple(qn.shape)}, "
+                         f"{tuple(kn.shape)}, {tuple(v.shape)}, {tuple(idx.shape)}")
+    B, K, Nq = qn.shape
+    Nk = kn.shape[2]
+    if kn.shape[:2] != (B, K) or v.shape[0] != B or v.shape[2] != Nk or v.shape[1] < 1 or idx.shape[:2] != (B, Nq):
+        raise ValueError(f"sparse_softmax_warp: shape mismatch qn{tuple(qn.shape)} kn{tuple(kn.shape)} v{tuple(v.shape)} idx{tuple(idx.shape)}")
+    if K != FUSED_K:
+        raise ValueError(f"sparse_softmax_warp: needs {FUSED_K} channels, got {K}")
+    _check_topk("sparse_softmax_warp", int(idx.shape[2]), Nk)
+    for t, name in ((qn, "qn"), (kn, "kn"), (v, "v"), (idx, "idx")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"sparse_softmax_warp: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if PRECISION != "f16x3":
+        raise _lib.CocosHipError("sparse_softmax_warp: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    if planes is None:
+        planes = OperandPlanes()
+    qn, kn = (t if planes.has(t) else _chk(t, f"sparse_softmax_warp: {name}") for t, name in ((qn, "qn"), (kn, "kn")))
+    v = _chk(v, "sparse_softmax_warp: v")
+    with torch.no_grad():
+        idx = idx.clamp(0, Nk - 1).to(torch.int32).contiguous()
+        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
+    out, w = _SparseSoftmaxWarp.apply(qn, kn, v, idx, float(inv_temperature), *pl)
+    return (out, w) if return_weights else out
+
+
+# ------------------------------------------------------------------------------------------
 # K3  materialised correlation         (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
 # ------------------------------------------------------------------------------------------
 class _CorrMaterialize(torch.autograd.Function):

@@ -1255,6 +1255,43 @@ int cocos_row_topk_lse(const float* logits, int* idx, float* val, float* lse, in
 int cocos_gather_blend_patches(const float* img, const int* idx, const float* w, float* out, int B, int C, int H, int W, int down,
                                int k, long long img_batch_stride, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K42 k-sparse correspondence warp with gradients (sparse_warp_f16x3.hip): attention over the k keys per query that the top-k match
+ *     readout selected (selection itself carries no gradient),
+ *         s[b,i,r] = inv_temperature <qn[b,:,i], kn[b,:,j_r]>,  j_r = idx[b,i,r],  w = softmax over r of s,
+ *         out[b,:,i] = sum_r w[b,i,r] v[b,:,j_r]
+ *     — the weights of the k-sparse blend of cocos_gather_blend_patches, now differentiable in qn, kn and v.  Nothing Nq x Nk exists:
+ *     the state is idx, w and ds, each [B,Nq,k].
+ *     Common to the three kernels: qh,ql [B,Nq,256], kh,kl [B,Nk,256] are the position-major f16 hi / lo operand planes of
+ *     cocos_corr_topk_f16x3 (value = (hi + lo) / operand_scale), 16-byte aligned; idx [B,Nq,k] int32, ANY values (repeats inside a row
+ *     are legal, values outside [0, Nk) are clamped into it); every fp32 tensor is POSITION-major: v_t [B,Nk,Cv], out_t / dout_t
+ *     [B,Nq,Cv], dq_t [B,Nq,256], dk_t [B,Nk,256], dv_t [B,Nk,Cv] (cocos_transpose_f32 makes them from / turns them into the
+ *     channel-major tensors, once per tensor).  fp32 arithmetic in a fixed order, no atomics: results are bitwise reproducible.
+ *     Null pointers, dims < 1, k outside 1..COCOS_MATCH_TOPK_MAX or above Nk: COCOS_ERR_INVALID; K != 256, or B Nq k / B Nk at or
+ *     above 2^31: COCOS_ERR_UNSUPPORTED — all before any HIP call.
+ *   cocos_sparse_softmax_warp_fwd_f16x3: one wave per query; writes out_t and w [B,Nq,k].
+ *   cocos_sparse_softmax_warp_bwd_query_f16x3: one wave per query; dw_r = <dout_t[i], v_t[j_r]>, ds_r = w_r (dw_r - sum_r' w_r' dw_r');
+ *       writes ds [B,Nq,k] and, unless dq_t is null, dq_t[i] = inv_temperature sum_r ds_r kn[j_r].
+ *   cocos_sparse_softmax_warp_bwd_key_f16x3: one wave per key, a gather over the INVERSE table of idx: entries [B Nq k] int32 holds the
+ *       flat positions p = (b Nq + i) k + r of idx grouped by the key b Nk + j they name (clamped), ascending inside a group;
+ *       offsets [B Nk + 1] int32 the group boundaries.  dk_t[j] = inv_temperature sum ds[p] qn[i], dv_t[j] = sum w[p] dout_t[i], summed
+ *       serially in table order; either output may be null (not both; dk_t null: qh, ql, ds may be null too).  A key nobody names gets
+ *       zeros, written by the kernel.  A key all queries name is one serial list of Nq entries for one wave.  Positions and offsets
+ *       are clamped into the tables.
+ *   cocos_transpose_f32: in [B,R,C] -> out [B,C,R] (B <= 65535, R <= 65535 * 32, else COCOS_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------- */
+int cocos_sparse_softmax_warp_fwd_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* v_t,
+                                        const int* idx, float* out_t, float* w, int B, int K, int Nq, int Nk, int Cv, int k,
+                                        float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_sparse_softmax_warp_bwd_query_f16x3(const void* kh, const void* kl, const float* v_t, const float* dout_t, const int* idx,
+                                              const float* w, float* ds, float* dq_t /* nullable */, int B, int K, int Nq, int Nk,
+                                              int Cv, int k, float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_sparse_softmax_warp_bwd_key_f16x3(const void* qh, const void* ql, const float* dout_t, const float* ds, const float* w,
+                                            const int* entries, const int* offsets, float* dk_t /* nullable */,
+                                            float* dv_t /* nullable */, int B, int K, int Nq, int Nk, int Cv, int k,
+                                            float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_transpose_f32(const float* in, float* out, int B, int R, int C, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
