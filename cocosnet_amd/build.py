@@ -70,6 +70,7 @@ HIP_SOURCES = [
     "row_topk_lse.hip",
     "gather_blend_patches.hip",
     "sparse_warp_f16x3.hip",
+    "patchmatch_f16x3.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]
@@ -108,7 +109,7 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC_DIR, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC_DIR, "common.h"), os.path.join(CSRC_DIR, "box3_common.h"), os.path.join(CSRC_DIR, "proj_frag.h"),
-                   os.path.join(CSRC_DIR, "topk_list.h"),
+                   os.path.join(CSRC_DIR, "topk_list.h"), os.path.join(CSRC_DIR, "sparse_row.h"),
                    os.path.join(REPO_DIR, "include", "cocos_hip.h")]
     stamp = LIB_PATH + ".sha256"      # next to the library: it travels with it (obj/ does not have to)
     want = _digest(deps)

@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import HotPathConfig, _sparse_scope, correspondence_hot_path, correspondence_match, correspondence_sparse
+from .hot_path import HotPathConfig, _sparse_scope, _sparse_search, correspondence_hot_path, correspondence_match, correspondence_sparse
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -325,20 +325,24 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
         return out
 
-    def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4):
+    def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, search="dense", search_opts=None):
         """The trainable k-sparse warp (hot_path.correspondence_sparse): per content position the `topk` best exemplar positions are
         selected without gradient, and a softmax over those k logits alone blends the pooled exemplar (and, under
         --warp_mask_losstype direct, the exemplar's labels) — attention over k keys instead of all HW, with gradients to the whole
         network through theta and phi and nothing HWxHW in memory.  Returns {warp_out [B,3,H,W], warp_mask [B,nc,h,w] (direct),
         match_index [B,k,h,w] int64, match_weight [B,k,h,w]} (+ loss_novgg_featpair where project() makes it).  Scope: match_kernel 1
-        with PONO_C on the plain flag set; everything else raises ValueError (no fall-back).  forward() and match() are unaffected."""
+        with PONO_C on the plain flag set; everything else raises ValueError (no fall-back).  forward() and match() are unaffected.
+        `search` / `search_opts`: the candidate selector, "dense" (default: the scan over all keys) or "patchmatch" (K43) with its
+        schedule, as hot_path.correspondence_sparse takes them."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
         _sparse_scope(cfg, topk)                  # out-of-scope flags are refused before the network runs
+        _sparse_search(search, search_opts)
         if ref_img is None or ref_seg_map is None:
             raise ValueError("sparse_warp: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
-        coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk))
+        coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, search=search,
+                                              search_opts=search_opts))
         return coor_out
 
 

@@ -15,32 +15,13 @@
 //   key backward     one wave per key, a GATHER over the inverse table of idx (per key the entries (i, r) that name it, ascending):
 //                    dkn^T[j] = inv_t sum ds qn[i],  dv^T[j] = sum w dout^T[i], summed serially in table order — bitwise reproducible;
 //                    a key nobody names gets zeros from this kernel.  A key every query names is a serial list of Nq entries.
-#include "common.h"
+#include "sparse_row.h"      // wave_sum, load_row4, lane_dot4, clamp_key: shared with K43 (patchmatch_f16x3.hip)
 
 namespace cocos {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SW_KD = 256;               // channels of the operand planes
 constexpr int SW_WAVES = 4;              // rows (queries or keys) per workgroup, one per wave
 constexpr int SW_THREADS = SW_WAVES * kWave;
 constexpr int SW_MAXK = COCOS_MATCH_TOPK_MAX;
-
-// sum over the 64 lanes, the same bits in every lane (xor butterfly: both partners add the same two numbers)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-
-// channels 4 lane .. 4 lane + 3 of row `row` of a [rows,256] hi/lo plane pair, hi + lo in fp32 (still x operand_scale)
-__device__ __forceinline__ f32x4 load_row4(const _Float16* __restrict__ hi, const _Float16* __restrict__ lo, long long row, int lane) {
-    const f16x4 h = *reinterpret_cast<const f16x4*>(hi + row * SW_KD + lane * 4);
-    const f16x4 l = *reinterpret_cast<const f16x4*>(lo + row * SW_KD + lane * 4);
-    return f32x4{(float)h[0] + (float)l[0], (float)h[1] + (float)l[1], (float)h[2] + (float)l[2], (float)h[3] + (float)l[3]};
-}
-
-__device__ __forceinline__ int clamp_key(int j, int Nk) { return min(max(j, 0), Nk - 1); }
 
 __global__ __launch_bounds__(SW_THREADS) void sparse_warp_fwd_kernel(const _Float16* __restrict__ qh, const _Float16* __restrict__ ql,
                                                                      const _Float16* __restrict__ kh, const _Float16* __restrict__ kl,
@@ -62,7 +43,7 @@ __global__ __launch_bounds__(SW_THREADS) void sparse_warp_fwd_kernel(const _Floa
         if (r < k) {
             key[r] = kbase + clamp_key(idx[row * k + r], Nk);
             const f32x4 kv = load_row4(kh, kl, key[r], lane);
-            s[r] = wave_sum(__builtin_fmaf(q[3], kv[3], __builtin_fmaf(q[2], kv[2], __builtin_fmaf(q[1], kv[1], q[0] * kv[0])))) * logit_scale;
+            s[r] = wave_sum(lane_dot4(q, kv)) * logit_scale;
             m = fmaxf(m, s[r]);
         }
     }

@@ -733,8 +733,52 @@ def _sparse_scope(cfg: HotPathConfig, topk):
     return topk
 
 
+def _sparse_search(search, search_opts):
+    """ValueError for a selector correspondence_sparse does not have, or options it does not know -> the PatchMatch schedule (None for
+    the dense scan); checked after _sparse_scope, before any tensor is looked at"""
+    name = "correspondence_sparse"
+    if search not in ("dense", "patchmatch"):
+        raise ValueError(f"{name}: search={search!r}: expected 'dense' or 'patchmatch'")
+    opts = dict(search_opts or {})
+    if search == "dense":
+        if opts:
+            raise ValueError(f"{name}: search_opts {sorted(opts)} given with search='dense' (the dense scan has no options)")
+        return None
+    unknown = sorted(set(opts) - set(ops.PATCHMATCH_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{name}: unknown search_opts {unknown}: expected a subset of {sorted(ops.PATCHMATCH_DEFAULTS)}")
+    return dict(ops.PATCHMATCH_DEFAULTS, **opts)
+
+
+def _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k):
+    """The starting candidates of the PatchMatch selector, [B,N,k] int64, or "random" where the half grid is out of the dense readout's
+    reach (an odd side, half-grid positions that are no multiple of 4, fewer than k half-grid keys): theta / phi averaged over 2 x 2
+    cells (torch glue), K1 planes of the pooled features, the dense top-k (K39a) at a quarter of the positions on each side — a
+    sixteenth of the full scan — and every coarse candidate (ky, kx) of coarse query (y / 2, x / 2) expanded to the fine key
+    (2 ky + y % 2, 2 kx + x % 2): the key that lies in its coarse cell where the query lies in its own."""
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    if fh % 2 or fw % 2 or gh % 2 or gw % 2:
+        return "random"
+    Nc, Nkc = (fh // 2) * (fw // 2), (gh // 2) * (gw // 2)
+    if k > Nkc or not ops.corr_split_ok(B, C, Nc, Nkc, 1, False) or not ops.corr_topk_ok(k):
+        return "random"
+    planes = ops.OperandPlanes()
+    pool = lambda t: _flat(torch.nn.functional.avg_pool2d(t.detach(), 2))
+    qc = ops.center_l2norm_planes(pool(theta_raw), 1, planes, want_chan=False)
+    kc = ops.center_l2norm_planes(pool(phi_raw), 1, planes, want_chan=False)
+    coarse, _, _ = ops.corr_topk(qc, kc, inv_t, k, planes)                          # [B,Nc,k] int32
+    coarse = coarse.to(torch.int64).reshape(B, fh // 2, fw // 2, k)
+    coarse = coarse.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)         # the coarse query of every fine query
+    dev = coarse.device
+    py = (torch.arange(fh, device=dev) % 2).view(1, fh, 1, 1)
+    px = (torch.arange(fw, device=dev) % 2).view(1, 1, fw, 1)
+    cky, ckx = torch.div(coarse, gw // 2, rounding_mode="floor"), coarse % (gw // 2)
+    return ((2 * cky + py) * gw + 2 * ckx + px).reshape(B, fh * fw, k)
+
+
 def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                          exemplar=None):
+                          exemplar=None, search="dense", search_opts=None):
     """The k-sparse, trainable variant of correspondence_hot_path's row pass (CoCosNet-v2 style): per content position the `topk` best
     exemplar positions are SELECTED without gradient by the match readout (K23 / K1 planes -> K39a, as correspondence_match), then a
     softmax over those k logits alone blends their values — ops.sparse_softmax_warp (K42), with gradients to theta_raw and phi_raw
@@ -746,8 +790,16 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
 
     Scope: match_kernel 1, PONO_C, 256 channels, shapes ops.corr_split_ok and ops.corr_topk_ok(k) accept, COCOS_PRECISION=f16x3, plain
     flag set (no warp_patch / warp_bilinear / cycle terms), no prepared exemplar: everything else raises ValueError — there is no
-    fall-back route.  CPU tensors raise CocosHipError."""
+    fall-back route.  CPU tensors raise CocosHipError.
+
+    `search`: how the k candidates are found.  "dense" (the default) is the scan over all keys above.  "patchmatch" (K43) starts from
+    the dense top-k of the 2 x 2 average-pooled features (_patchmatch_coarse_init; a random start where the half grid is out of the
+    readout's reach) and runs ops.patchmatch_topk on the full-grid planes: propagation from the grid neighbours plus a random search,
+    O(N k) dot products per iteration whatever the number of keys.  Its candidates are the best of what it looked at, not of all keys
+    (DESIGN.md 3.27 records recall and cost against the dense scan); scope and refusals are the dense selector's.  `search_opts`
+    overrides entries of ops.PATCHMATCH_DEFAULTS: strides (one iteration per entry), radii, radius0, seed."""
     k = _sparse_scope(cfg, topk)
+    pm = _sparse_search(search, search_opts)
     if exemplar is not None:
         raise ValueError("correspondence_sparse: a prepared exemplar is out of scope (it is forward-only; the sparse warp differentiates phi)")
     lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
@@ -779,7 +831,12 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     inv_t = 1.0 / temperature
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
     with torch.no_grad():
-        idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                    # selection: no gradient
+        if pm is None:
+            idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                # selection: no gradient
+        else:
+            idx, _ = ops.patchmatch_topk(qn, kn, inv_t, k, (tuple(theta_raw.shape[2:]), tuple(phi_raw.shape[2:])),
+                                         _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k), pm["strides"],
+                                         (pm["radii"], pm["radius0"]), pm["seed"], planes)
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
     o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True)
     n_ref = ref_img.shape[1]

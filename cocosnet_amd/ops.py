@@ -1190,6 +1190,144 @@ def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandP
 
 
 # ------------------------------------------------------------------------------------------
+# K43  PatchMatch candidate search: the selector of the k-sparse warp whose work does not grow with the number of keys
+# ------------------------------------------------------------------------------------------
+#: the largest number of search radii per iteration (COCOS_PATCHMATCH_MAX_RADII of cocos_hip.h)
+PATCHMATCH_MAX_RADII = _lib.CONSTANTS["COCOS_PATCHMATCH_MAX_RADII"]
+#: the schedule hot_path.correspondence_sparse(search="patchmatch") runs when search_opts names none: one launch per stride, `radii`
+#: search radii per launch starting at `radius0` (DESIGN.md 3.27 holds the measurements behind it)
+PATCHMATCH_DEFAULTS = dict(strides=(1, 2, 1, 1), radii=3, radius0=4, seed=0)
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def _patchmatch_grids(name: str, grids):
+    try:
+        (hq, wq), (hk, wk) = grids
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: grids={grids!r}: expected ((hq, wq), (hk, wk))") from None
+    if not all(_is_int(n) and n >= 1 for n in (hq, wq, hk, wk)):
+        raise ValueError(f"{name}: grids={grids!r}: expected positive integers ((hq, wq), (hk, wk))")
+    return hq, wq, hk, wk
+
+
+def _patchmatch_operands(name: str, qn, kn, grids, k, planes):
+    """the shape checks patchmatch_step / patchmatch_topk share -> (planes, hq, wq, hk, wk); ValueError before the library is called"""
+    hq, wq, hk, wk = _patchmatch_grids(name, grids)
+    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[:2] != kn.shape[:2] or qn.shape[2] != hq * wq or kn.shape[2] != hk * wk:
+        raise ValueError(f"{name}: qn{tuple(qn.shape)} kn{tuple(kn.shape)} do not fit a {hq}x{wq} query grid and a {hk}x{wk} key grid "
+                         "(expected qn [B,256,hq*wq], kn [B,256,hk*wk])")
+    if qn.shape[1] != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    _check_topk(name, k, hk * wk)
+    return (OperandPlanes() if planes is None else planes), hq, wq, hk, wk
+
+
+def _patchmatch_device(name: str, qn, kn):
+    """after every ValueError: the tensors themselves"""
+    for t, what in ((qn, "qn"), (kn, "kn")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if PRECISION != "f16x3":
+        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+
+
+def _patchmatch_search(name: str, stride, radii, radius0, seed, iteration=0):
+    if not _is_int(stride) or stride < 1:
+        raise ValueError(f"{name}: stride={stride!r}: expected an integer >= 1")
+    if not _is_int(radii) or not 0 <= radii <= PATCHMATCH_MAX_RADII:
+        raise ValueError(f"{name}: radii={radii!r}: expected an integer in 0..{PATCHMATCH_MAX_RADII}")
+    if not _is_int(radius0) or radius0 < 0:
+        raise ValueError(f"{name}: radius0={radius0!r}: expected an integer >= 0")
+    if not _is_int(seed) or not _is_int(iteration) or not (-2 ** 31 <= seed < 2 ** 31 and 0 <= iteration < 2 ** 31):
+        raise ValueError(f"{name}: seed={seed!r} iteration={iteration!r}: expected 32-bit integers (iteration >= 0)")
+
+
+def _patchmatch_launch(planes4, idx, hq, wq, hk, wk, inv_t, k, stride, radii, radius0, seed, iteration):
+    """one K43 launch on ready planes; idx int32 [B,Nq,k] contiguous or None -> (idx_out, val_out), fresh buffers"""
+    qh, ql, kh, kl = planes4
+    B, Nq, K = qh.shape
+    idx_out = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
+    val_out = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
+    _call("patchmatch_step", "cocos_patchmatch_step_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), _ptr(idx),
+          idx_out.data_ptr(), val_out.data_ptr(), B, K, hq, wq, hk, wk, k, stride, radii, radius0, seed, iteration, float(inv_t),
+          SPLIT_OPERAND_SCALE, _stream())
+    return idx_out, val_out
+
+
+def _patchmatch_planes(name: str, qn, kn, planes):
+    qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
+    out = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
+    if out[2].shape[0] != out[0].shape[0]:
+        raise ValueError(f"{name}: query and key batch differ")
+    return out
+
+
+def _patchmatch_table(name: str, idx, B, Nq, k):
+    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: the index table must be an int32 or int64 tensor")
+    if tuple(idx.shape) != (B, Nq, k):
+        raise ValueError(f"{name}: the index table is {tuple(idx.shape)}, expected {(B, Nq, k)}")
+    if not idx.is_cuda:
+        raise _lib.CocosHipError(f"{name}: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    # (int64 tables are narrowed after a clamp into int32's range, which keeps every value on its side of [0, Nk): the kernel clamps)
+    return (idx if idx.dtype == torch.int32 else idx.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
+
+
+def patchmatch_step(qn, kn, idx, grids, inv_t: float, k: int, stride: int, radii: int, radius0: int, seed: int, iteration: int,
+                    planes: OperandPlanes | None = None):
+    """One PatchMatch iteration (K43; forward only) -> (idx int32 [B,Nq,k], val [B,Nq,k]): per query the k best distinct keys, logit
+    descending (equal bits: lower key first), of the pool {its own candidates idx[b,i,:]} U {the candidates of its four neighbours at
+    distance `stride` on the query grid, shifted back by that offset} U {`radii` random offsets around each own candidate, the s-th
+    within max(1, radius0 >> s)}.  qn [B,256,hq*wq], kn [B,256,hk*wk] as corr_topk takes them (fp32 unit-norm columns, or handles
+    registered in `planes`); grids = ((hq, wq), (hk, wk)); idx [B,Nq,k] int32 / int64 (values outside the key grid are clamped into
+    it) or None: a random initialisation hashed from (seed, iteration).  val holds the logits sparse_softmax_warp forms for the same
+    pairs.  The draw is a pure function of (seed, iteration, query, rank), so a call is bitwise reproducible.  A pool with fewer than k
+    distinct keys repeats its last pair.  Bad k, grids, stride, radii: ValueError before the library is called."""
+    name = "patchmatch_step"
+    planes, hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k, planes)
+    _patchmatch_search(name, stride, radii, radius0, seed, iteration)
+    _patchmatch_device(name, qn, kn)
+    with torch.no_grad():
+        if idx is not None:
+            idx = _patchmatch_table(name, idx, qn.shape[0], hq * wq, k)
+        return _patchmatch_launch(_patchmatch_planes(name, qn, kn, planes), idx, hq, wq, hk, wk, inv_t, k, stride, radii, radius0, seed,
+                                  iteration)
+
+
+def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=PATCHMATCH_DEFAULTS["strides"],
+                    radii=PATCHMATCH_DEFAULTS["radii"], seed: int = 0, planes: OperandPlanes | None = None):
+    """PatchMatch top-k selection (K43; forward only) -> (idx int32 [B,Nq,k], val [B,Nq,k]) for sparse_softmax_warp: one
+    patchmatch_step per entry of `strides` (iteration t = 0, 1, ...: launch t reads the table launch t - 1 wrote, two buffers alive at a
+    time).  `init`: "random" or an integer tensor [B,Nq,k] of starting candidates.  `radii`: the number of search radii per iteration,
+    starting at half the longer side of the key grid, or a pair (radii, radius0).  Operands, grids and errors as patchmatch_step; an
+    empty `strides` is a ValueError (a selection needs scores)."""
+    name = "patchmatch_topk"
+    planes, hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k, planes)
+    if isinstance(init, str) and init != "random" or not (isinstance(init, str) or torch.is_tensor(init)):
+        raise ValueError(f"{name}: init={init!r}: expected 'random' or an integer tensor [B,Nq,k]")
+    try:
+        strides = tuple(strides)
+    except TypeError:
+        raise ValueError(f"{name}: strides={strides!r}: expected a non-empty sequence of integers >= 1") from None
+    if not strides:
+        raise ValueError(f"{name}: strides is empty: expected a non-empty sequence of integers >= 1")
+    n_radii, radius0 = radii if isinstance(radii, (tuple, list)) and len(radii) == 2 else (radii, max(hk, wk) // 2)
+    for t, stride in enumerate(strides):
+        _patchmatch_search(name, stride, n_radii, radius0, seed, t)
+    _patchmatch_device(name, qn, kn)
+    with torch.no_grad():
+        idx = None if isinstance(init, str) else _patchmatch_table(name, init, qn.shape[0], hq * wq, k)
+        planes4 = _patchmatch_planes(name, qn, kn, planes)
+        val = None
+        for t, stride in enumerate(strides):
+            idx, val = _patchmatch_launch(planes4, idx, hq, wq, hk, wk, inv_t, k, stride, n_radii, radius0, seed, t)
+        return idx, val
+
+
+# ------------------------------------------------------------------------------------------
 # K3  materialised correlation         (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
 # ------------------------------------------------------------------------------------------
 class _CorrMaterialize(torch.autograd.Function):

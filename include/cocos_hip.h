@@ -1292,6 +1292,33 @@ int cocos_sparse_softmax_warp_bwd_key_f16x3(const void* qh, const void* ql, cons
                                             float inv_temperature, float operand_scale, cocos_stream_t stream);
 int cocos_transpose_f32(const float* in, float* out, int B, int R, int C, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K43 PatchMatch candidate search for the k-sparse warp (patchmatch_f16x3.hip): ONE Jacobi iteration per call — a second selector
+ *     next to cocos_corr_topk_f16x3 whose work is O(Nq k (5 + radii)) dot products whatever Nk is (CoCosNet-v2's replacement of the
+ *     dense scan).  Query grid hq x wq (Nq = hq wq, position i = y wq + x), key grid hk x wk (Nk = hk wk); operand planes, score
+ *     arithmetic and output order as K42 / K39: val is the logit cocos_sparse_softmax_warp_fwd_f16x3 forms for the same pair, bit for
+ *     bit; idx_out / val_out [B,Nq,k] hold the k best DISTINCT keys of the pool, score descending, equal bits: lower key first.
+ *     The pool of query (b, y, x), idx_in [B,Nq,k] int32 clamped into [0, Nk) first:
+ *       own          idx_in[b,i,r], r < k;
+ *       propagation  neighbours n = (y -+ stride, x), (y, x -+ stride) inside the query grid, r < k: the key position of idx_in[b,n,r]
+ *                    minus (n - i); skipped when it leaves the key grid;
+ *       search       s < radii, r < k: own key position + (oy, ox), clamped into the key grid; rho = max(1, radius0 >> s),
+ *                    oy = H(word) mod (2 rho + 1) - rho, ox = H(word | 1) mod (2 rho + 1) - rho, word = (r << 8) | (s << 1).
+ *     H(word) = f(f(f(f(seed ^ 0x9e3779b9) ^ iteration) ^ (b Nq + i)) ^ word) on uint32, f the murmur3 finaliser
+ *     (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16).  idx_in null: every list (own and neighbours')
+ *     is the random initialisation  p_r = H((r << 8) | 0xff) mod Nk, stepped by +1 mod Nk while it equals an earlier p_e, e < r.
+ *     A pool with fewer than k distinct keys repeats its last (key, score) in the remaining slots (K42 accepts repeats).
+ *     idx_in and idx_out must be different buffers; the result is a pure function of the arguments (no atomics, bitwise reproducible).
+ *     Null planes / outputs, idx_in == idx_out, non-positive inv_temperature / operand_scale, misaligned planes: COCOS_ERR_INVALID;
+ *     K != 256, k outside 1..COCOS_MATCH_TOPK_MAX or above Nk, an empty grid or batch, stride < 1, radii outside
+ *     0..COCOS_PATCHMATCH_MAX_RADII, radius0 outside 0..2^20, B Nq k or B Nk at or above 2^31: COCOS_ERR_UNSUPPORTED — all before any
+ *     HIP call.  Instantiated for 1, 2, 4, 8 candidates; a k between two runs the next larger one, truncated.
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_PATCHMATCH_MAX_RADII 8
+int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* idx_in /* nullable */,
+                                int* idx_out, float* val_out, int B, int K, int hq, int wq, int hk, int wk, int k, int stride, int radii,
+                                int radius0, int seed, int iteration, float inv_temperature, float operand_scale, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
