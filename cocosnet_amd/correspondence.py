@@ -24,7 +24,8 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import HotPathConfig, _sparse_scope, _sparse_search, correspondence_hot_path, correspondence_match, correspondence_sparse
+from .hot_path import (HotPathConfig, _refine_scope, _sparse_scope, _sparse_search, correspondence_hot_path, correspondence_match,
+                       correspondence_sparse)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -270,7 +271,7 @@ class NoVGGCorrespondence(NetworkBase):
         return coor_out
 
     def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False, topk=1,
-              blend="topk"):
+              blend="topk", refine=0, refine_temperature=None):
         """Where each position matched, and how sure the match is — the hard readout of the correlation that
         `forward(..., return_corr=True)` returns as a [B,HW,HW] matrix (:305-306), without that matrix wherever the fused
         match_kernel-1 back end runs, and with one HWxHW tensor (the x-box correlation T, read once) instead of two logit matrices
@@ -288,7 +289,14 @@ class NoVGGCorrespondence(NetworkBase):
         the one T = xbox(C) read once on the fused match_kernel-3 route (K41), the logits matrix read once everywhere else.  With `hard_warp` also warp_hard (the rank-0 gather, as with topk = 1)
         and warp_topk [B,3,H,W]: per cell the blend of the k candidates' full-resolution patches, weighted by `blend` =
         "topk" (softmax over the k logits: the weights sum to 1 — a k-sparse softmax) or "full" (match_prob itself: the true
-        softmax weights, which sum to <= 1).  An unknown `blend` raises ValueError."""
+        softmax weights, which sum to <= 1).  An unknown `blend` raises ValueError.
+
+        `refine` = r in 1..3 (K44; 0, the default, changes nothing) refines the top-1 match below the feature grid: a softmax at
+        `refine_temperature` (None: `temperature`) over the (2 r + 1)^2 window of positions around the match gives match_offset
+        [B,2,h,w] (x, y; in cells, |offset| <= r), match_xy_sub = match_xy + match_offset (fp32) and match_window_prob [B,h,w], the
+        window's share of the position's softmax mass; with `hard_warp` also warp_sub [B,3,H,W], ref_img sampled bilinearly at the
+        refined position (warp_hard stays).  Scope: topk = 1, no prepared exemplar, the fused match_kernel-1 route (PONO_C,
+        COCOS_PRECISION=f16x3, ops.MATCH_FUSED); everything else raises ValueError before the network runs."""
         if direction not in ("rows", "cols"):
             raise ValueError(f"match: direction {direction!r}: expected 'rows' or 'cols'")
         if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
@@ -297,6 +305,8 @@ class NoVGGCorrespondence(NetworkBase):
             raise ValueError(f"match: blend {blend!r}: expected 'topk' or 'full'")
         if hard_warp and direction == "cols":
             raise ValueError("match: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _refine_scope("match", cfg, refine, refine_temperature, topk, exemplar is not None, self.inter_channels)
         keys = phi_raw = None
         with torch.no_grad():
             if exemplar is not None:
@@ -312,12 +322,17 @@ class NoVGGCorrespondence(NetworkBase):
                 raise ValueError("match: ref_img and ref_seg_map are required without a prepared exemplar")
             if keys is None and phi_raw is None:      # (real_img: project() reads it for the training-time featpair term only)
                 theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
-            cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk)
+            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk, refine=refine,
+                                     refine_temperature=refine_temperature)
             out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse}
+            if refine:
+                out.update(match_offset=m.offset, match_xy_sub=m.xy_sub(), match_window_prob=m.window_prob)
             if hard_warp and topk == 1:
                 fh, fw = m.index.shape[1:]
                 out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+                if refine:
+                    off = m.offset.permute(0, 2, 3, 1).reshape(m.index.shape[0], fh * fw, 2)
+                    out["warp_sub"] = ops.gather_patches_subcell(ref_img, m.index, off, (fh, fw), m.grid, self.opt.down)
             elif hard_warp:
                 fh, fw = m.index.shape[2:]
                 out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)

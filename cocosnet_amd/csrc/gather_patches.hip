@@ -22,7 +22,81 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
     out[e] = img[b * img_bstride + ((long long)c * H + sy) * W + sx];
 }
 
+// K44: the same warp at a SUB-CELL position — cell (y, x) of the fh x fw content grid samples the exemplar (an hk x wk grid of
+// down x down cells) bilinearly around its match moved by off[b, y*fw + x] = (off_x, off_y) cells.  For pixel (Y, X), r = (Y % down, X % down):
+//   sx = (xk + off_x) * down + rx, clamped into [0, Wr - 1];  x0 = floor(sx), fx = sx - x0, x1 = min(x0 + 1, Wr - 1);  y likewise
+//   out = top + fy * (bottom - top),  top = v00 + fx * (v01 - v00),  bottom = v10 + fx * (v11 - v10)
+// Contraction is off: with off == 0 both weights are 0 and the result is v00, gather_patches_kernel's copy (bit for bit for finite
+// pixels other than -0).  A non-finite offset makes the pixel NaN (the address then falls back to column / row 0: it stays in the image).
+//
+// floor(sx) and sx - floor(sx) of one axis without forming sx in fp32 (a sum near Wr would round the fraction away): the integer
+// part `base` = xk * down + rx stays an integer, t = off * down is exact for a power-of-two `down` (one rounding of a value of a few
+// cells otherwise), and t - floor(t) is exact.  Returns the fraction, the sample's lower pixel in `p0`; a position below 0 or at or
+// above `side` - 1 is the border pixel with fraction 0 — the clamp of sx.  A NaN or infinite offset returns NaN (p0 = 0).
+__device__ __forceinline__ float subcell_split(float off, int base, int down, int side, int& p0) {
+#pragma clang fp contract(off)
+    const float t = off * (float)down;
+    const float ti = floorf(t);
+    float f = t - ti;                                          // exact; NaN for a non-finite t
+    const float lim = (float)(1 << 25);                        // |base| < 2^24 (the entry point checks the image sides): no overflow
+    const int p = base + (int)fminf(fmaxf(ti, -lim), lim);    // (fmaxf(NaN, -lim) = -lim: p < 0, the first clamp)
+    const bool low = p < 0, high = p >= side - 1;
+    p0 = low ? 0 : (high ? side - 1 : p);
+    if ((low || high) && f == f) f = 0.f;
+    return f;
+}
+
+__global__ __launch_bounds__(256) void gather_patches_subcell_kernel(const float* __restrict__ img, const int* __restrict__ idx,
+                                                                     const float* __restrict__ off, float* __restrict__ out,
+                                                                     long long total, int C, int fh, int fw, int hk, int wk, int down,
+                                                                     long long img_bstride) {
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int H = fh * down, W = fw * down, Hr = hk * down, Wr = wk * down;
+    const int X = (int)(e % W), Y = (int)((e / W) % H);
+    const long long bc = e / ((long long)W * H);
+    const int c = (int)(bc % C);
+    const long long b = bc / C;
+    const int x = X / down, y = Y / down;
+    const long long cell = b * ((long long)fh * fw) + (long long)y * fw + x;
+    int j = idx[cell];
+    j = min(max(j, 0), hk * wk - 1);                           // an index outside the grid reads the nearest valid cell
+    const float ox = off[cell * 2], oy = off[cell * 2 + 1];
+    int x0, y0;
+    const float fx = subcell_split(ox, (j % wk) * down + (X - x * down), down, Wr, x0);
+    const float fy = subcell_split(oy, (j / wk) * down + (Y - y * down), down, Hr, y0);
+    const int x1 = min(x0 + 1, Wr - 1), y1 = min(y0 + 1, Hr - 1);
+    const float* plane = img + b * img_bstride + (long long)c * Hr * Wr;
+    const float v00 = plane[(long long)y0 * Wr + x0], v01 = plane[(long long)y0 * Wr + x1];
+    const float v10 = plane[(long long)y1 * Wr + x0], v11 = plane[(long long)y1 * Wr + x1];
+    const float top = v00 + fx * (v01 - v00), bottom = v10 + fx * (v11 - v10);
+    out[e] = top + fy * (bottom - top);
+}
+
 }  // namespace cocos
+
+extern "C" int cocos_gather_patches_subcell(const float* img, const int* idx, const float* off, float* out, int B, int C, int fh, int fw,
+                                            int hk, int wk, int down, long long img_batch_stride, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "gather_patches_subcell";
+    COCOS_REQUIRE(img && idx && off && out, COCOS_ERR_INVALID, "%s: null pointer (img, idx, off, out)", name);
+    COCOS_REQUIRE(B >= 1 && C >= 1 && fh >= 1 && fw >= 1 && hk >= 1 && wk >= 1 && down >= 1, COCOS_ERR_INVALID,
+                  "%s: non-positive size: B=%d C=%d fh=%d fw=%d hk=%d wk=%d down=%d", name, B, C, fh, fw, hk, wk, down);
+    const long long Hr = (long long)hk * down, Wr = (long long)wk * down, H = (long long)fh * down, W = (long long)fw * down;
+    COCOS_REQUIRE(Hr < (1 << 24) && Wr < (1 << 24) && H < (1 << 24) && W < (1 << 24) && (long long)hk * wk < 0x7fffffffll &&
+                      (long long)fh * fw < 0x7fffffffll,
+                  COCOS_ERR_UNSUPPORTED, "%s: an image side of 2^24 pixels or more (fp32 sample positions are exact below it)", name);
+    const long long per = (long long)C * Hr * Wr;
+    COCOS_REQUIRE(img_batch_stride == 0 || img_batch_stride == per, COCOS_ERR_INVALID,
+                  "%s: img_batch_stride %lld: expected 0 (one exemplar for all samples) or the dense %lld", name, img_batch_stride, per);
+    const long long total = (long long)B * C * H * W, blocks = (total + 255) / 256;
+    COCOS_REQUIRE(blocks < 0x7fffffffll, COCOS_ERR_UNSUPPORTED, "%s: %lld elements", name, total);
+    hipLaunchKernelGGL(gather_patches_subcell_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), img, idx, off, out, total, C,
+                       fh, fw, hk, wk, down, img_batch_stride);
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
 
 extern "C" int cocos_gather_patches(const float* img, const int* idx, float* out, int B, int C, int H, int W, int down,
                                     long long img_batch_stride, cocos_stream_t stream) {

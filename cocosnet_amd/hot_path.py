@@ -584,11 +584,22 @@ class MatchReadout:
     max_logit: torch.Tensor
     lse: torch.Tensor
     grid: tuple = None      # (gh, gw) of the side the indices point into; None = the same as index.shape[1:]
+    # with refine = r > 0 (K44): `offset` [B,2,fh,fw] the (x, y) soft-argmax offset, in cells, over the (2 r + 1)^2 window of the other
+    # side's grid around the match; `window_prob` [B,fh,fw] = exp(lse_win - lse), the share of the position's full softmax mass that
+    # lies in the window (meaningful when the refinement runs at the readout's temperature)
+    offset: torch.Tensor = None
+    window_prob: torch.Tensor = None
 
     def xy(self):
         """[B,2,fh,fw] int64: (x, y) of the match on the other side's grid — index = y * gw + x"""
         gw = (self.grid or tuple(self.index.shape[1:]))[1]
         return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=1)
+
+    def xy_sub(self):
+        """[B,2,fh,fw] fp32: the sub-cell position xy() + offset (a readout made with refine > 0)"""
+        if self.offset is None:
+            raise ValueError("MatchReadout.xy_sub: the readout holds no offset (correspondence_match(refine=r > 0) makes one)")
+        return self.xy().float() + self.offset
 
 
 @dataclass
@@ -610,7 +621,37 @@ class TopkMatchReadout:
         return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=2)
 
 
-def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows", topk=1):
+def _refine_scope(name: str, cfg: HotPathConfig, refine, refine_temperature, topk, has_exemplar: bool, channels=None):
+    """ValueError for a `refine` that is no radius, and — with refine > 0 — for everything outside the sub-cell refinement's scope (K44:
+    top-1 on the fused match_kernel-1 route, no prepared exemplar); checked before any tensor is looked at.  `channels`: the width of
+    theta / phi where the caller knows it."""
+    top = ops.MATCH_REFINE_MAX_RADIUS
+    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= top:
+        raise ValueError(f"{name}: refine={refine!r}: expected an integer in 0..{top} (0: no refinement)")
+    if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
+                                               and refine_temperature > 0):
+        raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+    if refine == 0:
+        return
+    if topk != 1:
+        raise ValueError(f"{name}: refine={refine} with topk={topk}: the refinement is built for the single best match (topk = 1)")
+    if has_exemplar:
+        raise ValueError(f"{name}: refine={refine} with a prepared exemplar is out of scope (not built)")
+    route = "the sub-cell refinement (refine > 0) runs on the fused match_kernel 1 route only"
+    if cfg.match_kernel != 1:
+        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope: {route}")
+    if not cfg.PONO_C:
+        raise ValueError(f"{name}: needs PONO_C: {route}")
+    if ops.PRECISION != "f16x3":
+        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope: {route}")
+    if not ops.MATCH_FUSED:
+        raise ValueError(f"{name}: ops.MATCH_FUSED = False (the materialised readout) is out of scope: {route}")
+    if channels is not None and channels != ops.FUSED_K:
+        raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}: {route}")
+
+
+def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows", topk=1, refine=0,
+                         refine_temperature=None):
     """The hard readout of the correlation of correspondence.py:272-304: argmax, maximum and log-sum-exp of every row of the scaled
     matrix f / temperature that forward(return_corr=True) returns (:305-306) — `direction="rows"`: per CONTENT position over the
     exemplar positions; "cols": per EXEMPLAR position over the content positions (the rows of f^T).  Returns a MatchReadout.
@@ -627,11 +668,19 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     `topk` = k > 1 (at most ops.MATCH_TOPK_MAX and the number of positions asked about, else ValueError) returns a TopkMatchReadout:
     the k best candidates per position.  The fused match_kernel-1 route then runs K39a (ops.corr_topk_ok(k); still nothing HWxHW)
     and the fused match_kernel-3 route K41 (ops.box3_topk_ok(k): the same one T, read once, K37's kernel with a candidate list per
-    lane); every other route materialises its logits and reads them in one sweep with K39b."""
+    lane); every other route materialises its logits and reads them in one sweep with K39b.
+
+    `refine` = r in 1..ops.MATCH_REFINE_MAX_RADIUS (K44; 0, the default, changes nothing) adds a sub-cell position to the top-1 readout:
+    a softmax at `refine_temperature` (None: `temperature`) over the logits of the (2 r + 1)^2 window of the other side's grid around
+    every match — positions outside the grid are left out — whose expected offset becomes MatchReadout.offset, with
+    MatchReadout.window_prob the window's share of the full softmax mass; the same operand planes serve the scan and the window.
+    Scope: topk = 1, no prepared exemplar, the fused match_kernel-1 route (PONO_C, 256 channels, COCOS_PRECISION=f16x3,
+    ops.MATCH_FUSED); everything else raises ValueError — nothing falls back."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
         raise ValueError(f"correspondence_match: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+    _refine_scope("correspondence_match", cfg, refine, refine_temperature, topk, exemplar is not None, theta_raw.shape[1])
     if (exemplar is None) == (phi_raw is None):
         raise ValueError("correspondence_match: pass phi_raw or a prepared exemplar in its place (not both)")
     B, C, fh, fw = theta_raw.shape
@@ -655,6 +704,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             raise ops._lib.CocosHipError("correspondence_match: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
         fused = (ops.MATCH_FUSED and mk == 1 and C == ops.FUSED_K and cfg.PONO_C and ops.corr_split_ok(B, C, N, Nk, 1, False)
                  and (k == 1 or ops.corr_topk_ok(k)))
+        if refine and not fused:
+            raise ValueError(f"correspondence_match: refine={refine}: the fused match_kernel 1 route does not take B={B}, {fh}x{fw} content "
+                             f"and {gh}x{gw} exemplar positions (ops.corr_split_ok), and the refinement runs on no other route")
+        off = lse_win = None
         if fused and exemplar is not None:
             # the query side as _attention_with_exemplar makes it; the record's key planes are read in place
             if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
@@ -676,6 +729,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
             if k == 1:
                 idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
+                if refine:      # K44: the window scores come from the operand planes that chose the centre
+                    inv_rt = inv_t if refine_temperature is None else 1.0 / refine_temperature
+                    asks, other_side, kgrid = (qn, kn, (gh, gw)) if rows else (kn, qn, (fh, fw))
+                    off, lse_win = ops.match_refine(asks, other_side, idx, kgrid, inv_rt, refine, planes)
             else:
                 idx, mx, lse = ops.corr_topk(qn, kn, inv_t, k, planes) if rows else ops.corr_topk(kn, qn, inv_t, k, planes)
         elif ((k == 1 or ops.box3_topk_ok(k)) and ops.MATCH_FUSED and mk == 3 and cfg.PONO_C and (gh, gw) == (fh, fw)
@@ -708,8 +765,12 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             val = rank_first(mx)
             return TopkMatchReadout(index=rank_first(idx.to(torch.int64)), prob=torch.exp(val - lse.unsqueeze(1)), logit=val, lse=lse,
                                     grid=other)
-        return MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
-                            max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)
+        m = MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
+                         max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)
+        if refine:
+            m.offset = off.reshape(shape + (2,)).permute(0, 3, 1, 2).contiguous()
+            m.window_prob = torch.exp(lse_win - lse).reshape(shape)
+        return m
 
 
 # ---- K42: differentiable k-sparse warp over the top-k matches ---------------------------------------------------------------------

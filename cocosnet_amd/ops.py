@@ -1328,7 +1328,99 @@ def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=
 
 
 # ------------------------------------------------------------------------------------------
-# K3  materialised correlation         (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
+# K44  sub-cell match refinement: a soft-argmax over the window around a hard match, and the warp sampled there
+# ------------------------------------------------------------------------------------------
+#: the largest window radius of match_refine (COCOS_MATCH_REFINE_MAX_RADIUS of cocos_hip.h)
+MATCH_REFINE_MAX_RADIUS = _lib.CONSTANTS["COCOS_MATCH_REFINE_MAX_RADIUS"]
+
+
+def _refine_grid(name: str, what: str, grid):
+    try:
+        h, w = grid
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: {what}={grid!r}: expected (rows, columns)") from None
+    if not (_is_int(h) and _is_int(w) and h >= 1 and w >= 1):
+        raise ValueError(f"{name}: {what}={grid!r}: expected two positive integers")
+    return h, w
+
+
+def _refine_table(name: str, idx, B, Nq):
+    """the centre table of K44 -> int32 [B,Nq] contiguous (TypeError / ValueError first, then the device)"""
+    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: idx must be an int32 or int64 tensor")
+    if idx.shape[0] != B or idx.numel() != B * Nq:
+        raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
+    if not idx.is_cuda:
+        raise _lib.CocosHipError(f"{name}: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    # (int64 tables are narrowed after a clamp into int32's range, which keeps every value on its side of the grid: the kernels clamp)
+    return (idx if idx.dtype == torch.int32 else idx.clamp(-1, 2 ** 31 - 1).to(torch.int32)).reshape(B, Nq).contiguous()
+
+
+def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):
+    """Sub-cell refinement of a hard match (K44; forward only) -> (off [B,Nq,2] fp32, x first; lse_win [B,Nq]): per query a softmax
+    over the logits <qn[b,:,i], kn[b,:,j]> * inv_t of the keys j in the (2 radius + 1)^2 window around idx[b,i] on the `kgrid` =
+    (hk, wk) key grid — positions outside the grid are left out — and its expected offset (sum p dx, sum p dy), in cells; lse_win is
+    the window's log-sum-exp.  qn [B,256,Nq], kn [B,256,hk*wk] as corr_match takes them (fp32 unit-norm columns, or handles
+    registered in `planes`); idx [B,Nq] (or [B,h,w]) int32 / int64, values outside the key grid are clamped into it.  The logits are
+    sparse_softmax_warp's for the same pairs, bit for bit.  radius in 1..MATCH_REFINE_MAX_RADIUS, inv_t > 0: ValueError before the
+    library is called."""
+    name = "match_refine"
+    hk, wk = _refine_grid(name, "kgrid", kgrid)
+    if not _is_int(radius) or not 1 <= radius <= MATCH_REFINE_MAX_RADIUS:
+        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{MATCH_REFINE_MAX_RADIUS}")
+    if not inv_t > 0:
+        raise ValueError(f"{name}: inv_t={inv_t!r}: expected a positive number")
+    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[:2] != kn.shape[:2] or kn.shape[2] != hk * wk:
+        raise ValueError(f"{name}: qn{tuple(qn.shape)} kn{tuple(kn.shape)} do not fit a {hk}x{wk} key grid "
+                         "(expected qn [B,256,Nq], kn [B,256,hk*wk])")
+    if qn.shape[1] != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    B, _, Nq = qn.shape
+    if planes is None:
+        planes = OperandPlanes()
+    _patchmatch_device(name, qn, kn)
+    with torch.no_grad():
+        idx = _refine_table(name, idx, B, Nq)
+        qh, ql, kh, kl = _patchmatch_planes(name, qn, kn, planes)
+        off = torch.empty((B, Nq, 2), device=qh.device, dtype=torch.float32)
+        lse_win = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+        _call("match_refine", "cocos_match_refine_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
+              off.data_ptr(), lse_win.data_ptr(), B, qh.shape[2], Nq, hk * wk, hk, wk, radius, float(inv_t), SPLIT_OPERAND_SCALE,
+              _stream())
+    return off, lse_win
+
+
+def gather_patches_subcell(img: torch.Tensor, idx: torch.Tensor, off: torch.Tensor, grid, kgrid, down: int):
+    """gather_patches at a sub-cell position (K44; forward only): out [B,C,fh*down,fw*down] whose cell (y, x) of the `grid` = (fh, fw)
+    samples img bilinearly where its match idx[b, y*fw+x] on the `kgrid` = (hk, wk) grid, moved by off[b, y*fw+x] = (off_x, off_y)
+    cells, puts it (sample positions are clamped into the image).  img [Be,C,hk*down,wk*down] fp32, Be == B or 1; idx [B,fh*fw] or
+    [B,fh,fw] int32 / int64 (values outside the key grid are clamped into it); off [B,fh*fw,2] fp32, x first, as match_refine returns
+    it.  With off == 0 the output is gather_patches' copy, bit for bit."""
+    name = "gather_patches_subcell"
+    fh, fw = _refine_grid(name, "grid", grid)
+    hk, wk = _refine_grid(name, "kgrid", kgrid)
+    if not _is_int(down) or down < 1:
+        raise ValueError(f"{name}: down={down!r}: expected an integer >= 1")
+    if not torch.is_tensor(off) or off.dtype != torch.float32:
+        raise TypeError(f"{name}: off must be a float32 tensor")
+    if img.dim() != 4 or tuple(img.shape[2:]) != (hk * down, wk * down):
+        raise ValueError(f"{name}: img{tuple(img.shape)} is not a [Be,C,{hk * down},{wk * down}] image (a {hk}x{wk} grid with down={down})")
+    B = off.shape[0]
+    if tuple(off.shape) != (B, fh * fw, 2) or img.shape[0] not in (B, 1):
+        raise ValueError(f"{name}: off{tuple(off.shape)} img{tuple(img.shape)}: expected off [B,{fh * fw},2] and an image batch of B or 1")
+    img = _chk(img.detach(), f"{name}: img")
+    with torch.no_grad():
+        idx = _refine_table(name, idx, B, fh * fw)
+        off = _chk(off.detach(), f"{name}: off")
+        Be, C = img.shape[:2]
+        out = torch.empty((B, C, fh * down, fw * down), device=img.device, dtype=torch.float32)
+        _call("gather_patches_subcell", "cocos_gather_patches_subcell", img.data_ptr(), idx.data_ptr(), off.data_ptr(), out.data_ptr(), B,
+              C, fh, fw, hk, wk, down, C * hk * down * wk * down if Be == B else 0, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# K3  materialised correlation        (correspondence.py:291 + :304; return_corr / WTA / mk != 1)
 # ------------------------------------------------------------------------------------------
 class _CorrMaterialize(torch.autograd.Function):
     @staticmethod

@@ -1319,6 +1319,35 @@ int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const void* kh, 
                                 int* idx_out, float* val_out, int B, int K, int hq, int wq, int hk, int wk, int k, int stride, int radii,
                                 int radius0, int seed, int iteration, float inv_temperature, float operand_scale, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K44 Sub-cell match refinement (match_refine_f16x3.hip, gather_patches.hip): a soft-argmax over the window of keys around a hard
+ *     match, and the full-resolution warp sampled at the refined position.
+ *   cocos_match_refine_f16x3: qh, ql [B,Nq,256], kh, kl [B,Nk,256] operand planes and score arithmetic as K42 / K43 (the logit
+ *     cocos_sparse_softmax_warp_fwd_f16x3 forms for the same pair, bit for bit); idx [B,Nq] int32 the centre key of every query,
+ *     clamped into [0, Nk) first, at (yk, xk) of the hk x wk key grid (hk wk == Nk).  The window is the keys (yk + dy, xk + dx),
+ *     |dy|, |dx| <= radius, INSIDE the grid (a position outside is left out: neither clamped nor wrapped), visited dy ascending
+ *     outside, dx ascending inside.  With s the window's logits: m = max s, lse_win = m + log sum exp(s - m), p = exp(s - lse_win),
+ *     off = (sum p dx, sum p dy) in visiting order, limited to [-radius, radius] (the rounded p may sum to an ulp above 1).
+ *     off [B,Nq,2] fp32, x first; lse_win [B,Nq] fp32.  Non-finite
+ *     scores are not sanitised (they make lse_win and off NaN).  No atomics: bitwise reproducible.
+ *     A null pointer, a non-positive size, hk wk != Nk, radius outside 1..COCOS_MATCH_REFINE_MAX_RADIUS, non-positive inv_temperature /
+ *     operand_scale, misaligned planes: COCOS_ERR_INVALID; K != 256, B Nq or B Nk at or above the 32-bit tables: COCOS_ERR_UNSUPPORTED
+ *     — all before any HIP call.
+ *   cocos_gather_patches_subcell: cocos_gather_patches at a sub-cell position.  img [B or 1,C,hk down,wk down] (img_batch_stride as
+ *     cocos_gather_patches), idx [B,fh fw] int32 (clamped into [0, hk wk)), off [B,fh fw,2] as above, out [B,C,fh down,fw down].  For
+ *     pixel (Y, X) of cell (Y / down, X / down):  sx = (xk + off_x) down + X % down clamped into [0, wk down - 1], x0 = floor(sx),
+ *     fx = sx - x0, x1 = min(x0 + 1, wk down - 1), y likewise;  out = top + fy (bottom - top), top = v00 + fx (v01 - v00),
+ *     bottom = v10 + fx (v11 - v10), no contraction: with off == 0 the output is cocos_gather_patches' copy.  floor(sx) and fx are formed from the integer xk down + X % down and from off_x down
+ *     separately (no fp32 rounding of the position for a power-of-two down).  A non-finite offset makes the cell's pixels NaN.  Null pointers, non-positive sizes, a batch stride that is neither 0 nor dense: COCOS_ERR_INVALID; an image
+ *     side of 2^24 pixels or more, a launch grid above 2^31 blocks: COCOS_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------- */
+#define COCOS_MATCH_REFINE_MAX_RADIUS 3
+int cocos_match_refine_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* idx, float* off, float* lse_win,
+                             int B, int K, int Nq, int Nk, int hk, int wk, int radius, float inv_temperature, float operand_scale,
+                             cocos_stream_t stream);
+int cocos_gather_patches_subcell(const float* img, const int* idx, const float* off, float* out, int B, int C, int fh, int fw, int hk,
+                                 int wk, int down, long long img_batch_stride, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
