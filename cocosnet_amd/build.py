@@ -72,6 +72,7 @@ HIP_SOURCES = [
     "sparse_warp_f16x3.hip",
     "patchmatch_f16x3.hip",
     "match_refine_f16x3.hip",
+    "match_refine_bwd_f16x3.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

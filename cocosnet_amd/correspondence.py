@@ -24,8 +24,8 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _refine_scope, _sparse_scope, _sparse_search, correspondence_hot_path, correspondence_match,
-                       correspondence_sparse)
+from .hot_path import (HotPathConfig, _flow_scope, _refine_scope, _sparse_scope, _sparse_search, correspondence_flow,
+                       correspondence_hot_path, correspondence_match, correspondence_sparse)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -358,6 +358,25 @@ class NoVGGCorrespondence(NetworkBase):
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, search=search,
                                               search_opts=search_opts))
+        return coor_out
+
+    def flow_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, radius=1, refine_temperature=None):
+        """The trainable sub-cell correspondence (hot_path.correspondence_flow): per content position the best exemplar position is
+        selected without gradient, a softmax at `refine_temperature` (None: `temperature`) over the (2 radius + 1)^2 window around it
+        gives a sub-cell offset, and ref_img is sampled bilinearly at the refined position — with gradients to the whole network
+        through theta and phi (none to ref_img), so a photometric loss on warp_out or a regression loss on match_offset trains the
+        field below the feature grid.  Returns {warp_out [B,3,H,W], match_index [B,h,w] int64, match_offset [B,2,h,w],
+        match_xy_sub [B,2,h,w], match_window_prob [B,h,w]} (+ loss_novgg_featpair where project() makes it); match_index and
+        match_offset are match(refine=radius)'s bit for bit.  Scope: sparse_warp's (match_kernel 1 with PONO_C on the plain flag set),
+        radius in 1..3; everything else raises ValueError before the network runs.  forward() and match() are unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _flow_scope(cfg, radius, refine_temperature)      # out-of-scope flags are refused before the network runs
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("flow_warp: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        coor_out = {}
+        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        coor_out.update(correspondence_flow(theta_raw, phi_raw, ref_img, cfg, temperature, radius=radius,
+                                            refine_temperature=refine_temperature))
         return coor_out
 
 

@@ -909,3 +909,79 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     out["match_index"] = rank_first(idx.to(torch.int64))
     out["match_weight"] = rank_first(w)
     return out
+
+
+# ---- K46: trainable sub-cell correspondence (a flow-style readout with gradients) --------------------------------------------------
+def _flow_scope(cfg: HotPathConfig, radius, refine_temperature):
+    """ValueError for everything outside correspondence_flow's scope: correspondence_sparse's flag checks (_sparse_scope, in its words),
+    then the window radius and the refinement temperature; checked before any tensor is looked at"""
+    _sparse_scope(cfg, 1)
+    name, top = "correspondence_flow", ops.MATCH_REFINE_MAX_RADIUS
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
+        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
+    if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
+                                               and refine_temperature > 0):
+        raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+
+
+def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, temperature=0.01, *, radius=1, refine_temperature=None,
+                        exemplar=None):
+    """The trainable sub-cell correspondence (K46): per content position the best exemplar position is SELECTED without gradient (the
+    top-1 of ops.corr_topk: correspondence_match's centre), a softmax at `refine_temperature` (None: `temperature`) over the
+    (2 radius + 1)^2 window of exemplar positions around it gives a sub-cell offset — ops.soft_match_offset, with gradients to
+    theta_raw and phi_raw through the producer of the operand planes, which serve selection and refinement alike — and the exemplar
+    is sampled bilinearly at the refined position — ops.subcell_warp, with a gradient to the offset.  A photometric loss on warp_out
+    or a regression loss on match_offset therefore trains theta and phi below the feature grid.  Nothing HWxHW is allocated.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1; the planes are made as correspondence_match makes them (K23 from a
+    lazy pair it takes, K1 otherwise), so match_index and match_offset are correspondence_match(refine=radius)'s bit for bit.
+    ref_img [B,3,H,W] gets no gradient (one that requires it raises ValueError).  Returns {warp_out [B,3,H,W], match_index [B,h,w]
+    int64, match_offset [B,2,h,w] (x, y; in cells; with gradient), match_xy_sub [B,2,h,w] = match_xy + match_offset (with gradient),
+    match_window_prob [B,h,w] (the window's share of the softmax mass; no gradient)}.
+
+    Scope and refusals: correspondence_sparse's (match_kernel 1, PONO_C, the plain flag set, COCOS_PRECISION=f16x3, 256 channels,
+    positions a multiple of 4, no prepared exemplar), radius in 1..ops.MATCH_REFINE_MAX_RADIUS: everything else raises ValueError — there
+    is no fall-back route.  CPU tensors raise CocosHipError."""
+    name = "correspondence_flow"
+    _flow_scope(cfg, radius, refine_temperature)
+    if exemplar is not None:
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the refinement differentiates phi)")
+    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
+    if lazy[0] != lazy[1]:
+        raise TypeError(f"{name}: theta and phi must both be tensors or both be ops.LazyProj1x1")
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    N, Nk, down = fh * fw, gh * gw, cfg.down
+    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
+        raise ValueError(f"{name}: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
+                         f"{tuple(phi_raw.shape)}")
+    if ref_img.dim() != 4 or ref_img.shape[0] != B or tuple(ref_img.shape[2:]) != (gh * down, gw * down):
+        raise ValueError(f"{name}: ref_img {tuple(ref_img.shape)} is not a batch of {B} images of down={down} times the exemplar grid "
+                         f"{(gh, gw)}")
+    if ref_img.requires_grad:
+        raise ValueError(f"{name}: ref_img requires a gradient, and the gradient to the exemplar image is not built (pass ref_img.detach())")
+    if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(1):
+        raise ValueError(f"{name}: the fused readout does not take B={B}, {N} x {Nk} positions (positions must be multiples of 4)")
+    planes = ops.OperandPlanes()
+    keep = torch.is_grad_enabled() and (theta_raw.requires_grad or phi_raw.requires_grad)
+    if all(lazy) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw) and ops.proj_norm_fused_ok(phi_raw):
+        qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw, phi_raw, 1, planes, want_chan=keep)      # K23, as correspondence_match
+    else:
+        if all(lazy):
+            theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
+        qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
+        kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    inv_t = 1.0 / temperature
+    inv_rt = inv_t if refine_temperature is None else 1.0 / refine_temperature
+    with torch.no_grad():
+        idx, _, lse = ops.corr_topk(qn, kn, inv_t, 1, planes)                  # selection: no gradient
+        idx = idx.reshape(B, N)
+    off, lse_win = ops.soft_match_offset(qn, kn, idx, (gh, gw), inv_rt, radius, planes)
+    warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
+    index = idx.to(torch.int64).reshape(B, fh, fw)
+    offset = off.reshape(B, fh, fw, 2).permute(0, 3, 1, 2).contiguous()
+    xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
+    return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
+            "match_window_prob": torch.exp(lse_win.detach() - lse.reshape(B, N)).reshape(B, fh, fw)}

@@ -1356,15 +1356,8 @@ def _refine_table(name: str, idx, B, Nq):
     return (idx if idx.dtype == torch.int32 else idx.clamp(-1, 2 ** 31 - 1).to(torch.int32)).reshape(B, Nq).contiguous()
 
 
-def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):
-    """Sub-cell refinement of a hard match (K44; forward only) -> (off [B,Nq,2] fp32, x first; lse_win [B,Nq]): per query a softmax
-    over the logits <qn[b,:,i], kn[b,:,j]> * inv_t of the keys j in the (2 radius + 1)^2 window around idx[b,i] on the `kgrid` =
-    (hk, wk) key grid — positions outside the grid are left out — and its expected offset (sum p dx, sum p dy), in cells; lse_win is
-    the window's log-sum-exp.  qn [B,256,Nq], kn [B,256,hk*wk] as corr_match takes them (fp32 unit-norm columns, or handles
-    registered in `planes`); idx [B,Nq] (or [B,h,w]) int32 / int64, values outside the key grid are clamped into it.  The logits are
-    sparse_softmax_warp's for the same pairs, bit for bit.  radius in 1..MATCH_REFINE_MAX_RADIUS, inv_t > 0: ValueError before the
-    library is called."""
-    name = "match_refine"
+def _refine_operands(name: str, qn, kn, kgrid, inv_t, radius):
+    """the checks of the window soft-argmax's arguments (K44, K46) -> (hk, wk); ValueError before the library is called"""
     hk, wk = _refine_grid(name, "kgrid", kgrid)
     if not _is_int(radius) or not 1 <= radius <= MATCH_REFINE_MAX_RADIUS:
         raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{MATCH_REFINE_MAX_RADIUS}")
@@ -1375,6 +1368,19 @@ def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandP
                          "(expected qn [B,256,Nq], kn [B,256,hk*wk])")
     if qn.shape[1] != FUSED_K:
         raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    return hk, wk
+
+
+def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):
+    """Sub-cell refinement of a hard match (K44; forward only) -> (off [B,Nq,2] fp32, x first; lse_win [B,Nq]): per query a softmax
+    over the logits <qn[b,:,i], kn[b,:,j]> * inv_t of the keys j in the (2 radius + 1)^2 window around idx[b,i] on the `kgrid` =
+    (hk, wk) key grid — positions outside the grid are left out — and its expected offset (sum p dx, sum p dy), in cells; lse_win is
+    the window's log-sum-exp.  qn [B,256,Nq], kn [B,256,hk*wk] as corr_match takes them (fp32 unit-norm columns, or handles
+    registered in `planes`); idx [B,Nq] (or [B,h,w]) int32 / int64, values outside the key grid are clamped into it.  The logits are
+    sparse_softmax_warp's for the same pairs, bit for bit.  radius in 1..MATCH_REFINE_MAX_RADIUS, inv_t > 0: ValueError before the
+    library is called."""
+    name = "match_refine"
+    hk, wk = _refine_operands(name, qn, kn, kgrid, inv_t, radius)
     B, _, Nq = qn.shape
     if planes is None:
         planes = OperandPlanes()
@@ -1390,13 +1396,8 @@ def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandP
     return off, lse_win
 
 
-def gather_patches_subcell(img: torch.Tensor, idx: torch.Tensor, off: torch.Tensor, grid, kgrid, down: int):
-    """gather_patches at a sub-cell position (K44; forward only): out [B,C,fh*down,fw*down] whose cell (y, x) of the `grid` = (fh, fw)
-    samples img bilinearly where its match idx[b, y*fw+x] on the `kgrid` = (hk, wk) grid, moved by off[b, y*fw+x] = (off_x, off_y)
-    cells, puts it (sample positions are clamped into the image).  img [Be,C,hk*down,wk*down] fp32, Be == B or 1; idx [B,fh*fw] or
-    [B,fh,fw] int32 / int64 (values outside the key grid are clamped into it); off [B,fh*fw,2] fp32, x first, as match_refine returns
-    it.  With off == 0 the output is gather_patches' copy, bit for bit."""
-    name = "gather_patches_subcell"
+def _subcell_shapes(name: str, img, off, grid, kgrid, down):
+    """the checks of the sub-cell gather's arguments (K44, K46) -> (fh, fw, hk, wk, B); TypeError / ValueError before the library is called"""
     fh, fw = _refine_grid(name, "grid", grid)
     hk, wk = _refine_grid(name, "kgrid", kgrid)
     if not _is_int(down) or down < 1:
@@ -1408,6 +1409,17 @@ def gather_patches_subcell(img: torch.Tensor, idx: torch.Tensor, off: torch.Tens
     B = off.shape[0]
     if tuple(off.shape) != (B, fh * fw, 2) or img.shape[0] not in (B, 1):
         raise ValueError(f"{name}: off{tuple(off.shape)} img{tuple(img.shape)}: expected off [B,{fh * fw},2] and an image batch of B or 1")
+    return fh, fw, hk, wk, B
+
+
+def gather_patches_subcell(img: torch.Tensor, idx: torch.Tensor, off: torch.Tensor, grid, kgrid, down: int):
+    """gather_patches at a sub-cell position (K44; forward only): out [B,C,fh*down,fw*down] whose cell (y, x) of the `grid` = (fh, fw)
+    samples img bilinearly where its match idx[b, y*fw+x] on the `kgrid` = (hk, wk) grid, moved by off[b, y*fw+x] = (off_x, off_y)
+    cells, puts it (sample positions are clamped into the image).  img [Be,C,hk*down,wk*down] fp32, Be == B or 1; idx [B,fh*fw] or
+    [B,fh,fw] int32 / int64 (values outside the key grid are clamped into it); off [B,fh*fw,2] fp32, x first, as match_refine returns
+    it.  With off == 0 the output is gather_patches' copy, bit for bit."""
+    name = "gather_patches_subcell"
+    fh, fw, hk, wk, B = _subcell_shapes(name, img, off, grid, kgrid, down)
     img = _chk(img.detach(), f"{name}: img")
     with torch.no_grad():
         idx = _refine_table(name, idx, B, fh * fw)
@@ -1417,6 +1429,115 @@ def gather_patches_subcell(img: torch.Tensor, idx: torch.Tensor, off: torch.Tens
         _call("gather_patches_subcell", "cocos_gather_patches_subcell", img.data_ptr(), idx.data_ptr(), off.data_ptr(), out.data_ptr(), B,
               C, fh, fw, hk, wk, down, C * hk * down * wk * down if Be == B else 0, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# K46  trainable sub-cell correspondence: gradients of the window soft-argmax (to qn, kn) and of the bilinear warp (to the offset)
+# ------------------------------------------------------------------------------------------
+class _SoftMatchOffset(torch.autograd.Function):
+    """K44's readout with K46's backward.  qn / kn are only the autograd inputs (fp32 tensors or producer handles): the kernels read
+    their position-major operand planes.  Saved for the backward: the four planes and idx [B,Nq] — nothing with an Nq x Nk extent (the
+    window's logits are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, idx, inv_t: float, radius: int, hk: int, wk: int, qh, ql, kh, kl):
+        B, Nq, K = qh.shape
+        off = torch.empty((B, Nq, 2), device=qh.device, dtype=torch.float32)
+        lse_win = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+        _call("match_refine", "cocos_match_refine_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
+              off.data_ptr(), lse_win.data_ptr(), B, K, Nq, hk * wk, hk, wk, radius, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+        ctx.save_for_backward(qh, ql, kh, kl, idx)
+        ctx.cfg = (float(inv_t), radius, hk, wk)
+        ctx.mark_non_differentiable(lse_win)
+        return off, lse_win
+
+    @staticmethod
+    def backward(ctx, doff, _dlse):
+        qh, ql, kh, kl, idx = ctx.saved_tensors
+        inv_t, radius, hk, wk = ctx.cfg
+        need_q, need_k = ctx.needs_input_grad[:2]
+        dqn = dkn = None
+        if need_q or need_k:
+            B, Nq, K = qh.shape
+            Nk, slots = hk * wk, (2 * radius + 1) ** 2
+            doff = _chk(doff, "soft_match_offset: doff")
+            dims = (B, K, Nq, Nk, hk, wk, radius, inv_t, SPLIT_OPERAND_SCALE, _stream())
+            ds = torch.empty((B, Nq, slots), device=doff.device, dtype=torch.float32)
+            dq_t = torch.empty((B, Nq, K), device=doff.device, dtype=torch.float32) if need_q else None
+            _call("match_refine_bwd_query", "cocos_match_refine_bwd_query_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+                  idx.data_ptr(), doff.data_ptr(), ds.data_ptr(), _ptr(dq_t), *dims)
+            if need_q:
+                dqn = _transpose(dq_t)
+                del dq_t
+            if need_k:      # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
+                entries, offsets = _inverse_index_table(idx.view(B, Nq, 1), Nk)
+                dk_t = torch.empty((B, Nk, K), device=doff.device, dtype=torch.float32)
+                _call("match_refine_bwd_key", "cocos_match_refine_bwd_key_f16x3", qh.data_ptr(), ql.data_ptr(), ds.data_ptr(),
+                      entries.data_ptr(), offsets.data_ptr(), dk_t.data_ptr(), *dims)
+                dkn = _transpose(dk_t)
+        return dqn, dkn, None, None, None, None, None, None, None, None, None
+
+
+def soft_match_offset(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):
+    """match_refine with gradients (K46) -> (off [B,Nq,2], lse_win [B,Nq]), both match_refine's bit for bit: the expected offset of the
+    softmax over the (2 radius + 1)^2 window of keys around idx[b,i], differentiable in qn and kn (each gradient computed only when
+    needed; idx is data, lse_win carries no gradient).  The forward's limit of off to [-radius, radius] only absorbs an ulp of rounding:
+    the backward treats it as the identity.  Nothing Nq x Nk is allocated, forward or backward; dkn is gathered over the inverse table
+    of the centres in a fixed order (no atomics: bitwise reproducible; a centre all queries share is one serial list per key around it).
+    Arguments and errors as match_refine."""
+    name = "soft_match_offset"
+    hk, wk = _refine_operands(name, qn, kn, kgrid, inv_t, radius)
+    B, _, Nq = qn.shape
+    if planes is None:
+        planes = OperandPlanes()
+    _patchmatch_device(name, qn, kn)
+    qn, kn = (t if planes.has(t) else _chk(t, f"{name}: {what}") for t, what in ((qn, "qn"), (kn, "kn")))
+    with torch.no_grad():
+        idx = _refine_table(name, idx, B, Nq).clamp(0, hk * wk - 1)      # the kernels clamp as well: the table the key side inverts
+        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
+        if pl[2].shape[0] != pl[0].shape[0]:
+            raise ValueError(f"{name}: query and key batch differ")
+    return _SoftMatchOffset.apply(qn, kn, idx, float(inv_t), radius, hk, wk, *pl)
+
+
+class _SubcellWarp(torch.autograd.Function):
+    """K44's sub-cell gather with K46's gradient to the offset (none to the image: subcell_warp refuses one that asks)."""
+
+    @staticmethod
+    def forward(ctx, off, img, idx, fh: int, fw: int, hk: int, wk: int, down: int):
+        B, (Be, C) = off.shape[0], img.shape[:2]
+        out = torch.empty((B, C, fh * down, fw * down), device=img.device, dtype=torch.float32)
+        ctx.dims = (B, C, fh, fw, hk, wk, down, C * hk * down * wk * down if Be == B else 0)
+        _call("gather_patches_subcell", "cocos_gather_patches_subcell", img.data_ptr(), idx.data_ptr(), off.data_ptr(), out.data_ptr(),
+              *ctx.dims, _stream())
+        ctx.save_for_backward(img, idx, off)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        img, idx, off = ctx.saved_tensors
+        dout = _chk(dout, "subcell_warp: dout")
+        doff = torch.empty_like(off)
+        _call("gather_patches_subcell_bwd_off", "cocos_gather_patches_subcell_bwd_off", img.data_ptr(), idx.data_ptr(), off.data_ptr(),
+              dout.data_ptr(), doff.data_ptr(), *ctx.dims, _stream())
+        return (doff,) + (None,) * 7
+
+
+def subcell_warp(img: torch.Tensor, idx: torch.Tensor, off: torch.Tensor, grid, kgrid, down: int):
+    """gather_patches_subcell with a gradient to the offset (K46): out [B,C,fh*down,fw*down], gather_patches_subcell's bit for bit;
+    d out / d off is the slope of the bilinear sample along each axis, 0 where the sample is clamped at the image border (at an exact
+    pixel position: the right derivative).  The gradient to the image is not built: an `img` that requires one raises ValueError
+    (detach it) — nothing drops a gradient silently.  Arguments and errors as gather_patches_subcell."""
+    name = "subcell_warp"
+    fh, fw, hk, wk, B = _subcell_shapes(name, img, off, grid, kgrid, down)
+    if img.requires_grad:
+        raise ValueError(f"{name}: img requires a gradient, and the gradient to the exemplar image is not built (pass img.detach())")
+    img, off = _chk(img, f"{name}: img"), _chk(off, f"{name}: off")
+    with torch.no_grad():
+        idx = _refine_table(name, idx, B, fh * fw)
+    return _SubcellWarp.apply(off, img, idx, fh, fw, hk, wk, down)
 
 
 # ------------------------------------------------------------------------------------------

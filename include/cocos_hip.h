@@ -1348,6 +1348,44 @@ int cocos_match_refine_f16x3(const void* qh, const void* ql, const void* kh, con
 int cocos_gather_patches_subcell(const float* img, const int* idx, const float* off, float* out, int B, int C, int fh, int fw, int hk,
                                  int wk, int down, long long img_batch_stride, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K46 Gradients of the sub-cell refinement (match_refine_bwd_f16x3.hip, gather_patches.hip): K44's offset becomes trainable — the
+ *     backward of cocos_match_refine_f16x3 to the two operands and of cocos_gather_patches_subcell to the offset.
+ *     Common to the two match kernels: planes, idx, grids, radius and scales as cocos_match_refine_f16x3; W = (2 radius + 1)^2 window
+ *     slots per query, slot s = (dy + radius) (2 radius + 1) + (dx + radius); ds [B,Nq,W] fp32; dq_t [B,Nq,256], dk_t [B,Nk,256]
+ *     POSITION-major fp32, 16-byte aligned (cocos_transpose_f32 turns them into the channel-major gradients).  fp32 in a fixed order,
+ *     contraction off, no atomics: bitwise reproducible.  A null pointer, a non-positive size, hk wk != Nk, radius outside
+ *     1..COCOS_MATCH_REFINE_MAX_RADIUS, non-positive inv_temperature / operand_scale, misaligned planes: COCOS_ERR_INVALID; K != 256,
+ *     B Nq W or B Nk at or above 2^31: COCOS_ERR_UNSUPPORTED — all before any HIP call.
+ *   cocos_match_refine_bwd_query_f16x3: one wave per query.  Recomputes the window's logits as cocos_match_refine_f16x3 forms them, bit
+ *     for bit (membership, visiting order, arithmetic), p = exp(s - m) / sum exp(s - m) (= exp(s - lse_win), formed without the
+ *     rounding of lse_win) and the expectation o = (sum p dx, sum p dy) WITHOUT the
+ *     forward's limit to [-radius, radius]: that limit only absorbs an ulp of rounding and is treated as the identity.  With doff
+ *     [B,Nq,2] the incoming gradient of off:  ds_s = p_s ((dx_s - o_x) doff_x + (dy_s - o_y) doff_y), 0 for a slot outside the key
+ *     grid — every slot is written; unless dq_t is null, dq_t[i] = inv_temperature sum_s ds_s kn[j_s], slots ascending.
+ *   cocos_match_refine_bwd_key_f16x3: one wave per key j at (yj, xj), a gather: for dy ascending, then dx ascending, the centre
+ *     c = (yj - dy, xj - dx) (skipped outside the grid) and, for every query i of c's group in table order,
+ *     dk_t[j] += inv_temperature ds[i, s(dy, dx)] qn[i].  entries [B Nq] / offsets [B Nk + 1] int32 are the inverse table of the
+ *     CLAMPED centre table as cocos_sparse_softmax_warp_bwd_key_f16x3 takes it with k = 1 (rows b Nq + i grouped by the centre
+ *     b Nk + j they name, ascending).  A key in nobody's window gets zeros, written by the kernel.  Table positions and offsets are
+ *     clamped into the tables.  A centre all queries share is one serial list for each key around it.
+ *   cocos_gather_patches_subcell_bwd_off: img, idx, off, sizes and img_batch_stride as cocos_gather_patches_subcell; dout
+ *     [B,C,fh down,fw down]; doff [B,fh fw,2] = per cell the sum over its C down^2 pixels of dout * d out / d off, with the integer
+ *     pixel and the fraction formed exactly as the forward forms them:  d out / d off_x = down ((1 - fy) (v01 - v00) + fy (v11 - v10)),
+ *     d out / d off_y = down (bottom - top), each 0 where that axis' clamp acted (the sample left of 0 or at or beyond the last column
+ *     / row).  At an exact integer off down the segment [x0, x0 + 1] is used (the right derivative, consistent with floor).  One wave
+ *     per cell, a lane-strided loop and a xor butterfly: a fixed order, no atomics.  The image gradient is not built.  Errors as
+ *     cocos_gather_patches_subcell.
+ * ------------------------------------------------------------------------------------- */
+int cocos_match_refine_bwd_query_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* idx, const float* doff,
+                                       float* ds, float* dq_t /* nullable */, int B, int K, int Nq, int Nk, int hk, int wk, int radius,
+                                       float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_match_refine_bwd_key_f16x3(const void* qh, const void* ql, const float* ds, const int* entries, const int* offsets, float* dk_t,
+                                     int B, int K, int Nq, int Nk, int hk, int wk, int radius, float inv_temperature, float operand_scale,
+                                     cocos_stream_t stream);
+int cocos_gather_patches_subcell_bwd_off(const float* img, const int* idx, const float* off, const float* dout, float* doff, int B, int C,
+                                         int fh, int fw, int hk, int wk, int down, long long img_batch_stride, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
