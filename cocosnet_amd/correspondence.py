@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_scope, _refine_scope, _sparse_scope, _sparse_search, correspondence_flow,
+from .hot_path import (HotPathConfig, _flow_scope, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search, correspondence_flow,
                        correspondence_hot_path, correspondence_match, correspondence_sparse)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
@@ -271,7 +271,7 @@ class NoVGGCorrespondence(NetworkBase):
         return coor_out
 
     def match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, direction="rows", hard_warp=False, topk=1,
-              blend="topk", refine=0, refine_temperature=None):
+              blend="topk", refine=0, refine_temperature=None, restrict=None):
         """Where each position matched, and how sure the match is — the hard readout of the correlation that
         `forward(..., return_corr=True)` returns as a [B,HW,HW] matrix (:305-306), without that matrix wherever the fused
         match_kernel-1 back end runs, and with one HWxHW tensor (the x-box correlation T, read once) instead of two logit matrices
@@ -296,7 +296,16 @@ class NoVGGCorrespondence(NetworkBase):
         [B,2,h,w] (x, y; in cells, |offset| <= r), match_xy_sub = match_xy + match_offset (fp32) and match_window_prob [B,h,w], the
         window's share of the position's softmax mass; with `hard_warp` also warp_sub [B,3,H,W], ref_img sampled bilinearly at the
         refined position (warp_hard stays).  Scope: topk = 1, no prepared exemplar, the fused match_kernel-1 route (PONO_C,
-        COCOS_PRECISION=f16x3, ops.MATCH_FUSED); everything else raises ValueError before the network runs."""
+        COCOS_PRECISION=f16x3, ops.MATCH_FUSED); everything else raises ValueError before the network runs.
+
+        `restrict` (K47; None, the default, changes nothing): "label" picks every position's candidates only among the positions of
+        the other side that carry its class — the majority class of each feature cell of seg_map / ref_seg_map
+        (hot_path.cell_labels); a pair (q_labels [B,h,w], k_labels [B,h,w]) of int32 / int64 tensors, content side first, says
+        "this region takes from that region" with any labels (a negative content label: unrestricted).  match_prob and match_lse
+        are then over the ALLOWED positions, not all of them; warp_hard / warp_topk work unchanged from the restricted indices.  A
+        position whose label has fewer than topk positions on the other side falls back to the unrestricted scan; match_restricted
+        [B,h,w] bool says which positions were restricted.  Scope: the fused match_kernel-1 route (PONO_C, COCOS_PRECISION=f16x3,
+        ops.MATCH_FUSED), no prepared exemplar, refine = 0; everything else raises a ValueError naming restrict before the network runs."""
         if direction not in ("rows", "cols"):
             raise ValueError(f"match: direction {direction!r}: expected 'rows' or 'cols'")
         if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
@@ -306,6 +315,7 @@ class NoVGGCorrespondence(NetworkBase):
         if hard_warp and direction == "cols":
             raise ValueError("match: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _restrict_scope("match", cfg, restrict, exemplar is not None, refine, channels=self.inter_channels)
         _refine_scope("match", cfg, refine, refine_temperature, topk, exemplar is not None, self.inter_channels)
         keys = phi_raw = None
         with torch.no_grad():
@@ -322,9 +332,15 @@ class NoVGGCorrespondence(NetworkBase):
                 raise ValueError("match: ref_img and ref_seg_map are required without a prepared exemplar")
             if keys is None and phi_raw is None:      # (real_img: project() reads it for the training-time featpair term only)
                 theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
-            m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk, refine=refine,
-                                     refine_temperature=refine_temperature)
+            if restrict is None:
+                m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk, refine=refine,
+                                         refine_temperature=refine_temperature)
+            else:
+                m = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=keys, direction=direction, topk=topk, refine=refine,
+                                         refine_temperature=refine_temperature, restrict=restrict, seg_map=seg_map, ref_seg_map=ref_seg_map)
             out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse}
+            if restrict is not None:
+                out["match_restricted"] = m.restricted
             if refine:
                 out.update(match_offset=m.offset, match_xy_sub=m.xy_sub(), match_window_prob=m.window_prob)
             if hard_warp and topk == 1:
@@ -340,7 +356,8 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
         return out
 
-    def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, search="dense", search_opts=None):
+    def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, search="dense", search_opts=None,
+                    restrict=None):
         """The trainable k-sparse warp (hot_path.correspondence_sparse): per content position the `topk` best exemplar positions are
         selected without gradient, and a softmax over those k logits alone blends the pooled exemplar (and, under
         --warp_mask_losstype direct, the exemplar's labels) — attention over k keys instead of all HW, with gradients to the whole
@@ -348,16 +365,20 @@ class NoVGGCorrespondence(NetworkBase):
         match_index [B,k,h,w] int64, match_weight [B,k,h,w]} (+ loss_novgg_featpair where project() makes it).  Scope: match_kernel 1
         with PONO_C on the plain flag set; everything else raises ValueError (no fall-back).  forward() and match() are unaffected.
         `search` / `search_opts`: the candidate selector, "dense" (default: the scan over all keys) or "patchmatch" (K43) with its
-        schedule, as hot_path.correspondence_sparse takes them."""
+        schedule, as hot_path.correspondence_sparse takes them.  `restrict` (K47; None changes nothing): "label" or a pair of label
+        tensors, as match() takes them — the candidates come from the exemplar positions of the content position's label (dense
+        selector only), the result gains match_restricted [B,h,w], and the gradients are the same: the indices are data."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _restrict_scope("sparse_warp", cfg, restrict, False, 0, search, self.inter_channels)
         _sparse_scope(cfg, topk)                  # out-of-scope flags are refused before the network runs
         _sparse_search(search, search_opts)
         if ref_img is None or ref_seg_map is None:
             raise ValueError("sparse_warp: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        kw = {} if restrict is None else {"restrict": restrict}
         coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, search=search,
-                                              search_opts=search_opts))
+                                              search_opts=search_opts, **kw))
         return coor_out
 
     def flow_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, radius=1, refine_temperature=None):

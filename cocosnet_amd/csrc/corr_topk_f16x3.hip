@@ -64,10 +64,13 @@ __device__ __forceinline__ void topk_merge_sum_groups(float& m, float& l, float 
     m = mm;
 }
 
-template <int K>
+// LABELS (K47): q_label [B,Nq], k_label [B,Nk] (one [Nk] row when k_bstride is 0) int32; pair (i, j) is allowed when q_label[i] < 0 or
+// q_label[i] == k_label[j], every other logit is -inf before it meets the tile maximum, the list or the sum.  Without LABELS the two
+// pointers are not read (null).
+template <int K, bool LABELS>
 __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
     const _Float16* __restrict__ qh, const _Float16* __restrict__ ql, const _Float16* __restrict__ kh,
-    const _Float16* __restrict__ kl, int* __restrict__ idx_out, float* __restrict__ val_out, float* __restrict__ lse_out,
+    const _Float16* __restrict__ kl, const int* __restrict__ q_label, const int* __restrict__ k_label, int* __restrict__ idx_out, float* __restrict__ val_out, float* __restrict__ lse_out,
     int B, int Nq, int Nk, int k_out /* columns written: 1 .. K */, float scale_log2 /* inv_temperature * log2(e) / operand_scale^2 */,
     float scale_nat /* inv_temperature / operand_scale^2 */, size_t k_bstride /* halfs: Nk * 256, or 0 = one key set for all */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -121,6 +124,16 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
         *reinterpret_cast<u32x4*>(kt + (buf * 2 + pl) * CT_PLANE + k_lds[u]) = kst[pl][u];
     };
 
+    // ---- labels: the query's in a register (past Nq: unrestricted, never written); the keys' through a bounds-checked descriptor
+    //      over this sample's Nk labels — a lane's 16 keys are four runs of four, and since Nk % 4 == 0 a run lies wholly inside the
+    //      row or wholly past it (zeros, never dereferenced: those keys are -inf already)
+    int q_lab = -1;
+    __amdgpu_buffer_rsrc_t lab_rs;
+    if constexpr (LABELS) {
+        if (i_lane < Nq) q_lab = q_label[(size_t)b * Nq + i_lane];
+        lab_rs = make_rsrc(k_label + (k_bstride ? (size_t)b * Nk : (size_t)0), (size_t)Nk * 4);
+    }
+
     const int nstages = (Nk + CT_STAGE - 1) / CT_STAGE;
 #pragma unroll
     for (int i = 0; i < 8; ++i) fetch(i & 1, i >> 1, 0);
@@ -150,6 +163,7 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
         f32x16 sa;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sa[r] = 0.f;
+        u32x4 klab[4];           // labels of keys j0 + 8g + 4h .. + 3: rows 4g .. 4g + 3 of the accumulator
         // ---- S^T = K_tile . Q : 16 k-steps x 3 terms into one accumulator, in the forward kernel's order; the A fragments come
         //      from LDS RA - 1 steps ahead and the eight staged pieces of the next stage ride in the gaps, one every other step
 #pragma unroll
@@ -167,6 +181,11 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
                 commit(i & 1, i >> 1, buf ^ 1);
                 fetch(i & 1, i >> 1, jn);
             }
+            if constexpr (LABELS) {
+                // the tile's labels ride in the last steps, where no A fragment is fetched ahead any more and its registers are free
+                if (s >= NS - 4)
+                    klab[s - (NS - 4)] = __builtin_amdgcn_raw_buffer_load_b128(lab_rs, (j0 + 8 * (s - (NS - 4)) + 4 * h) * 4, 0, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- this lane's 16 keys: j0 + acc_row_base(r) + 4h, ascending in r.  Keys past Nk (zero rows: logit 0, which would beat
@@ -175,6 +194,11 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (j0 + acc_row_base(r) + 4 * h >= Nk) sa[r] = -INFINITY;
+        }
+        if constexpr (LABELS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (q_lab >= 0 && (int)klab[r >> 2][r & 3] != q_lab) sa[r] = -INFINITY;
         }
         float tmax = sa[0];
 #pragma unroll
@@ -245,17 +269,18 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
     }
 }
 
-template <int K>
+template <int K, bool LABELS = false>
 static int launch_corr_topk(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out, float* val_out,
                             float* lse_out, int B, int Nq, int Nk, int k, float inv_temperature, float operand_scale,
-                            long long k_batch_stride, cocos_stream_t stream) {
+                            long long k_batch_stride, cocos_stream_t stream, const int* q_label = nullptr,
+                            const int* k_label = nullptr) {
     const int nqb = (Nq + CT_BQ - 1) / CT_BQ;
     const float s2 = operand_scale * operand_scale;
-    auto kern = corr_topk_f16x3_kernel<K>;
+    auto kern = corr_topk_f16x3_kernel<K, LABELS>;
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT_SMEM));
     hipLaunchKernelGGL(kern, dim3(B * nqb), dim3(CT_THREADS), CT_SMEM, as_stream(stream), static_cast<const _Float16*>(qh),
-                       static_cast<const _Float16*>(ql), static_cast<const _Float16*>(kh), static_cast<const _Float16*>(kl), idx_out,
-                       val_out, lse_out, B, Nq, Nk, k, inv_temperature * kLog2e / s2, inv_temperature / s2, (size_t)k_batch_stride);
+                       static_cast<const _Float16*>(ql), static_cast<const _Float16*>(kh), static_cast<const _Float16*>(kl), q_label,
+                       k_label, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature * kLog2e / s2, inv_temperature / s2, (size_t)k_batch_stride);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }
@@ -316,4 +341,29 @@ extern "C" int cocos_corr_topk_f16x3(const void* qh, const void* ql, const void*
     if (k <= 4)
         return launch_corr_topk<4>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride, stream);
     return launch_corr_topk<8>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride, stream);
+}
+
+// K47: the same readout over the keys each query's label allows
+extern "C" int cocos_corr_topk_labels_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* q_label,
+                                            const int* k_label, int* idx_out, float* val_out, float* lse_out, int B, int K, int Nq,
+                                            int Nk, int k, float inv_temperature, float operand_scale, long long k_batch_stride,
+                                            cocos_stream_t stream) {
+    using namespace cocos;
+    COCOS_REQUIRE(q_label && k_label, COCOS_ERR_INVALID, "corr_topk_labels_f16x3: null label pointer");
+    if (const int rc = check_corr_readout("corr_topk_labels_f16x3", "a host-side mask of materialised logits and cocos_row_topk_lse", qh, ql,
+                                          kh, kl, idx_out, val_out, lse_out, B, K, Nq, Nk, k, inv_temperature, operand_scale, k_batch_stride))
+        return rc;
+    COCOS_REQUIRE((reinterpret_cast<uintptr_t>(q_label) & 3) == 0 && (reinterpret_cast<uintptr_t>(k_label) & 3) == 0, COCOS_ERR_INVALID,
+                  "corr_topk_labels_f16x3: label arrays must be 4-byte aligned");
+    if (k == 1)
+        return launch_corr_topk<1, true>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale,
+                                         k_batch_stride, stream, q_label, k_label);
+    if (k == 2)
+        return launch_corr_topk<2, true>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale,
+                                         k_batch_stride, stream, q_label, k_label);
+    if (k <= 4)
+        return launch_corr_topk<4, true>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale,
+                                         k_batch_stride, stream, q_label, k_label);
+    return launch_corr_topk<8, true>(qh, ql, kh, kl, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature, operand_scale,
+                                     k_batch_stride, stream, q_label, k_label);
 }

@@ -589,6 +589,9 @@ class MatchReadout:
     # lies in the window (meaningful when the refinement runs at the readout's temperature)
     offset: torch.Tensor = None
     window_prob: torch.Tensor = None
+    # with restrict (K47): bool [B,fh,fw], the positions whose candidates were restricted to their label (the others fell back to
+    # the scan over all positions); index, prob, max_logit and lse are then over the allowed set
+    restricted: torch.Tensor = None
 
     def xy(self):
         """[B,2,fh,fw] int64: (x, y) of the match on the other side's grid — index = y * gw + x"""
@@ -614,6 +617,7 @@ class TopkMatchReadout:
     logit: torch.Tensor
     lse: torch.Tensor
     grid: tuple = None      # (gh, gw) of the side the indices point into; None = the same as index.shape[2:]
+    restricted: torch.Tensor = None     # with restrict (K47): as MatchReadout.restricted; prob and lse are over the allowed set
 
     def xy(self):
         """[B,k,2,fh,fw] int64: (x, y) of every candidate on the other side's grid — index = y * gw + x"""
@@ -650,8 +654,92 @@ def _refine_scope(name: str, cfg: HotPathConfig, refine, refine_temperature, top
         raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}: {route}")
 
 
+# ---- K47: label-restricted candidates ---------------------------------------------------------------------------------------------
+def cell_labels(seg_map, down):
+    """int64 [B,h,w]: the majority class of every down x down cell of a one-hot (or soft) label map seg_map [B,nc,h*down,w*down]; among
+    equally frequent classes the lower one (torch glue: the labels of correspondence_match / correspondence_sparse with
+    restrict="label")."""
+    if not torch.is_tensor(seg_map) or seg_map.dim() != 4:
+        raise ValueError("cell_labels: expected a label map [B,nc,H,W]")
+    if isinstance(down, bool) or not isinstance(down, int) or down < 1 or seg_map.shape[2] % down or seg_map.shape[3] % down:
+        raise ValueError(f"cell_labels: down={down!r} does not divide the {tuple(seg_map.shape[2:])} label map")
+    return F.avg_pool2d(seg_map.float(), down).argmax(1)
+
+
+def _restrict_scope(name: str, cfg: HotPathConfig, restrict, has_exemplar: bool, refine=0, search="dense", channels=None):
+    """ValueError for a `restrict` that is neither None, "label" nor a pair of integer tensors (TypeError for another dtype), and — with
+    a restriction — for everything outside its scope (K47: the fused match_kernel-1 route, no prepared exemplar, no refinement, the
+    dense selector); checked before any tensor is looked at.  Every message names `restrict`."""
+    if restrict is None:
+        return
+    pair = isinstance(restrict, (tuple, list)) and len(restrict) == 2 and all(torch.is_tensor(t) for t in restrict)
+    if not (pair or (isinstance(restrict, str) and restrict == "label")):
+        what = repr(restrict) if isinstance(restrict, str) else type(restrict).__name__
+        raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
+    if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
+        raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
+    route = "restrict runs on the fused match_kernel 1 route only"
+    if cfg.match_kernel != 1:
+        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope: {route}")
+    if not cfg.PONO_C:
+        raise ValueError(f"{name}: needs PONO_C: {route}")
+    if ops.PRECISION != "f16x3":
+        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope: {route}")
+    if not ops.MATCH_FUSED:
+        raise ValueError(f"{name}: ops.MATCH_FUSED = False (the materialised readout) is out of scope: {route}")
+    if has_exemplar:
+        raise ValueError(f"{name}: restrict with a prepared exemplar is out of scope (not built)")
+    if refine:
+        raise ValueError(f"{name}: restrict with refine={refine!r} is out of scope (not built)")
+    if search != "dense":
+        raise ValueError(f"{name}: restrict with search={search!r} is out of scope: the label mask lives in the dense scan")
+    if channels is not None and channels != ops.FUSED_K:
+        raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}: {route}")
+
+
+def _restrict_labels(name: str, restrict, seg_map, ref_seg_map, down, B, content_grid, exemplar_grid):
+    """(content labels [B,fh*fw], exemplar labels [B,gh*gw]) of a restriction _restrict_scope accepted: cell_labels of the two label
+    maps, or the given pair; ValueError for what does not fit the grids"""
+    (fh, fw), (gh, gw) = content_grid, exemplar_grid
+    if isinstance(restrict, str):
+        for what, seg, (h, w) in (("seg_map", seg_map, content_grid), ("ref_seg_map", ref_seg_map, exemplar_grid)):
+            if not torch.is_tensor(seg) or seg.dim() != 4 or seg.shape[0] != B or tuple(seg.shape[2:]) != (h * down, w * down):
+                got = tuple(seg.shape) if torch.is_tensor(seg) else type(seg).__name__
+                raise ValueError(f"{name}: restrict='label' needs {what} [B={B},nc,{h * down},{w * down}] (down={down} times the {h}x{w} "
+                                 f"grid), got {got}")
+        if seg_map.shape[1] != ref_seg_map.shape[1]:
+            raise ValueError(f"{name}: restrict='label': seg_map has {seg_map.shape[1]} classes, ref_seg_map {ref_seg_map.shape[1]}")
+        q_lab, k_lab = cell_labels(seg_map, down), cell_labels(ref_seg_map, down)
+    else:
+        q_lab, k_lab = restrict
+        if tuple(q_lab.shape) != (B, fh, fw) or tuple(k_lab.shape) != (B, gh, gw):
+            raise ValueError(f"{name}: restrict: labels {tuple(q_lab.shape)}, {tuple(k_lab.shape)} do not fit the content grid "
+                             f"{(B, fh, fw)} and the exemplar grid {(B, gh, gw)}")
+    return q_lab.reshape(B, fh * fw), k_lab.reshape(B, gh * gw)
+
+
+def restrict_fallback(q_lab, k_lab, k):
+    """The fallback rule of a restriction: asking position i of sample b is restricted only if the other side holds at least k
+    positions of its label in that sample (a negative label: never).  q_lab [B,Nq], k_lab [B,Nk] integer tensors of one device ->
+    (q_eff, k_eff, restricted): int32 labels for ops.corr_topk_labelled — dense ids of the labels that occur, so any int64 ids
+    survive the narrowing; -1 for an unrestricted asking position and for a negative label of the other side — and restricted bool
+    [B,Nq].  So no row of the readout is short or empty.  Counts: a scatter_add over b * L + id."""
+    B, Nq = q_lab.shape
+    ids, inv = torch.unique(torch.cat((q_lab, k_lab), 1).to(torch.int64), return_inverse=True)
+    L = ids.numel()
+    q_id, k_id = inv[:, :Nq], inv[:, Nq:]
+    k_valid = k_lab >= 0
+    at = torch.arange(B, device=q_lab.device).view(B, 1) * L
+    counts = torch.zeros(B * L, dtype=torch.int64, device=q_lab.device)
+    counts.scatter_add_(0, (at + k_id).reshape(-1), k_valid.reshape(-1).to(torch.int64))
+    restricted = (q_lab >= 0) & (counts.view(B, L).gather(1, q_id) >= k)
+    minus = torch.full_like(q_id, -1)
+    return (torch.where(restricted, q_id, minus).to(torch.int32).contiguous(),
+            torch.where(k_valid, k_id, torch.full_like(k_id, -1)).to(torch.int32).contiguous(), restricted)
+
+
 def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, direction="rows", topk=1, refine=0,
-                         refine_temperature=None):
+                         refine_temperature=None, restrict=None, seg_map=None, ref_seg_map=None):
     """The hard readout of the correlation of correspondence.py:272-304: argmax, maximum and log-sum-exp of every row of the scaled
     matrix f / temperature that forward(return_corr=True) returns (:305-306) — `direction="rows"`: per CONTENT position over the
     exemplar positions; "cols": per EXEMPLAR position over the content positions (the rows of f^T).  Returns a MatchReadout.
@@ -675,11 +763,22 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     every match — positions outside the grid are left out — whose expected offset becomes MatchReadout.offset, with
     MatchReadout.window_prob the window's share of the full softmax mass; the same operand planes serve the scan and the window.
     Scope: topk = 1, no prepared exemplar, the fused match_kernel-1 route (PONO_C, 256 channels, COCOS_PRECISION=f16x3,
-    ops.MATCH_FUSED); everything else raises ValueError — nothing falls back."""
+    ops.MATCH_FUSED); everything else raises ValueError — nothing falls back.
+
+    `restrict` (K47; None, the default, is the code path above, untouched) keeps every position's candidates inside its own region:
+    "label" takes the majority class of each cell of the one-hot `seg_map` / `ref_seg_map` [B,nc,h*down,w*down] (cell_labels, with
+    cfg.down); a pair (q_labels [B,h,w], k_labels [B,gh,gw]) of int32 / int64 tensors — content side first, whatever the direction —
+    is taken as given (face-parsing parts, instance ids, scribbles; a negative content label: unrestricted).  The mask is applied
+    inside the scan (ops.corr_topk_labelled): index, logit, prob and lse are then over the ALLOWED positions, and still nothing HWxHW
+    exists.  A position whose label has fewer than topk positions on the other side of its sample falls back to the unrestricted scan
+    (restrict_fallback), so no row is short; the readout's `restricted` says which positions were restricted.  Scope: the fused
+    match_kernel-1 route (PONO_C, 256 channels, COCOS_PRECISION=f16x3, ops.MATCH_FUSED, ops.corr_split_ok shapes), no prepared
+    exemplar, refine = 0; everything else raises a ValueError that names restrict — nothing falls back to a materialised matrix."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
         raise ValueError(f"correspondence_match: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+    _restrict_scope("correspondence_match", cfg, restrict, exemplar is not None, refine, channels=theta_raw.shape[1])
     _refine_scope("correspondence_match", cfg, refine, refine_temperature, topk, exemplar is not None, theta_raw.shape[1])
     if (exemplar is None) == (phi_raw is None):
         raise ValueError("correspondence_match: pass phi_raw or a prepared exemplar in its place (not both)")
@@ -699,6 +798,9 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
     if k > (Nk if rows else N):
         raise ValueError(f"correspondence_match: topk={k} exceeds the {Nk if rows else N} positions each row of direction={direction!r} ranges over")
+    labels = None
+    if restrict is not None:
+        labels = _restrict_labels("correspondence_match", restrict, seg_map, ref_seg_map, cfg.down, B, (fh, fw), (gh, gw))
     with torch.no_grad():
         if not _hip_fp32(theta_raw):
             raise ops._lib.CocosHipError("correspondence_match: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
@@ -707,7 +809,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
         if refine and not fused:
             raise ValueError(f"correspondence_match: refine={refine}: the fused match_kernel 1 route does not take B={B}, {fh}x{fw} content "
                              f"and {gh}x{gw} exemplar positions (ops.corr_split_ok), and the refinement runs on no other route")
-        off = lse_win = None
+        if restrict is not None and not fused:
+            raise ValueError(f"correspondence_match: restrict: the fused match_kernel 1 route does not take B={B}, {fh}x{fw} content and "
+                             f"{gh}x{gw} exemplar positions, topk={k} (ops.corr_split_ok, ops.corr_topk_ok), and restrict runs on no other route")
+        off = lse_win = restricted = None
         if fused and exemplar is not None:
             # the query side as _attention_with_exemplar makes it; the record's key planes are read in place
             if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
@@ -727,7 +832,13 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             else:
                 qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
                 kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
-            if k == 1:
+            if labels is not None:      # K47: the side that asks brings its labels, operands and label tensors swap together
+                asks, other_side = (qn, kn) if rows else (kn, qn)
+                q_eff, k_eff, restricted = restrict_fallback(*(labels if rows else labels[::-1]), k)
+                idx, mx, lse = ops.corr_topk_labelled(asks, other_side, q_eff, k_eff, inv_t, k, planes)
+                if k == 1:
+                    idx, mx = idx[..., 0], mx[..., 0]
+            elif k == 1:
                 idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
                 if refine:      # K44: the window scores come from the operand planes that chose the centre
                     inv_rt = inv_t if refine_temperature is None else 1.0 / refine_temperature
@@ -764,12 +875,14 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             lse = lse.reshape(shape)
             val = rank_first(mx)
             return TopkMatchReadout(index=rank_first(idx.to(torch.int64)), prob=torch.exp(val - lse.unsqueeze(1)), logit=val, lse=lse,
-                                    grid=other)
+                                    grid=other, restricted=None if restricted is None else restricted.reshape(shape))
         m = MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
                          max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)
         if refine:
             m.offset = off.reshape(shape + (2,)).permute(0, 3, 1, 2).contiguous()
             m.window_prob = torch.exp(lse_win - lse).reshape(shape)
+        if restricted is not None:
+            m.restricted = restricted.reshape(shape)
         return m
 
 
@@ -839,7 +952,7 @@ def _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k):
 
 
 def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                          exemplar=None, search="dense", search_opts=None):
+                          exemplar=None, search="dense", search_opts=None, restrict=None):
     """The k-sparse, trainable variant of correspondence_hot_path's row pass (CoCosNet-v2 style): per content position the `topk` best
     exemplar positions are SELECTED without gradient by the match readout (K23 / K1 planes -> K39a, as correspondence_match), then a
     softmax over those k logits alone blends their values — ops.sparse_softmax_warp (K42), with gradients to theta_raw and phi_raw
@@ -858,7 +971,14 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     readout's reach) and runs ops.patchmatch_topk on the full-grid planes: propagation from the grid neighbours plus a random search,
     O(N k) dot products per iteration whatever the number of keys.  Its candidates are the best of what it looked at, not of all keys
     (DESIGN.md 3.27 records recall and cost against the dense scan); scope and refusals are the dense selector's.  `search_opts`
-    overrides entries of ops.PATCHMATCH_DEFAULTS: strides (one iteration per entry), radii, radius0, seed."""
+    overrides entries of ops.PATCHMATCH_DEFAULTS: strides (one iteration per entry), radii, radius0, seed.
+
+    `restrict` (K47; None, the default, is the code path above, untouched): "label" or a pair (q_labels [B,h,w], k_labels [B,gh,gw]),
+    as correspondence_match takes them — the k candidates are selected among the exemplar positions of the content position's label
+    (ops.corr_topk_labelled; positions whose label has fewer than topk exemplar positions fall back to the scan over all), and the
+    warp and its gradients are the same K42 on those indices.  The result gains match_restricted [B,h,w] bool.  Scope: the dense
+    selector of the scope above; everything else raises a ValueError that names restrict."""
+    _restrict_scope("correspondence_sparse", cfg, restrict, exemplar is not None, 0, search, theta_raw.shape[1])
     k = _sparse_scope(cfg, topk)
     pm = _sparse_search(search, search_opts)
     if exemplar is not None:
@@ -876,11 +996,14 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     if tuple(ref_img.shape[2:]) != (phi_raw.shape[2] * down, phi_raw.shape[3] * down) or ref_img.shape[3] % 4 != 0:
         raise ValueError(f"correspondence_sparse: ref_img {tuple(ref_img.shape)} is not down={down} times the exemplar grid "
                          f"{tuple(phi_raw.shape[2:])} (width a multiple of 4)")
+    labels = None
+    if restrict is not None:
+        labels = _restrict_labels("correspondence_sparse", restrict, seg_map, ref_seg_map, down, B, (fh, fw), tuple(phi_raw.shape[2:]))
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError("correspondence_sparse: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(k):
         raise ValueError(f"correspondence_sparse: the fused top-k readout does not take B={B}, {N} x {Nk} positions, k={k} "
-                         "(positions must be multiples of 4)")
+                         "(positions must be multiples of 4)" + ("; restrict runs on no other route" if restrict is not None else ""))
     if all(lazy):
         theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
     # K1 with autograd, in the flavour correspondence_match selects from: the position-major operand planes are written once and serve
@@ -892,7 +1015,11 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     inv_t = 1.0 / temperature
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
     with torch.no_grad():
-        if pm is None:
+        restricted = None
+        if labels is not None:      # K47: the same selection among the exemplar positions of the position's label
+            q_eff, k_eff, restricted = restrict_fallback(*labels, k)
+            idx, _, _ = ops.corr_topk_labelled(qn, kn, q_eff, k_eff, inv_t, k, planes)
+        elif pm is None:
             idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                # selection: no gradient
         else:
             idx, _ = ops.patchmatch_topk(qn, kn, inv_t, k, (tuple(theta_raw.shape[2:]), tuple(phi_raw.shape[2:])),
@@ -908,6 +1035,8 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     rank_first = lambda t: t.reshape(B, fh, fw, k).permute(0, 3, 1, 2).contiguous()
     out["match_index"] = rank_first(idx.to(torch.int64))
     out["match_weight"] = rank_first(w)
+    if restricted is not None:
+        out["match_restricted"] = restricted.reshape(B, fh, fw)
     return out
 
 

@@ -1041,6 +1041,64 @@ def corr_topk_shared(qh, ql, keys: PreparedKeys, inv_temperature: float, k: int)
         return _corr_topk_planes(qh, ql, kh, kl, inv_temperature, k)
 
 
+# K47  label-restricted readout: the same scan over the keys each query's label allows
+def _label_table(name: str, what: str, lab, B, N):
+    """TypeError / ValueError of a label tensor (before any device is looked at)"""
+    if not torch.is_tensor(lab) or lab.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: {what} must be an int32 or int64 tensor")
+    if tuple(lab.shape) != (B, N):
+        raise ValueError(f"{name}: {what} is {tuple(lab.shape)}, expected {(B, N)}")
+
+
+def _narrow_labels(lab):
+    # (int64 labels are narrowed after a clamp into int32's range, which keeps a negative label negative; two classes above 2^31 - 2
+    #  would collide: no label map has them)
+    return (lab if lab.dtype == torch.int32 else lab.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
+
+
+def _corr_topk_labels_planes(qh, ql, kh, kl, q_label, k_label, inv_temperature: float, k: int):
+    """K47 on operand planes (as _corr_topk_planes) and int32 contiguous labels [B,Nq], [Be,Nk] on their device"""
+    B, K, Nq, Nk, k_stride = _readout_planes("corr_topk_labelled", qh, ql, kh, kl)
+    k = _check_topk("corr_topk_labelled", k, Nk)
+    if tuple(q_label.shape) != (B, Nq) or tuple(k_label.shape) != (kh.shape[0], Nk):
+        raise ValueError(f"corr_topk_labelled: labels {tuple(q_label.shape)}, {tuple(k_label.shape)} do not fit q{tuple(qh.shape)} k{tuple(kh.shape)}")
+    idx = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
+    val = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
+    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("corr_topk_labelled", "cocos_corr_topk_labels_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+          q_label.data_ptr(), k_label.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature),
+          SPLIT_OPERAND_SCALE, k_stride, _stream())
+    return idx, val, lse
+
+
+def corr_topk_labelled(qn, kn, q_label, k_label, inv_temperature: float, k: int, planes: OperandPlanes | None = None):
+    """corr_topk over the keys each query's label allows (K47; forward only) -> (idx int32 [B,Nq,k], val [B,Nq,k], lse [B,Nq]).
+    q_label [B,Nq], k_label [B,Nk] int32 / int64: key j is allowed for query i when q_label[b,i] < 0 (unrestricted) or
+    q_label[b,i] == k_label[b,j]; a negative key label is matched by unrestricted queries only.  The mask is applied to the logits
+    inside the scan, before the candidate list and the log-sum-exp: lse is over the allowed keys, idx / val their k best in corr_topk's
+    order.  A row with fewer than k allowed keys has val = -inf on the missing ranks (idx stays inside [0, Nk)); a row with none has
+    lse = -inf.  With nothing restricted the outputs are corr_topk's bit for bit.  Operands, k and refusals as corr_topk; labels of
+    another dtype raise TypeError, of another shape ValueError."""
+    name = "corr_topk_labelled"
+    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0]:
+        raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
+    B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
+    _label_table(name, "q_label", q_label, B, Nq)
+    _label_table(name, "k_label", k_label, B, Nk)
+    _check_topk(name, k, Nk)
+    for t, what in ((qn, "qn"), (kn, "kn"), (q_label, "q_label"), (k_label, "k_label")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if PRECISION != "f16x3":
+        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    if planes is None:
+        planes = OperandPlanes()
+    with torch.no_grad():
+        qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
+        return _corr_topk_labels_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
+                                        _narrow_labels(q_label), _narrow_labels(k_label), inv_temperature, k)
+
+
 def row_topk_lse(f: torch.Tensor, k: int):
     """(idx int32 [..., k], val [..., k], lse [...]) of the rows of a materialised logit matrix f [..., Nk] in one sweep (K39b):
     torch.topk(f, k, -1) with the lower index first among equal values, and torch.logsumexp(f, -1).  Rank 0 and lse are

@@ -1252,6 +1252,17 @@ int cocos_corr_topk_f16x3(const void* qh, const void* ql, const void* kh, const 
                           float* lse_out, int B, int K, int Nq, int Nk, int k, float inv_temperature, float operand_scale,
                           long long k_batch_stride, cocos_stream_t stream);
 int cocos_row_topk_lse(const float* logits, int* idx, float* val, float* lse, int B, int Nq, int Nk, int k, cocos_stream_t stream);
+/* K47 label-restricted readout (corr_topk_f16x3.hip, the LABELS instantiations): cocos_corr_topk_f16x3 over the keys a query's label
+ *     allows.  q_label [B,Nq], k_label [B,Nk] int32 (k_batch_stride == 0: k_label is the one [Nk] row of the shared key set), 4-byte
+ *     aligned, any values;  allowed(i, j) = q_label[i] < 0 || q_label[i] == k_label[j]  (a negative query label: unrestricted; a
+ *     negative key label is matched by unrestricted queries only).  A disallowed logit is -inf before the candidate list and the
+ *     log-sum-exp: lse is over the allowed keys, idx / val are the k best allowed keys in K39's order.  A row with fewer than k
+ *     allowed keys has val = -inf on the missing ranks (idx clamped into [0, Nk)); a row with none has lse = -inf.  No NaN from
+ *     finite input.  With every query unrestricted, or one label everywhere, the three outputs are cocos_corr_topk_f16x3's bit for
+ *     bit.  Arguments, limits and error codes of cocos_corr_topk_f16x3; a null label pointer is COCOS_ERR_INVALID. */
+int cocos_corr_topk_labels_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* q_label, const int* k_label,
+                                 int* idx_out, float* val_out, float* lse_out, int B, int K, int Nq, int Nk, int k,
+                                 float inv_temperature, float operand_scale, long long k_batch_stride, cocos_stream_t stream);
 int cocos_gather_blend_patches(const float* img, const int* idx, const float* w, float* out, int B, int C, int H, int W, int down,
                                int k, long long img_batch_stride, cocos_stream_t stream);
 
