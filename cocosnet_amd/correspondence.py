@@ -24,8 +24,8 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_scope, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search, correspondence_flow,
-                       correspondence_hot_path, correspondence_match, correspondence_sparse)
+from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search, _upsample,
+                       correspondence_flow, correspondence_hot_path, correspondence_match, correspondence_mutual, correspondence_sparse)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -354,6 +354,48 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)
                 weights = torch.softmax(m.logit, dim=1) if blend == "topk" else m.prob
                 out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
+        return out
+
+    def mutual_match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, exemplar=None, max_dist=0, hard_warp=False):
+        """Where each position matched AND whether the match is confirmed from the other side (K48, hot_path.correspondence_mutual):
+        content position i goes to exemplar position j = match_index, j goes back to content position match_round_trip, and the match
+        counts as mutual when that lies within `max_dist` cells (Chebyshev; 0, the default: exactly i — mutual nearest neighbours) of
+        i.  One projection of the network, under torch.no_grad(); where the fused match_kernel-1 route runs, ONE sweep of the
+        correlation serves both directions (every other route, prepared exemplars included, pays two readouts).  Returns
+        match_index [B,h,w] int64 / match_xy [B,2,h,w] / match_prob / match_lse: match(direction="rows")'s, bit for bit;
+        back_index [B,gh,gw] / back_xy / back_prob / back_lse: the column direction, per exemplar position its best content position;
+        match_round_trip [B,h,w] int64, match_cycle_dist [B,h,w] int32, match_mutual [B,h,w] bool on the content grid;
+        back_cycle_dist, back_mutual [B,gh,gw] on the exemplar grid;
+        with `hard_warp`: warp_hard [B,3,H,W] as match() returns it and warp_valid [B,1,H,W] fp32, match_mutual up-sampled by `down`
+        (nearest neighbour): the full-resolution cells whose source is confirmed.
+        `exemplar`: a record of inference.prepare_exemplar in place of ref_img / ref_seg_map, as for match().  `max_dist` must be a
+        non-negative integer (ValueError before the network runs).  match(), forward(), sparse_warp() and flow_warp() are unaffected."""
+        max_dist = _max_dist("mutual_match", max_dist)
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        keys = phi_raw = None
+        with torch.no_grad():
+            if exemplar is not None:
+                exemplar = self._check_exemplar(exemplar, seg_map.shape[0])
+                if inference.FROZEN:
+                    theta_raw, keys = self._project_content(seg_map, exemplar, lazy=True)
+                    phi_raw, ref_img = None, exemplar.ref_img
+                    if not isinstance(keys, ops.PreparedKeys):      # CPU / fp64 content: as match() — the readout refuses the tensors
+                        phi_raw, keys = keys, None
+                else:
+                    ref_img, ref_seg_map = _stored_inputs(exemplar, seg_map.shape[0])
+            elif ref_img is None or ref_seg_map is None:
+                raise ValueError("mutual_match: ref_img and ref_seg_map are required without a prepared exemplar")
+            if keys is None and phi_raw is None:
+                theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
+            m = correspondence_mutual(theta_raw, phi_raw, cfg, temperature, exemplar=keys, max_dist=max_dist)
+            out = {"match_index": m.rows.index, "match_xy": m.rows.xy(), "match_prob": m.rows.prob, "match_lse": m.rows.lse,
+                   "back_index": m.cols.index, "back_xy": m.cols.xy(), "back_prob": m.cols.prob, "back_lse": m.cols.lse,
+                   "match_round_trip": m.rows_back, "match_cycle_dist": m.rows_dist, "match_mutual": m.rows_mutual,
+                   "back_cycle_dist": m.cols_dist, "back_mutual": m.cols_mutual}
+            if hard_warp:
+                fh, fw = m.rows.index.shape[1:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.rows.index, fh, fw, self.opt.down)
+                out["warp_valid"] = _upsample(m.rows_mutual.to(torch.float32).unsqueeze(1).contiguous(), self.opt.down, False)
         return out
 
     def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, search="dense", search_opts=None,

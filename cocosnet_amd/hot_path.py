@@ -886,6 +886,94 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
         return m
 
 
+# ---- K48: mutual match — both directions and the round trip ---------------------------------------------------------------------
+@dataclass
+class MutualMatchReadout:
+    """Both directions of the hard readout and their round trip (correspondence_mutual).  `rows`: the MatchReadout of the content
+    positions (into the exemplar grid), `cols`: of the exemplar positions (into the content grid), each exactly as
+    correspondence_match builds it.  rows_back [B,fh,fw] int64: where a content position comes back to on its OWN grid
+    (cols.index at rows.index), rows_dist int32 the Chebyshev distance in cells between that and the position itself, rows_mutual
+    bool = rows_dist <= max_dist (max_dist = 0: mutual nearest neighbours); cols_back / cols_dist / cols_mutual [B,gh,gw] the same
+    for the exemplar positions."""
+    rows: MatchReadout
+    cols: MatchReadout
+    rows_back: torch.Tensor
+    cols_back: torch.Tensor
+    rows_dist: torch.Tensor
+    cols_dist: torch.Tensor
+    rows_mutual: torch.Tensor
+    cols_mutual: torch.Tensor
+    max_dist: int = 0
+
+
+def _max_dist(name: str, max_dist):
+    if isinstance(max_dist, bool) or not isinstance(max_dist, int) or max_dist < 0:
+        raise ValueError(f"{name}: max_dist={max_dist!r}: expected a non-negative integer (cells; 0: mutual nearest neighbours)")
+    return max_dist
+
+
+def mutual_fused_route(cfg: HotPathConfig, B, C, N, Nk, has_exemplar: bool) -> bool:
+    """correspondence_mutual sweeps the correlation once: where correspondence_match's fused match_kernel-1 route runs, without a
+    prepared exemplar, on the shapes the mutual kernel takes, and with both switches on"""
+    return bool(ops.MATCH_FUSED and ops.MATCH_MUTUAL_FUSED and not has_exemplar and cfg.match_kernel == 1 and C == ops.FUSED_K
+                and cfg.PONO_C and ops.PRECISION == "f16x3" and ops.corr_split_ok(B, C, N, Nk, 1, False)
+                and ops.corr_match_mutual_ok(B, N, Nk))
+
+
+def correspondence_mutual(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, exemplar=None, max_dist=0):
+    """The round-trip test of the hard correspondence: content position i goes to its best exemplar position j
+    (correspondence_match, direction="rows"), j goes to its best content position i' (direction="cols"), and the match is confirmed
+    when i' is i or within `max_dist` cells of it (Chebyshev, on the content grid) — an occlusion / "nothing to copy from" mask, the
+    hard-readout counterpart of the cycle terms (warp_cycle_w, correspondence.py:350-372).  Returns a MutualMatchReadout.  Arguments
+    as correspondence_match; `max_dist` must be a non-negative integer (ValueError, before any tensor is looked at).  Forward only.
+
+    Routes.  FUSED: where correspondence_match's fused match_kernel-1 route runs (ops.MATCH_FUSED, match_kernel 1, 256 channels,
+    PONO_C, COCOS_PRECISION=f16x3) with no prepared exemplar, ops.MATCH_MUTUAL_FUSED on and shapes ops.corr_match_mutual_ok takes,
+    the operand planes are made once (the K23 pair where it applies) and the correlation is swept ONCE: K48's kernel reads every
+    S^T tile along the keys and along the queries (ops.corr_match_mutual).  `rows` is then correspondence_match's readout bit for
+    bit; `cols` holds the same logits reduced in another order: its index is the exchanged call's except among logits closer than
+    the kernel's rounding, its lse within the same error bound.  EVERYWHERE ELSE (the fused match_kernel-3 route, the
+    materialised routes, prepared exemplars, ops.MATCH_MUTUAL_FUSED = False) this makes two correspondence_match calls on the same
+    theta_raw / phi_raw, rows then cols: those routes pay two readouts (two projections' worth of centring / normalisation, two
+    sweeps or two reads of their matrix) — sharing T or the operand planes between the two calls is out of scope here.  Every route
+    ends in the same round-trip kernel (ops.match_round_trip)."""
+    name = "correspondence_mutual"
+    max_dist = _max_dist(name, max_dist)
+    if (exemplar is None) == (phi_raw is None):
+        raise ValueError(f"{name}: pass phi_raw or a prepared exemplar in its place (not both)")
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
+    N, Nk = fh * fw, gh * gw
+    inv_t = 1.0 / temperature
+    with torch.no_grad():
+        fused = (exemplar is None and isinstance(theta_raw, ops.LazyProj1x1) == isinstance(phi_raw, ops.LazyProj1x1)
+                 and _hip_fp32(theta_raw) and mutual_fused_route(cfg, B, C, N, Nk, False))
+        if fused:
+            raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
+            planes = ops.OperandPlanes()      # made as correspondence_match's fused route makes them
+            if (isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
+                    and ops.proj_norm_fused_ok(phi_raw)):
+                qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw.detach(), phi_raw.detach(), 1, planes, want_chan=False)   # K23
+            else:
+                qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
+                kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
+            (ri, rm, rl), (ci, cm, cl) = ops.corr_match_mutual(qn, kn, inv_t, planes)
+            readout = lambda idx, mx, lse, shape, other: MatchReadout(
+                index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape), max_logit=mx.reshape(shape),
+                lse=lse.reshape(shape), grid=other)
+            rows = readout(ri, rm, rl, (B, fh, fw), (gh, gw))
+            cols = readout(ci, cm, cl, (B, gh, gw), (fh, fw))
+        else:      # two readouts; every refusal (CPU tensors, mixed operand kinds, a stale record) is correspondence_match's
+            rows = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=exemplar, direction="rows")
+            cols = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=exemplar, direction="cols")
+            ri, ci = rows.index.reshape(B, N), cols.index.reshape(B, Nk)
+        q_back, q_dist, k_back, k_dist = ops.match_round_trip(ri, ci, (fh, fw), (gh, gw))
+        q_dist, k_dist = q_dist.reshape(B, fh, fw), k_dist.reshape(B, gh, gw)
+        return MutualMatchReadout(rows=rows, cols=cols, rows_back=q_back.to(torch.int64).reshape(B, fh, fw),
+                                  cols_back=k_back.to(torch.int64).reshape(B, gh, gw), rows_dist=q_dist, cols_dist=k_dist,
+                                  rows_mutual=q_dist <= max_dist, cols_mutual=k_dist <= max_dist, max_dist=max_dist)
+
+
 # ---- K42: differentiable k-sparse warp over the top-k matches ---------------------------------------------------------------------
 def _sparse_scope(cfg: HotPathConfig, topk):
     """ValueError for every flag outside correspondence_sparse's scope (checked before any tensor is looked at) -> k"""

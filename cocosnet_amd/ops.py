@@ -1099,6 +1099,100 @@ def corr_topk_labelled(qn, kn, q_label, k_label, inv_temperature: float, k: int,
                                         _narrow_labels(q_label), _narrow_labels(k_label), inv_temperature, k)
 
 
+# ------------------------------------------------------------------------------------------
+# K48  mutual match: both softmax directions from one correlation sweep, and the round trip
+# ------------------------------------------------------------------------------------------
+#: hot_path.correspondence_mutual: True = one sweep of the fused kernel serves both directions where it runs; False = every call
+#: makes two readouts (rows, then cols).  The default follows profiles/k48_match_mutual.txt (tools/match_mutual_bench.py; B = 8, 64 x 64
+#: grid): the fused kernel plus its finishing kernel 0.2570 ms against 0.3505 ms for two cocos_corr_match_f16x3 calls, a difference of
+#: 0.0934 ms where the spread of the two-call windows is 0.0027 ms — above the spread, hence True.
+MATCH_MUTUAL_FUSED = True
+
+
+def corr_match_mutual_ok(B: int, Nq: int, Nk: int) -> bool:
+    """the fused mutual kernel takes [B,Nq,256] x [B,Nk,256] planes: Nq and Nk multiples of 4 (dense keys, 256 channels)"""
+    return (B >= 1 and Nq >= 4 and Nk >= 4 and Nq % 4 == 0 and Nk % 4 == 0
+            and _lib.load().cocos_corr_match_mutual_workspace_bytes(int(B), int(Nq), int(Nk)) > 0)
+
+
+def _corr_match_mutual_planes(qh, ql, kh, kl, inv_temperature: float):
+    """K48 on operand planes qh, ql [B,Nq,256], kh, kl [B,Nk,256] -> ((row_idx, row_max, row_lse) [B,Nq], (col_idx, col_max, col_lse)
+    [B,Nk])"""
+    B, K, Nq, Nk, k_stride = _readout_planes("corr_match_mutual", qh, ql, kh, kl)
+    if k_stride == 0 and B != 1:
+        raise ValueError("corr_match_mutual: one key set for all samples is out of scope (dense keys only)")
+    dev = qh.device
+    rows = (torch.empty((B, Nq), device=dev, dtype=torch.int32), torch.empty((B, Nq), device=dev, dtype=torch.float32),
+            torch.empty((B, Nq), device=dev, dtype=torch.float32))
+    cols = (torch.empty((B, Nk), device=dev, dtype=torch.int32), torch.empty((B, Nk), device=dev, dtype=torch.float32),
+            torch.empty((B, Nk), device=dev, dtype=torch.float32))
+    nbytes = _lib.load().cocos_corr_match_mutual_workspace_bytes(B, Nq, Nk)
+    ws = torch.empty((max(nbytes, 4) // 4,), device=dev, dtype=torch.float32)
+    _call("corr_match_mutual", "cocos_corr_match_mutual_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+          rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(),
+          ws.data_ptr(), ws.numel() * 4, B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, _stream())
+    return rows, cols
+
+
+def corr_match_mutual(qn, kn, inv_temperature: float, planes: OperandPlanes | None = None):
+    """Both directions of corr_match from ONE sweep of the correlation (K48; forward only) -> ((row_idx int32, row_max, row_lse), each
+    [B,Nq], (col_idx int32, col_max, col_lse), each [B,Nk]).  The row triple is corr_match(qn, kn)'s bit for bit; the column triple is
+    what corr_match(kn, qn) computes — per key the largest logit over the queries, its query (the lowest among bitwise-equal logits)
+    and the column log-sum-exp — from the same tile registers: col_max is an element of the tile, so a mutual pair has bitwise-equal
+    row_max and col_max; col_lse's summation order differs from the exchanged call's (within the same error bound).  Operands as
+    corr_match.  Shapes the kernel does not take (corr_match_mutual_ok) raise: make two corr_match calls."""
+    name = "corr_match_mutual"
+    for t, what in ((qn, "qn"), (kn, "kn")):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name}: {what}: expected a tensor, got {type(t).__name__}")
+    if planes is None or not (planes.has(qn) or planes.has(kn)):
+        if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0] or qn.shape[1] != kn.shape[1]:
+            raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
+    for t, what in ((qn, "qn"), (kn, "kn")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if PRECISION != "f16x3":
+        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    if planes is None:
+        planes = OperandPlanes()
+    with torch.no_grad():
+        qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
+        return _corr_match_mutual_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
+                                         inv_temperature)
+
+
+def _grid2(name: str, what: str, grid):
+    if (not isinstance(grid, (tuple, list)) or len(grid) != 2
+            or any(isinstance(g, bool) or not isinstance(g, int) or g < 1 for g in grid)):
+        raise ValueError(f"{name}: {what}={grid!r}: expected a pair (h, w) of positive integers")
+    return int(grid[0]), int(grid[1])
+
+
+def match_round_trip(row_idx, col_idx, qgrid, kgrid):
+    """The round trip of two index maps (K48, one launch) -> (q_back, q_dist, k_back, k_dist), all int32: row_idx [B,hq*wq] holds per
+    position of the qgrid = (hq, wq) grid a position of the kgrid = (hk, wk) grid, col_idx [B,hk*wk] the other way round;
+    q_back[b,i] = col_idx[b,row_idx[b,i]], q_dist[b,i] the Chebyshev distance in cells between q_back[b,i] and i on the qgrid, k_back /
+    k_dist the same for the key side.  Any integer dtype (narrowed to int32 after a clamp); indices outside their range are clamped."""
+    name = "match_round_trip"
+    for t, what in ((row_idx, "row_idx"), (col_idx, "col_idx")):
+        if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
+            raise TypeError(f"{name}: {what} must be an integer tensor")
+    (hq, wq), (hk, wk) = _grid2(name, "qgrid", qgrid), _grid2(name, "kgrid", kgrid)
+    if row_idx.dim() != 2 or col_idx.dim() != 2 or row_idx.shape[0] != col_idx.shape[0] or row_idx.shape[1] != hq * wq or col_idx.shape[1] != hk * wk:
+        raise ValueError(f"{name}: row_idx {tuple(row_idx.shape)}, col_idx {tuple(col_idx.shape)} do not fit the grids {hq}x{wq} and {hk}x{wk}")
+    for t, what in ((row_idx, "row_idx"), (col_idx, "col_idx")):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    B = row_idx.shape[0]
+    narrow = lambda t: (t if t.dtype == torch.int32 else t.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
+    row_idx, col_idx = narrow(row_idx), narrow(col_idx)
+    q_back, q_dist = torch.empty_like(row_idx), torch.empty_like(row_idx)
+    k_back, k_dist = torch.empty_like(col_idx), torch.empty_like(col_idx)
+    _call("match_round_trip", "cocos_match_round_trip", row_idx.data_ptr(), col_idx.data_ptr(), q_back.data_ptr(), q_dist.data_ptr(),
+          k_back.data_ptr(), k_dist.data_ptr(), B, hq, wq, hk, wk, _stream())
+    return q_back, q_dist, k_back, k_dist
+
+
 def row_topk_lse(f: torch.Tensor, k: int):
     """(idx int32 [..., k], val [..., k], lse [...]) of the rows of a materialised logit matrix f [..., Nk] in one sweep (K39b):
     torch.topk(f, k, -1) with the lower index first among equal values, and torch.logsumexp(f, -1).  Rank 0 and lse are

@@ -1267,6 +1267,37 @@ int cocos_gather_blend_patches(const float* img, const int* idx, const float* w,
                                int k, long long img_batch_stride, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K48 mutual match (corr_match_mutual_f16x3.hip): both softmax directions of the correlation from ONE sweep of Q.K^T, and the round
+ *     trip i -> j -> i' on top — the validity signal of a dense correspondence (i' == i, or within a cell of it), the hard-readout
+ *     counterpart of the cycle terms the reference trains with (warp_cycle_w, correspondence.py:350-372).
+ *   cocos_corr_match_mutual_f16x3: operands, staging, QK arithmetic and row state of cocos_corr_match_f16x3 (the MUTUAL instantiation
+ *       of the same kernel template, dense keys only);  row_idx / row_max / row_lse [B,Nq] are that entry's outputs bit for bit.  Per key j
+ *         col_max[b,j] = max_i inv_temperature <q_i, k_j>  over the queries i < Nq — an ELEMENT of the tile, the register value the row
+ *                        side saw: where row_idx[b,i] == j and col_idx[b,j] == i, row_max[b,i] and col_max[b,j] are equal bitwise
+ *         col_idx[b,j] = the i of that maximum, the lowest one among bitwise-equal logits; always in [0, Nq), also for non-finite input
+ *         col_lse[b,j] = log sum_i exp(inv_temperature <q_i, k_j>), with a running maximum as the reference of the sum
+ *       Queries past Nq in the last block of 128 are -inf for the column state.  The queries of a key are reduced across the lanes of
+ *       a wave, across the four waves of a workgroup through LDS, and one partial (max, sum, index) per (query block, key) is written to
+ *       `workspace`; a finishing kernel (second launch of this entry) merges a key's partials in ascending block order, comparing
+ *       (logit, index).  No atomics: two calls on the same inputs give the same bits.  Nothing Nq x Nk reaches memory.
+ *       workspace_bytes >= cocos_corr_match_mutual_workspace_bytes(B, Nq, Nk) = 12 B ceil(Nq / 128) Nk (host arithmetic; 0 for bad
+ *       dims), 4-byte aligned, contents undefined before and after.
+ *       Supported: K == 256, Nq % 4 == 0, Nk % 4 == 0 (otherwise COCOS_ERR_UNSUPPORTED); null / misaligned pointers (planes 16 bytes,
+ *       outputs and workspace 4), bad dims and a short workspace are COCOS_ERR_INVALID; all checked before any HIP call.
+ *   cocos_match_round_trip: from row_idx [B,hq wq] (values are positions of the hk x wk grid) and col_idx [B,hk wk] (positions of the
+ *       hq x wq grid), one launch writes, all int32,
+ *         q_back[b,i] = col_idx[b,row_idx[b,i]],   q_dist[b,i] = max(|x(q_back) - x(i)|, |y(q_back) - y(i)|) on the hq x wq grid (cells),
+ *         k_back[b,j] = row_idx[b,col_idx[b,j]],   k_dist[b,j] = the same on the hk x wk grid.
+ *       Indices outside their range are clamped into it.  Integer code; serves every route that made the two index maps.
+ * ------------------------------------------------------------------------------------- */
+size_t cocos_corr_match_mutual_workspace_bytes(int B, int Nq, int Nk);
+int cocos_corr_match_mutual_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, int* row_idx, float* row_max,
+                                  float* row_lse, int* col_idx, float* col_max, float* col_lse, void* workspace, size_t workspace_bytes,
+                                  int B, int K, int Nq, int Nk, float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_match_round_trip(const int* row_idx, const int* col_idx, int* q_back, int* q_dist, int* k_back, int* k_dist, int B, int hq,
+                           int wq, int hk, int wk, cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K42 k-sparse correspondence warp with gradients (sparse_warp_f16x3.hip): attention over the k keys per query that the top-k match
  *     readout selected (selection itself carries no gradient),
  *         s[b,i,r] = inv_temperature <qn[b,:,i], kn[b,:,j_r]>,  j_r = idx[b,i,r],  w = softmax over r of s,
