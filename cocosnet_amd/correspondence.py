@@ -24,8 +24,9 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search, _upsample,
-                       correspondence_flow, correspondence_hot_path, correspondence_match, correspondence_mutual, correspondence_sparse)
+from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search,
+                       _upsample, correspondence_flow, correspondence_hot_path, correspondence_match, correspondence_mutual,
+                       correspondence_nll, correspondence_sparse)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -440,6 +441,30 @@ class NoVGGCorrespondence(NetworkBase):
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         coor_out.update(correspondence_flow(theta_raw, phi_raw, ref_img, cfg, temperature, radius=radius,
                                             refine_temperature=refine_temperature))
+        return coor_out
+
+    def match_loss(self, ref_img, real_img, seg_map, ref_seg_map, target, temperature=0.01, *, weight=None, symmetric=True):
+        """The supervised correspondence loss (hot_path.correspondence_nll, K49): `target` [B,h,w] int64 / int32 names, per content
+        cell, the flat exemplar position y * w + x it should match (negative: unsupervised) — from a self-pair, keypoints, a flow field
+        or the confirmed pairs of mutual_match — and the result holds the negative log-likelihood of that position under the row softmax
+        (match_nll [B,h,w]) and of the content cell under the column softmax of its target (back_nll [B,h,w]), both 0 where
+        unsupervised, match_lse [B,h,w] and back_lse [B,gh,gw] (mutual_match's), match_target_prob = exp(-match_nll) (detached) and
+            loss_match = sum_i w_i (match_nll_i + [symmetric] back_nll_i) / max(sum of w over the supervised cells, tiny)
+        with `weight` [B,h,w] fp32 >= 0 (None: 1), + loss_novgg_featpair where project() makes it.  The projection runs with gradients,
+        as in sparse_warp: loss_match.backward() reaches the whole network through theta and phi, and nothing HWxHW is allocated.
+        With no supervised cell the loss is 0 with zero gradients.  Scope: sparse_warp's (match_kernel 1 with PONO_C on the plain flag
+        set, COCOS_PRECISION=f16x3, no prepared exemplar); everything else raises ValueError before the network runs.  forward(),
+        match(), mutual_match(), sparse_warp() and flow_warp() are unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _nll_scope(cfg, symmetric)                # out-of-scope flags are refused before the network runs
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("match_loss: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"match_loss: target must be an int32 or int64 tensor, got "
+                            f"{target.dtype if torch.is_tensor(target) else type(target).__name__}")
+        coor_out = {}
+        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        coor_out.update(correspondence_nll(theta_raw, phi_raw, target, cfg, temperature, weight=weight, symmetric=symmetric))
         return coor_out
 
 

@@ -1202,3 +1202,103 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
     xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
     return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
             "match_window_prob": torch.exp(lse_win.detach() - lse.reshape(B, N)).reshape(B, fh, fw)}
+
+
+# ---- K49: trainable match readout — the correspondence negative log-likelihood in both softmax directions ---------------------------
+def _nll_scope(cfg: HotPathConfig, symmetric=True):
+    """ValueError for every flag outside correspondence_nll's scope — correspondence_sparse's, in messages that name match_loss;
+    checked before any tensor is looked at"""
+    name = "match_loss"
+    if not isinstance(symmetric, bool):
+        raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
+    if cfg.match_kernel != 1:
+        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope (the loss runs on the fused match_kernel 1 route)")
+    if not cfg.PONO_C:
+        raise ValueError(f"{name}: needs PONO_C (centring over the channels, as the fused match_kernel 1 route)")
+    for flag in ("warp_patch", "warp_bilinear"):
+        if getattr(cfg, flag):
+            raise ValueError(f"{name}: {flag} is out of scope (the plain flag set only, as sparse_warp)")
+    if cfg.warp_cycle_w > 0 or cfg.two_cycle or cfg.warp_mask_losstype == "cycle":
+        raise ValueError(f"{name}: the cycle terms (warp_cycle_w, two_cycle, warp_mask_losstype='cycle') are out of scope")
+    if ops.PRECISION != "f16x3":
+        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope (the loss reads the split-precision planes)")
+
+
+def _nll_targets(target, weight, B, fh, fw, Nk):
+    """target [B,h,w] int32 / int64 with values below Nk (negative: unsupervised), weight [B,h,w] fp32 >= 0 or None — TypeError /
+    ValueError in messages that name match_loss"""
+    name = "match_loss"
+    if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: target must be an int32 or int64 tensor, got {target.dtype if torch.is_tensor(target) else type(target).__name__}")
+    if tuple(target.shape) != (B, fh, fw):
+        raise ValueError(f"{name}: target is {tuple(target.shape)}, expected {(B, fh, fw)} (one exemplar position per content cell)")
+    if target.numel() and int(target.max()) >= Nk:
+        raise ValueError(f"{name}: target holds {int(target.max())}, expected flat exemplar positions below {Nk} (negative: unsupervised)")
+    if weight is not None:
+        if not torch.is_tensor(weight) or weight.dtype != torch.float32:
+            raise TypeError(f"{name}: weight must be a float32 tensor or None, got {weight.dtype if torch.is_tensor(weight) else type(weight).__name__}")
+        if tuple(weight.shape) != (B, fh, fw):
+            raise ValueError(f"{name}: weight is {tuple(weight.shape)}, expected {(B, fh, fw)}")
+        if weight.requires_grad:
+            raise ValueError(f"{name}: weight requires a gradient; it is data")
+        if weight.numel() and not bool((torch.isfinite(weight) & (weight >= 0)).all()):
+            raise ValueError(f"{name}: weight must be finite and >= 0")
+
+
+def nll_reduce(row_nll, col_nll, target, weight, symmetric: bool):
+    """loss_match = sum_i w_i (row_nll_i + [symmetric] col_nll_i) / max(sum over the supervised positions of w_i, tiny); with no
+    supervised position the numerator is a sum of zeros that still hangs on the graph: 0 with zero gradients.  Elementwise glue on
+    [B,N] tensors."""
+    sup = (target >= 0).reshape(row_nll.shape)
+    w = sup.to(row_nll.dtype) if weight is None else torch.where(sup, weight.reshape(row_nll.shape), torch.zeros_like(row_nll))
+    per = row_nll + col_nll if symmetric else row_nll
+    return (w * per).sum() / w.sum().clamp_min(torch.finfo(torch.float32).tiny)
+
+
+def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperature=0.01, *, weight=None, symmetric=True, exemplar=None):
+    """The supervised correspondence loss (K49): with s_ij = <qn_i, kn_j> / temperature over the projected, centred and normalised
+    features, the negative log-likelihood that content position i picks its target t_i among all exemplar positions (match_nll, the
+    row softmax) and that exemplar position t_i picks i among all content positions (back_nll, the column softmax) —
+    ops.corr_pair_nll, with gradients to theta_raw and phi_raw through the producer of the operand planes.  Nothing HWxHW is
+    allocated, forward or backward.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1 (planes made as correspondence_match makes them: match_lse / back_lse
+    are correspondence_mutual's bit for bit).  target [B,h,w] int32 / int64: flat exemplar position per content cell, negative =
+    unsupervised; weight [B,h,w] fp32 >= 0 or None.  Returns {match_nll, back_nll [B,h,w] (0 where unsupervised), match_lse [B,h,w],
+    back_lse [B,gh,gw], match_target_prob = exp(-match_nll) (detached), loss_match (see nll_reduce)}.
+
+    Scope and refusals: correspondence_sparse's (match_kernel 1, PONO_C, the plain flag set, COCOS_PRECISION=f16x3, 256 channels,
+    positions a multiple of 4, no prepared exemplar); everything else raises ValueError in a message that names match_loss — there is
+    no fall-back route.  CPU tensors raise CocosHipError."""
+    name = "match_loss"
+    _nll_scope(cfg, symmetric)
+    if exemplar is not None:
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the loss differentiates phi)")
+    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
+    if lazy[0] != lazy[1]:
+        raise TypeError(f"{name}: theta and phi must both be tensors or both be ops.LazyProj1x1")
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    N, Nk = fh * fw, gh * gw
+    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
+        raise ValueError(f"{name}: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
+                         f"{tuple(phi_raw.shape)}")
+    _nll_targets(target, weight, B, fh, fw, Nk)
+    if not (_hip_fp32(theta_raw) and target.is_cuda and (weight is None or weight.is_cuda)):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP tensors (fp32 features); the correspondence hot path has no CPU fallback")
+    if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_match_mutual_ok(B, N, Nk):
+        raise ValueError(f"{name}: the fused sweep does not take B={B}, {N} x {Nk} positions (positions must be multiples of 4)")
+    planes = ops.OperandPlanes()
+    keep = torch.is_grad_enabled() and (theta_raw.requires_grad or phi_raw.requires_grad)
+    if all(lazy) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw) and ops.proj_norm_fused_ok(phi_raw):
+        qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw, phi_raw, 1, planes, want_chan=keep)      # K23, as correspondence_match
+    else:
+        if all(lazy):
+            theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
+        qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
+        kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    tgt = target.reshape(B, N)
+    row_nll, col_nll, row_lse, col_lse = ops.corr_pair_nll(qn, kn, tgt, 1.0 / temperature, planes, return_lse=True, check_target=False)
+    return {"match_nll": row_nll.reshape(B, fh, fw), "back_nll": col_nll.reshape(B, fh, fw), "match_lse": row_lse.reshape(B, fh, fw),
+            "back_lse": col_lse.reshape(B, gh, gw), "match_target_prob": torch.exp(-row_nll.detach()).reshape(B, fh, fw),
+            "loss_match": nll_reduce(row_nll, col_nll, tgt, weight, symmetric)}

@@ -1161,6 +1161,208 @@ def corr_match_mutual(qn, kn, inv_temperature: float, planes: OperandPlanes | No
                                          inv_temperature)
 
 
+# ------------------------------------------------------------------------------------------
+# K49  trainable match readout: the two log-sum-exp vectors with gradients, and the correspondence NLL on top
+# ------------------------------------------------------------------------------------------
+def _corr_lse_bwd_planes(qh, ql, kh, kl, row_lse, col_lse, g_row, g_col, inv_temperature: float):
+    """K49's sweep on operand planes -> out_t [B,Nq,256] = inv_t sum_j (g_row_i exp(s_ij - row_lse_i) + g_col_j exp(s_ij - col_lse_j)) kn_j;
+    g_row [B,Nq] / g_col [B,Nk] fp32 contiguous or None (not both).  The key side is the same call with everything exchanged."""
+    B, Nq, K = qh.shape
+    Nk = kh.shape[1]
+    out_t = torch.empty((B, Nq, K), device=qh.device, dtype=torch.float32)
+    _call("corr_lse_bwd", "cocos_corr_lse_bwd_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), row_lse.data_ptr(),
+          col_lse.data_ptr(), _ptr(g_row), _ptr(g_col), out_t.data_ptr(), B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, _stream())
+    return out_t
+
+
+def _lse_grads(planes4, row_lse, col_lse, g_row, g_col, inv_t: float, need_q: bool, need_k: bool):
+    """(dq_t [B,Nq,256] | None, dk_t [B,Nk,256] | None) of sum g_row row_lse + sum g_col col_lse; both g None: zeros"""
+    qh, ql, kh, kl = planes4
+    dq_t = dk_t = None
+    if g_row is None and g_col is None:
+        if need_q:
+            dq_t = torch.zeros(qh.shape, device=qh.device, dtype=torch.float32)
+        if need_k:
+            dk_t = torch.zeros(kh.shape, device=kh.device, dtype=torch.float32)
+        return dq_t, dk_t
+    if need_q:
+        dq_t = _corr_lse_bwd_planes(qh, ql, kh, kl, row_lse, col_lse, g_row, g_col, inv_t)
+    if need_k:
+        dk_t = _corr_lse_bwd_planes(kh, kl, qh, ql, col_lse, row_lse, g_col, g_row, inv_t)
+    return dq_t, dk_t
+
+
+def _grad_vec(g, name: str):
+    return None if g is None else _chk(g, name)
+
+
+class _CorrLse(torch.autograd.Function):
+    """K49.  qn / kn are only the autograd inputs; saved: the four planes and the two lse vectors."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, inv_t: float, qh, ql, kh, kl):
+        rows, cols = _corr_match_mutual_planes(qh, ql, kh, kl, inv_t)
+        ctx.save_for_backward(qh, ql, kh, kl, rows[2], cols[2])
+        ctx.inv_t = float(inv_t)
+        ctx.set_materialize_grads(False)
+        return rows[2], cols[2]
+
+    @staticmethod
+    def backward(ctx, g_row, g_col):
+        qh, ql, kh, kl, row_lse, col_lse = ctx.saved_tensors
+        need_q, need_k = ctx.needs_input_grad[:2]
+        dq_t, dk_t = _lse_grads((qh, ql, kh, kl), row_lse, col_lse, _grad_vec(g_row, "corr_lse: d row_lse"),
+                                _grad_vec(g_col, "corr_lse: d col_lse"), ctx.inv_t, need_q, need_k)
+        return (_transpose(dq_t) if need_q else None, _transpose(dk_t) if need_k else None, None, None, None, None, None)
+
+
+def _pair_logits_planes(qh, ql, kh, kl, target, inv_temperature: float):
+    """s [B,Nq] = inv_t <qn_i, kn_target(i)> from the planes, K42's logit of the pair bit for bit; target int32 [B,Nq], negative: 0"""
+    B, Nq, K = qh.shape
+    s = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("pair_logits", "cocos_pair_logits_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), target.data_ptr(),
+          s.data_ptr(), B, K, Nq, kh.shape[1], float(inv_temperature), SPLIT_OPERAND_SCALE, _stream())
+    return s
+
+
+class _CorrPairNll(torch.autograd.Function):
+    """K49.  Saved for the backward: the four planes, row_lse [B,Nq], col_lse [B,Nk] and the table [B,Nq] — nothing with an Nq x Nk
+    extent.  Outputs: row_nll, col_nll and, without gradient, row_lse, col_lse."""
+
+    @staticmethod
+    def forward(ctx, qn, kn, target, inv_t: float, qh, ql, kh, kl):
+        rows, cols = _corr_match_mutual_planes(qh, ql, kh, kl, inv_t)
+        row_lse, col_lse = rows[2], cols[2]
+        s = _pair_logits_planes(qh, ql, kh, kl, target, inv_t)
+        sup = target >= 0
+        zero = torch.zeros_like(s)
+        row_nll = torch.where(sup, row_lse - s, zero)
+        col_nll = torch.where(sup, col_lse.gather(1, target.clamp(min=0).long()) - s, zero)
+        ctx.save_for_backward(qh, ql, kh, kl, row_lse, col_lse, target)
+        ctx.inv_t = float(inv_t)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(row_lse, col_lse)
+        return row_nll, col_nll, row_lse, col_lse
+
+    @staticmethod
+    def backward(ctx, g_r, g_c, _gl_r, _gl_c):
+        qh, ql, kh, kl, row_lse, col_lse, target = ctx.saved_tensors
+        need_q, need_k = ctx.needs_input_grad[:2]
+        none = (None,) * 8
+        if not (need_q or need_k):
+            return none
+        B, Nq, K = qh.shape
+        Nk = kh.shape[1]
+        dev = qh.device
+        sup = target >= 0
+        zero = torch.zeros((B, Nq), device=dev, dtype=torch.float32)
+        # d row_lse_i = g_r, d col_lse_{t(i)} += g_c, d s_i = -(g_r + g_c), all on the supervised positions only
+        g_r = None if g_r is None else torch.where(sup, _chk(g_r, "corr_pair_nll: d row_nll"), zero)
+        g_c = None if g_c is None else torch.where(sup, _chk(g_c, "corr_pair_nll: d col_nll"), zero)
+        if g_r is None and g_c is None:
+            return (torch.zeros((B, K, Nq), device=dev) if need_q else None, torch.zeros((B, K, Nk), device=dev) if need_k else None) + none[2:]
+        ds = -(g_r if g_c is None else g_c if g_r is None else g_r + g_c)
+        dims = (B, K, Nq, Nk, 1, 1, ctx.inv_t, SPLIT_OPERAND_SCALE, _stream())
+        # the key side of the pair terms walks the inverse table of the targets in a fixed order (K42's key backward at k = 1, Cv = 1):
+        # dk_pair[j] = inv_t sum_{t(i) = j} ds_i qn_i, and the same walk sums g_c over a key's queries — what the gather col_lse[t(i)]
+        # sends back to col_lse[j].  Unsupervised positions sit in key 0's list with ds = g_c = 0.
+        g_col = dk_pair = None
+        if need_k or g_c is not None:
+            entries, offsets = _inverse_index_table(target.clamp(min=0).view(B, Nq, 1), Nk)
+            dk_pair = torch.empty((B, Nk, K), device=dev, dtype=torch.float32) if need_k else None
+            g_col = torch.empty((B, Nk), device=dev, dtype=torch.float32) if g_c is not None else None
+            ones = torch.full((B, Nq), 1.0, device=dev, dtype=torch.float32)
+            _call("corr_pair_nll_bwd_key", "cocos_sparse_softmax_warp_bwd_key_f16x3", qh.data_ptr(), ql.data_ptr(), ones.data_ptr(),
+                  ds.data_ptr(), (g_c if g_c is not None else ones).data_ptr(), entries.data_ptr(), offsets.data_ptr(), _ptr(dk_pair),
+                  _ptr(g_col), *dims)
+            del entries, offsets, ones
+        dq_t, dk_t = _lse_grads((qh, ql, kh, kl), row_lse, col_lse, g_r, g_col, ctx.inv_t, need_q, need_k)
+        dqn = dkn = None
+        if need_q:
+            _call("pair_logits_bwd_query", "cocos_pair_logits_bwd_query_f16x3", kh.data_ptr(), kl.data_ptr(), target.data_ptr(), ds.data_ptr(),
+                  dq_t.data_ptr(), B, K, Nq, Nk, ctx.inv_t, SPLIT_OPERAND_SCALE, 1, _stream())
+            dqn = _transpose(dq_t)
+            del dq_t
+        if need_k:
+            dk_t.add_(dk_pair)
+            del dk_pair
+            dkn = _transpose(dk_t)
+        return (dqn, dkn) + none[2:]
+
+
+def _lse_operands(name: str, qn, kn):
+    """the argument checks corr_lse and corr_pair_nll share, in corr_match_mutual's order (the shape refusal included)"""
+    for t, what in ((qn, "qn"), (kn, "kn")):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name}: {what}: expected a tensor, got {type(t).__name__}")
+    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0] or qn.shape[1] != kn.shape[1]:
+        raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
+    if qn.shape[1] != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+
+
+def _lse_device(name: str, qn, kn, extra=()):
+    for t, what in ((qn, "qn"), (kn, "kn")) + tuple(extra):
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if PRECISION != "f16x3":
+        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
+    if not corr_match_mutual_ok(B, Nq, Nk):
+        raise ValueError(f"{name}: B={B} Nq={Nq} Nk={Nk}: the sweep takes Nq and Nk that are multiples of 4 (corr_match_mutual_ok)")
+
+
+def _lse_planes(name: str, qn, kn, planes):
+    if planes is None:
+        planes = OperandPlanes()
+    qn, kn = (t if planes.has(t) else _chk(t, f"{name}: {what}") for t, what in ((qn, "qn"), (kn, "kn")))
+    with torch.no_grad():
+        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
+    return qn, kn, pl
+
+
+def corr_lse(qn, kn, inv_temperature: float, planes: OperandPlanes | None = None):
+    """(row_lse [B,Nq], col_lse [B,Nk]): the log-sum-exp of inv_temperature <qn_i, kn_j> over the keys and over the queries, with
+    gradients for qn and kn (K49).  The forward is corr_match_mutual's sweep — the values are its row_lse / col_lse bit for bit; the
+    backward is one sweep per operand that needs a gradient (cocos_corr_lse_bwd_f16x3: S recomputed, W . Kn on the MFMA), with a null g
+    for an output nobody differentiated.  Nothing Nq x Nk is allocated, forward or backward; no atomics: bitwise reproducible.
+    Operands as corr_match_mutual; shapes outside corr_match_mutual_ok raise ValueError."""
+    name = "corr_lse"
+    _lse_operands(name, qn, kn)
+    _lse_device(name, qn, kn)
+    qn, kn, pl = _lse_planes(name, qn, kn, planes)
+    return _CorrLse.apply(qn, kn, float(inv_temperature), *pl)
+
+
+def corr_pair_nll(qn, kn, target, inv_temperature: float, planes: OperandPlanes | None = None, return_lse: bool = False,
+                  check_target: bool = True):
+    """The correspondence negative log-likelihood in both softmax directions (K49) -> (row_nll, col_nll), both [B,Nq] fp32:
+        row_nll[b,i] = row_lse[b,i] - s,   col_nll[b,i] = col_lse[b,t] - s,   s = inv_temperature <qn_i, kn_t>,   t = target[b,i]
+    — minus the log of the probability that query i picks key t among all keys, and that key t picks query i among all queries.
+    target [B,Nq] int32 / int64: the key every query should match; negative = unsupervised (both terms 0, no gradient); a target >= Nk
+    raises ValueError.  One autograd.Function, differentiable in qn and kn: it saves the operand planes, the two lse vectors and the
+    table, nothing with an Nq x Nk extent (`check_target` False: the caller has checked the range already — the check reads the
+    table's maximum back from the device, once per call is enough); the pair logit is sparse_softmax_warp's logit of the pair bit for bit; the key side of the
+    pair terms and the gradient the gather col_lse[t] sends to col_lse walk the inverse table of the targets in a fixed order (no
+    framework scatter, no atomics).  `return_lse`: also return (row_lse [B,Nq], col_lse [B,Nk]) without gradient.  Operands and refusals
+    as corr_lse."""
+    name = "corr_pair_nll"
+    _lse_operands(name, qn, kn)
+    if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: target must be an int32 or int64 tensor, got {target.dtype if torch.is_tensor(target) else type(target).__name__}")
+    B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
+    if tuple(target.shape) != (B, Nq):
+        raise ValueError(f"{name}: target is {tuple(target.shape)}, expected {(B, Nq)}")
+    if check_target and target.numel() and int(target.max()) >= Nk:
+        raise ValueError(f"{name}: target holds {int(target.max())}, expected values below Nk={Nk} (negative: unsupervised)")
+    _lse_device(name, qn, kn, ((target, "target"),))
+    qn, kn, pl = _lse_planes(name, qn, kn, planes)
+    with torch.no_grad():
+        target = target.clamp(min=-1).to(torch.int32).contiguous()
+    row_nll, col_nll, row_lse, col_lse = _CorrPairNll.apply(qn, kn, target, float(inv_temperature), *pl)
+    return (row_nll, col_nll, row_lse, col_lse) if return_lse else (row_nll, col_nll)
+
+
 def _grid2(name: str, what: str, grid):
     if (not isinstance(grid, (tuple, list)) or len(grid) != 2
             or any(isinstance(g, bool) or not isinstance(g, int) or g < 1 for g in grid)):

@@ -1298,6 +1298,38 @@ int cocos_match_round_trip(const int* row_idx, const int* col_idx, int* q_back, 
                            int wq, int hk, int wk, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K49 trainable match readout (corr_lse_bwd_f16x3.hip): the backward of K48's row_lse / col_lse and the pair terms of the
+ *     correspondence negative log-likelihood  row_nll_i = row_lse_i - s_{i,t(i)},  col_nll_i = col_lse_{t(i)} - s_{i,t(i)}.
+ *     Nothing Nq x Nk reaches memory.  qh,ql [B,Nq,256], kh,kl [B,Nk,256]: the position-major f16 hi / lo operand planes of
+ *     cocos_corr_match_mutual_f16x3 (value = (hi + lo) / operand_scale), 16-byte aligned.
+ *   cocos_corr_lse_bwd_f16x3: one dense sweep with S recomputed tile by tile in the readout kernels' arithmetic; writes
+ *         out_t[b,i,:] = inv_temperature sum_j w_ij kn[b,j,:]      (fp32 [B,Nq,256], position-major, 16-byte aligned)
+ *         w_ij = g_row[b,i] exp(s_ij - row_lse[b,i]) + g_col[b,j] exp(s_ij - col_lse[b,j])
+ *       — d qn of  sum_i g_row[i] row_lse[i] + sum_j g_col[j] col_lse[j].  The key side is the SAME entry with (qh, ql) <-> (kh, kl),
+ *       (row_lse, g_row) <-> (col_lse, g_col) and Nq <-> Nk exchanged.  g_row [B,Nq] / g_col [B,Nk] are each nullable (that term and
+ *       its exp are skipped; a null g is bitwise the same as a g of zeros), not both; the lse of a non-null g must be given.  The
+ *       exponent's argument is fma(s, scale, -lse) — one rounding, of the difference — clamped at 0 from above.  Keys past Nk and
+ *       queries past Nq of partial tiles contribute nothing.  The
+ *       second product runs on the MFMA with W split hi / lo at a per-sample power-of-two scale taken from max|g_row| + max|g_col|.
+ *       No atomics: bitwise reproducible.
+ *       Supported: K == 256, Nq % 4 == 0, Nk % 4 == 0 (otherwise COCOS_ERR_UNSUPPORTED); null / misaligned pointers (planes and out_t
+ *       16 bytes, vectors 4) and bad dims are COCOS_ERR_INVALID; all checked before any HIP call.
+ *   cocos_pair_logits_f16x3: s[b,i] = inv_temperature <qn_i, kn_t>, t = target[b,i] (int32 [B,Nq]; clamped into [0, Nk) from above),
+ *       formed as cocos_sparse_softmax_warp_fwd_f16x3 forms the logit of the same pair, bit for bit; t < 0: s = 0.
+ *   cocos_pair_logits_bwd_query_f16x3: dq_t[b,i,:] (+)= inv_temperature g[b,i] kn[b,t,:]  (zeros for t < 0); accumulate != 0 adds to
+ *       what dq_t holds (the sweep's output).  The key side is cocos_sparse_softmax_warp_bwd_key_f16x3 with k = 1 over the inverse
+ *       table of the targets.  Null pointers and bad dims: COCOS_ERR_INVALID; K != 256, or B Nq / B Nk at or above 2^31:
+ *       COCOS_ERR_UNSUPPORTED — before any HIP call.
+ * ------------------------------------------------------------------------------------- */
+int cocos_corr_lse_bwd_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* row_lse, const float* col_lse,
+                             const float* g_row, const float* g_col, float* out_t, int B, int K, int Nq, int Nk, float inv_temperature,
+                             float operand_scale, cocos_stream_t stream);
+int cocos_pair_logits_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* target, float* s, int B, int K,
+                            int Nq, int Nk, float inv_temperature, float operand_scale, cocos_stream_t stream);
+int cocos_pair_logits_bwd_query_f16x3(const void* kh, const void* kl, const int* target, const float* g, float* dq_t, int B, int K,
+                                      int Nq, int Nk, float inv_temperature, float operand_scale, int accumulate, cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K42 k-sparse correspondence warp with gradients (sparse_warp_f16x3.hip): attention over the k keys per query that the top-k match
  *     readout selected (selection itself carries no gradient),
  *         s[b,i,r] = inv_temperature <qn[b,:,i], kn[b,:,j_r]>,  j_r = idx[b,i,r],  w = softmax over r of s,
