@@ -625,6 +625,103 @@ class TopkMatchReadout:
         return torch.stack((self.index % gw, torch.div(self.index, gw, rounding_mode="floor")), dim=2)
 
 
+# ---- what the family's entry points share: argument checks, the fused-route scope, the operand planes, the readouts ----------------
+#: why each member refuses what lies off the fused match_kernel-1 route: the sentence its scope messages end in (_route_scope)
+_ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused match_kernel 1 route only",
+          "restrict": ": restrict runs on the fused match_kernel 1 route only",
+          "sparse": " (the sparse warp runs on the fused match_kernel 1 route)",
+          "nll": " (the loss runs on the fused match_kernel 1 route)"}
+
+
+def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool):
+    """ValueError for a flag set off the fused match_kernel-1 route, in this order: match_kernel, PONO_C, with `plain_flags` the warp
+    modes and the cycle terms, COCOS_PRECISION, with `match_fused` the ops.MATCH_FUSED switch; every message ends in _ROUTE[member]"""
+    route = _ROUTE[member]
+    if cfg.match_kernel != 1:
+        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope{route}")
+    if not cfg.PONO_C:
+        raise ValueError(f"{name}: needs PONO_C{route}")
+    if plain_flags:
+        for flag in ("warp_patch", "warp_bilinear"):
+            if getattr(cfg, flag):
+                raise ValueError(f"{name}: {flag} is out of scope{route}")
+        if cfg.warp_cycle_w > 0 or cfg.two_cycle or cfg.warp_mask_losstype == "cycle":
+            raise ValueError(f"{name}: the cycle terms (warp_cycle_w, two_cycle, warp_mask_losstype='cycle') are out of scope{route}")
+    if ops.PRECISION != "f16x3":
+        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope{route}")
+    if match_fused and not ops.MATCH_FUSED:
+        raise ValueError(f"{name}: ops.MATCH_FUSED = False (the materialised readout) is out of scope{route}")
+
+
+def _route_channels(name: str, member: str, channels):
+    if channels is not None and channels != ops.FUSED_K:
+        raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}{_ROUTE[member]}")
+
+
+def _topk_arg(name: str, topk):
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
+        raise ValueError(f"{name}: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+    return topk
+
+
+def _refine_temperature_arg(name: str, refine_temperature):
+    if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
+                                               and refine_temperature > 0):
+        raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+
+
+def _raw(t):
+    """the fp32 projection of a LazyProj1x1 (K0, computed once and cached by it); a tensor as it is"""
+    return t.raw() if isinstance(t, ops.LazyProj1x1) else t
+
+
+def _same_kind(name: str, theta_raw, phi_raw):
+    if isinstance(theta_raw, ops.LazyProj1x1) != isinstance(phi_raw, ops.LazyProj1x1):
+        raise TypeError(f"{name}: theta and phi must both be tensors or both be ops.LazyProj1x1")
+
+
+def _grids(theta_raw, phi_raw, exemplar=None):
+    """(B, C, fh, fw, gh, gw, N, Nk): the content grid of theta, the exemplar grid of phi (a prepared exemplar: the content's)"""
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
+    return B, C, fh, fw, gh, gw, fh * fw, gh * gw
+
+
+def _fused_width(name: str, theta_raw, phi_raw):
+    if theta_raw.shape[1] != ops.FUSED_K or phi_raw.shape[:2] != theta_raw.shape[:2]:
+        raise ValueError(f"{name}: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
+                         f"{tuple(phi_raw.shape)}")
+
+
+def _operand_planes(theta_raw, phi_raw, planes, *, detach: bool, want_chan, pair: bool = True):
+    """The one producer of the family's operand planes -> the handles (qn, kn) of theta's and phi's planes, registered in `planes`.
+    Two LazyProj1x1 of one input shape that ops.proj_norm_fused_ok takes go through K23 in one launch (`pair` False: never — the
+    caller's route projects and runs K1); everything else is projected where lazy (K0) and goes through K1 twice.  Every entry point
+    selects from these planes, which is what makes their indices and log-sum-exps agree bit for bit.  `detach`: a forward-only caller —
+    no graph, no channel-major planes; otherwise the handles carry the graph, K23 writes the channel-major planes on `want_chan`
+    and K1 for a side that requires a gradient."""
+    if (pair and isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
+            and ops.proj_norm_fused_ok(phi_raw)):
+        if detach:
+            theta_raw, phi_raw = theta_raw.detach(), phi_raw.detach()
+        return ops.proj_center_l2norm_planes_pair(theta_raw, phi_raw, 1, planes, want_chan=want_chan)      # K23
+    if detach:      # side by side: theta's projection and K1, then phi's
+        return tuple(ops.center_l2norm_planes(_flat(_raw(t)).detach(), 1, planes, want_chan=False) for t in (theta_raw, phi_raw))
+    theta_raw, phi_raw = _raw(theta_raw), _raw(phi_raw)     # both projections, then K1 twice
+    return ops.center_l2norm_planes(_flat(theta_raw), 1, planes), ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+
+
+def _readout(idx, mx, lse, shape, other):
+    """the MatchReadout of a kernel's (idx int32, max, lse) on the [B,h,w] `shape` of the side that asks; `other`: the grid indexed"""
+    return MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape), max_logit=mx.reshape(shape),
+                        lse=lse.reshape(shape), grid=other)
+
+
+def _rank_first(t, shape, k):
+    """a [B,N,k] kernel output (tiny) with the rank in front of the [B,h,w] `shape`: [B,k,h,w]"""
+    return t.reshape(tuple(shape) + (k,)).permute(0, 3, 1, 2).contiguous()
+
+
 def _refine_scope(name: str, cfg: HotPathConfig, refine, refine_temperature, topk, has_exemplar: bool, channels=None):
     """ValueError for a `refine` that is no radius, and — with refine > 0 — for everything outside the sub-cell refinement's scope (K44:
     top-1 on the fused match_kernel-1 route, no prepared exemplar); checked before any tensor is looked at.  `channels`: the width of
@@ -632,26 +729,15 @@ def _refine_scope(name: str, cfg: HotPathConfig, refine, refine_temperature, top
     top = ops.MATCH_REFINE_MAX_RADIUS
     if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= top:
         raise ValueError(f"{name}: refine={refine!r}: expected an integer in 0..{top} (0: no refinement)")
-    if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
-                                               and refine_temperature > 0):
-        raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+    _refine_temperature_arg(name, refine_temperature)
     if refine == 0:
         return
     if topk != 1:
         raise ValueError(f"{name}: refine={refine} with topk={topk}: the refinement is built for the single best match (topk = 1)")
     if has_exemplar:
         raise ValueError(f"{name}: refine={refine} with a prepared exemplar is out of scope (not built)")
-    route = "the sub-cell refinement (refine > 0) runs on the fused match_kernel 1 route only"
-    if cfg.match_kernel != 1:
-        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope: {route}")
-    if not cfg.PONO_C:
-        raise ValueError(f"{name}: needs PONO_C: {route}")
-    if ops.PRECISION != "f16x3":
-        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope: {route}")
-    if not ops.MATCH_FUSED:
-        raise ValueError(f"{name}: ops.MATCH_FUSED = False (the materialised readout) is out of scope: {route}")
-    if channels is not None and channels != ops.FUSED_K:
-        raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}: {route}")
+    _route_scope(name, cfg, "refine", plain_flags=False, match_fused=True)
+    _route_channels(name, "refine", channels)
 
 
 # ---- K47: label-restricted candidates ---------------------------------------------------------------------------------------------
@@ -678,23 +764,14 @@ def _restrict_scope(name: str, cfg: HotPathConfig, restrict, has_exemplar: bool,
         raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
     if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
         raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
-    route = "restrict runs on the fused match_kernel 1 route only"
-    if cfg.match_kernel != 1:
-        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope: {route}")
-    if not cfg.PONO_C:
-        raise ValueError(f"{name}: needs PONO_C: {route}")
-    if ops.PRECISION != "f16x3":
-        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope: {route}")
-    if not ops.MATCH_FUSED:
-        raise ValueError(f"{name}: ops.MATCH_FUSED = False (the materialised readout) is out of scope: {route}")
+    _route_scope(name, cfg, "restrict", plain_flags=False, match_fused=True)
     if has_exemplar:
         raise ValueError(f"{name}: restrict with a prepared exemplar is out of scope (not built)")
     if refine:
         raise ValueError(f"{name}: restrict with refine={refine!r} is out of scope (not built)")
     if search != "dense":
         raise ValueError(f"{name}: restrict with search={search!r} is out of scope: the label mask lives in the dense scan")
-    if channels is not None and channels != ops.FUSED_K:
-        raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}: {route}")
+    _route_channels(name, "restrict", channels)
 
 
 def _restrict_labels(name: str, restrict, seg_map, ref_seg_map, down, B, content_grid, exemplar_grid):
@@ -776,26 +853,20 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
     exemplar, refine = 0; everything else raises a ValueError that names restrict — nothing falls back to a materialised matrix."""
     if direction not in ("rows", "cols"):
         raise ValueError(f"correspondence_match: direction {direction!r}: expected 'rows' or 'cols'")
-    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
-        raise ValueError(f"correspondence_match: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
+    k = _topk_arg("correspondence_match", topk)
     _restrict_scope("correspondence_match", cfg, restrict, exemplar is not None, refine, channels=theta_raw.shape[1])
     _refine_scope("correspondence_match", cfg, refine, refine_temperature, topk, exemplar is not None, theta_raw.shape[1])
     if (exemplar is None) == (phi_raw is None):
         raise ValueError("correspondence_match: pass phi_raw or a prepared exemplar in its place (not both)")
-    B, C, fh, fw = theta_raw.shape
-    N = fh * fw
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw, exemplar)
     mk, inv_t = cfg.match_kernel, 1.0 / temperature
     rows = direction == "rows"
-    k = topk
     if exemplar is not None:
         exemplar.check(B)
         if exemplar.shape[1:] != theta_raw.shape[1:]:
             raise ValueError(f"prepared exemplar: feature grid {tuple(exemplar.shape)} does not match the content's {tuple(theta_raw.shape)}")
-    elif isinstance(theta_raw, ops.LazyProj1x1) != isinstance(phi_raw, ops.LazyProj1x1):
-        raise TypeError("correspondence_match: theta and phi must both be tensors or both be ops.LazyProj1x1")
-    gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
-    Nk = gh * gw
-    raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
+    else:
+        _same_kind("correspondence_match", theta_raw, phi_raw)
     if k > (Nk if rows else N):
         raise ValueError(f"correspondence_match: topk={k} exceeds the {Nk if rows else N} positions each row of direction={direction!r} ranges over")
     labels = None
@@ -818,7 +889,7 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             if isinstance(theta_raw, ops.LazyProj1x1) and ops.proj_norm_fused_ok(theta_raw):
                 qh, ql, _ = ops.proj_center_l2norm_planes_one(theta_raw, 1)      # K23, theta alone
             else:
-                qh, ql, _ = ops.center_l2norm_planes_fwd(_flat(raw(theta_raw)), 1)
+                qh, ql, _ = ops.center_l2norm_planes_fwd(_flat(_raw(theta_raw)), 1)
             if rows:
                 idx, mx, lse = ops.corr_match_shared(qh, ql, exemplar, inv_t) if k == 1 else ops.corr_topk_shared(qh, ql, exemplar, inv_t, k)
             else:       # the exemplar's positions ask: B different key sets (the contents), so the record's planes are needed per sample
@@ -826,12 +897,7 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 idx, mx, lse = ops._corr_match_planes(kh, kl, qh, ql, inv_t) if k == 1 else ops._corr_topk_planes(kh, kl, qh, ql, inv_t, k)
         elif fused:
             planes = ops.OperandPlanes()
-            if (isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
-                    and ops.proj_norm_fused_ok(phi_raw)):
-                qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw.detach(), phi_raw.detach(), 1, planes, want_chan=False)   # K23
-            else:
-                qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
-                kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
+            qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=True, want_chan=False)
             if labels is not None:      # K47: the side that asks brings its labels, operands and label tensors swap together
                 asks, other_side = (qn, kn) if rows else (kn, qn)
                 q_eff, k_eff, restricted = restrict_fallback(*(labels if rows else labels[::-1]), k)
@@ -851,17 +917,17 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             # the reference's default on the fused family's shapes: ONE HWxHW tensor (T, from the x-box GEMM's epilogue), read once
             # by K37 (k > 1: K41) — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
             if exemplar is not None:       # the record's planes and (nu, b): the key side is not recomputed
-                th = raw(theta_raw).detach()
+                th = _raw(theta_raw).detach()
                 boxed = _BoxedCorr(th, th.view_as(th), inv_t, prepared_k=exemplar.box_planes(B))
             elif isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:      # K25 / proj_unfold3_stats inside _BoxedCorr
                 boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
             else:
-                boxed = _BoxedCorr(raw(theta_raw).detach(), raw(phi_raw).detach(), inv_t)
+                boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
             idx, mx, lse = boxed.match(rows, k)
             del boxed
         else:
-            th = raw(theta_raw).detach()
-            ph = (exemplar.phi_raw(B) if exemplar is not None else raw(phi_raw)).detach()
+            th = _raw(theta_raw).detach()
+            ph = (exemplar.phi_raw(B) if exemplar is not None else _raw(phi_raw)).detach()
             if mk == 3 and cfg.PONO_C:
                 f = _box3_logits(th, ph, inv_t, transposed=not rows)
             else:   # f^T is the same matrix with the operands exchanged (centring and normalisation are per tensor)
@@ -870,16 +936,14 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             del f
         own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
         shape = (B,) + own
-        if k > 1:      # the [B,N,k] kernel outputs (tiny) with the rank in front of the grid
-            rank_first = lambda t: t.reshape(shape + (k,)).permute(0, 3, 1, 2).contiguous()
+        if k > 1:
             lse = lse.reshape(shape)
-            val = rank_first(mx)
-            return TopkMatchReadout(index=rank_first(idx.to(torch.int64)), prob=torch.exp(val - lse.unsqueeze(1)), logit=val, lse=lse,
-                                    grid=other, restricted=None if restricted is None else restricted.reshape(shape))
-        m = MatchReadout(index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape),
-                         max_logit=mx.reshape(shape), lse=lse.reshape(shape), grid=other)
+            val = _rank_first(mx, shape, k)
+            return TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.unsqueeze(1)), logit=val,
+                                    lse=lse, grid=other, restricted=None if restricted is None else restricted.reshape(shape))
+        m = _readout(idx, mx, lse, shape, other)
         if refine:
-            m.offset = off.reshape(shape + (2,)).permute(0, 3, 1, 2).contiguous()
+            m.offset = _rank_first(off, shape, 2)
             m.window_prob = torch.exp(lse_win - lse).reshape(shape)
         if restricted is not None:
             m.restricted = restricted.reshape(shape)
@@ -941,28 +1005,17 @@ def correspondence_mutual(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.
     max_dist = _max_dist(name, max_dist)
     if (exemplar is None) == (phi_raw is None):
         raise ValueError(f"{name}: pass phi_raw or a prepared exemplar in its place (not both)")
-    B, C, fh, fw = theta_raw.shape
-    gh, gw = (fh, fw) if exemplar is not None else tuple(phi_raw.shape[2:])
-    N, Nk = fh * fw, gh * gw
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw, exemplar)
     inv_t = 1.0 / temperature
     with torch.no_grad():
         fused = (exemplar is None and isinstance(theta_raw, ops.LazyProj1x1) == isinstance(phi_raw, ops.LazyProj1x1)
                  and _hip_fp32(theta_raw) and mutual_fused_route(cfg, B, C, N, Nk, False))
         if fused:
-            raw = lambda t: t.raw() if isinstance(t, ops.LazyProj1x1) else t
-            planes = ops.OperandPlanes()      # made as correspondence_match's fused route makes them
-            if (isinstance(theta_raw, ops.LazyProj1x1) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw)
-                    and ops.proj_norm_fused_ok(phi_raw)):
-                qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw.detach(), phi_raw.detach(), 1, planes, want_chan=False)   # K23
-            else:
-                qn = ops.center_l2norm_planes(_flat(raw(theta_raw)).detach(), 1, planes, want_chan=False)
-                kn = ops.center_l2norm_planes(_flat(raw(phi_raw)).detach(), 1, planes, want_chan=False)
+            planes = ops.OperandPlanes()
+            qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=True, want_chan=False)      # correspondence_match's planes
             (ri, rm, rl), (ci, cm, cl) = ops.corr_match_mutual(qn, kn, inv_t, planes)
-            readout = lambda idx, mx, lse, shape, other: MatchReadout(
-                index=idx.to(torch.int64).reshape(shape), prob=torch.exp(mx - lse).reshape(shape), max_logit=mx.reshape(shape),
-                lse=lse.reshape(shape), grid=other)
-            rows = readout(ri, rm, rl, (B, fh, fw), (gh, gw))
-            cols = readout(ci, cm, cl, (B, gh, gw), (fh, fw))
+            rows = _readout(ri, rm, rl, (B, fh, fw), (gh, gw))
+            cols = _readout(ci, cm, cl, (B, gh, gw), (fh, fw))
         else:      # two readouts; every refusal (CPU tensors, mixed operand kinds, a stale record) is correspondence_match's
             rows = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=exemplar, direction="rows")
             cols = correspondence_match(theta_raw, phi_raw, cfg, temperature, exemplar=exemplar, direction="cols")
@@ -977,22 +1030,9 @@ def correspondence_mutual(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.
 # ---- K42: differentiable k-sparse warp over the top-k matches ---------------------------------------------------------------------
 def _sparse_scope(cfg: HotPathConfig, topk):
     """ValueError for every flag outside correspondence_sparse's scope (checked before any tensor is looked at) -> k"""
-    name = "correspondence_sparse"
-    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
-        raise ValueError(f"{name}: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
-    if cfg.match_kernel != 1:
-        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope (the sparse warp runs on the fused match_kernel 1 route)")
-    if not cfg.PONO_C:
-        raise ValueError(f"{name}: needs PONO_C (centring over the channels, as the fused match_kernel 1 route)")
-    for flag in ("warp_patch", "warp_bilinear"):
-        if getattr(cfg, flag):
-            raise ValueError(f"{name}: {flag} is out of scope (the sparse warp up-samples the pooled exemplar by nearest neighbour)")
-    if cfg.warp_cycle_w > 0 or cfg.two_cycle or cfg.warp_mask_losstype == "cycle":
-        raise ValueError(f"{name}: the cycle terms (warp_cycle_w, two_cycle, warp_mask_losstype='cycle') are out of scope: they need the "
-                         "column softmax over all positions")
-    if ops.PRECISION != "f16x3":
-        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope (the candidates come from the split-precision readout)")
-    return topk
+    k = _topk_arg("correspondence_sparse", topk)
+    _route_scope("correspondence_sparse", cfg, "sparse", plain_flags=True, match_fused=False)
+    return k
 
 
 def _sparse_search(search, search_opts):
@@ -1071,35 +1111,29 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     pm = _sparse_search(search, search_opts)
     if exemplar is not None:
         raise ValueError("correspondence_sparse: a prepared exemplar is out of scope (it is forward-only; the sparse warp differentiates phi)")
-    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
-    if lazy[0] != lazy[1]:
-        raise TypeError("correspondence_sparse: theta and phi must both be tensors or both be ops.LazyProj1x1")
-    B, C, fh, fw = theta_raw.shape
-    N, Nk, down = fh * fw, phi_raw.shape[2] * phi_raw.shape[3], cfg.down
-    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
-        raise ValueError(f"correspondence_sparse: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
-                         f"{tuple(phi_raw.shape)}")
+    _same_kind("correspondence_sparse", theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    down = cfg.down
+    _fused_width("correspondence_sparse", theta_raw, phi_raw)
     if k > Nk:
         raise ValueError(f"correspondence_sparse: topk={k} exceeds the {Nk} exemplar positions")
-    if tuple(ref_img.shape[2:]) != (phi_raw.shape[2] * down, phi_raw.shape[3] * down) or ref_img.shape[3] % 4 != 0:
+    if tuple(ref_img.shape[2:]) != (gh * down, gw * down) or ref_img.shape[3] % 4 != 0:
         raise ValueError(f"correspondence_sparse: ref_img {tuple(ref_img.shape)} is not down={down} times the exemplar grid "
-                         f"{tuple(phi_raw.shape[2:])} (width a multiple of 4)")
+                         f"{(gh, gw)} (width a multiple of 4)")
     labels = None
     if restrict is not None:
-        labels = _restrict_labels("correspondence_sparse", restrict, seg_map, ref_seg_map, down, B, (fh, fw), tuple(phi_raw.shape[2:]))
+        labels = _restrict_labels("correspondence_sparse", restrict, seg_map, ref_seg_map, down, B, (fh, fw), (gh, gw))
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError("correspondence_sparse: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(k):
         raise ValueError(f"correspondence_sparse: the fused top-k readout does not take B={B}, {N} x {Nk} positions, k={k} "
                          "(positions must be multiples of 4)" + ("; restrict runs on no other route" if restrict is not None else ""))
-    if all(lazy):
-        theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
-    # K1 with autograd, in the flavour correspondence_match selects from: the position-major operand planes are written once and serve
-    # the selection and the warp alike (the same planes, so the same candidates as correspondence_match, bit for bit); qn / kn are the
-    # handles of those planes, and each keeps its channel-major planes for its own backward when it is differentiated
+    # K1 with autograd (_operand_planes without the K23 pair: lazy operands are projected): the position-major operand planes are
+    # written once and serve the selection and the warp alike (the same planes, so the same candidates as correspondence_match, bit
+    # for bit); qn / kn are the handles of those planes, and each keeps its channel-major planes for its own backward when it is
+    # differentiated
     planes = ops.OperandPlanes()
-    qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
-    kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=False, want_chan=None, pair=False)
     inv_t = 1.0 / temperature
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
     with torch.no_grad():
@@ -1110,8 +1144,8 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
         elif pm is None:
             idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                # selection: no gradient
         else:
-            idx, _ = ops.patchmatch_topk(qn, kn, inv_t, k, (tuple(theta_raw.shape[2:]), tuple(phi_raw.shape[2:])),
-                                         _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k), pm["strides"],
+            idx, _ = ops.patchmatch_topk(qn, kn, inv_t, k, ((fh, fw), (gh, gw)),
+                                         _patchmatch_coarse_init(_raw(theta_raw), _raw(phi_raw), inv_t, k), pm["strides"],
                                          (pm["radii"], pm["radius0"]), pm["seed"], planes)
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
     o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True)
@@ -1120,9 +1154,8 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
     if direct_mask:
         out["warp_mask"] = o_mask.reshape(B, -1, fh, fw)
-    rank_first = lambda t: t.reshape(B, fh, fw, k).permute(0, 3, 1, 2).contiguous()
-    out["match_index"] = rank_first(idx.to(torch.int64))
-    out["match_weight"] = rank_first(w)
+    out["match_index"] = _rank_first(idx.to(torch.int64), (B, fh, fw), k)
+    out["match_weight"] = _rank_first(w, (B, fh, fw), k)
     if restricted is not None:
         out["match_restricted"] = restricted.reshape(B, fh, fw)
     return out
@@ -1136,9 +1169,7 @@ def _flow_scope(cfg: HotPathConfig, radius, refine_temperature):
     name, top = "correspondence_flow", ops.MATCH_REFINE_MAX_RADIUS
     if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
         raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
-    if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
-                                               and refine_temperature > 0):
-        raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+    _refine_temperature_arg(name, refine_temperature)
 
 
 def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, temperature=0.01, *, radius=1, refine_temperature=None,
@@ -1150,7 +1181,7 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
     is sampled bilinearly at the refined position — ops.subcell_warp, with a gradient to the offset.  A photometric loss on warp_out
     or a regression loss on match_offset therefore trains theta and phi below the feature grid.  Nothing HWxHW is allocated.
 
-    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1; the planes are made as correspondence_match makes them (K23 from a
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1; the planes come from _operand_planes, correspondence_match's producer (K23 from a
     lazy pair it takes, K1 otherwise), so match_index and match_offset are correspondence_match(refine=radius)'s bit for bit.
     ref_img [B,3,H,W] gets no gradient (one that requires it raises ValueError).  Returns {warp_out [B,3,H,W], match_index [B,h,w]
     int64, match_offset [B,2,h,w] (x, y; in cells; with gradient), match_xy_sub [B,2,h,w] = match_xy + match_offset (with gradient),
@@ -1163,15 +1194,10 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
     _flow_scope(cfg, radius, refine_temperature)
     if exemplar is not None:
         raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the refinement differentiates phi)")
-    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
-    if lazy[0] != lazy[1]:
-        raise TypeError(f"{name}: theta and phi must both be tensors or both be ops.LazyProj1x1")
-    B, C, fh, fw = theta_raw.shape
-    gh, gw = phi_raw.shape[2:]
-    N, Nk, down = fh * fw, gh * gw, cfg.down
-    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
-        raise ValueError(f"{name}: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
-                         f"{tuple(phi_raw.shape)}")
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    down = cfg.down
+    _fused_width(name, theta_raw, phi_raw)
     if ref_img.dim() != 4 or ref_img.shape[0] != B or tuple(ref_img.shape[2:]) != (gh * down, gw * down):
         raise ValueError(f"{name}: ref_img {tuple(ref_img.shape)} is not a batch of {B} images of down={down} times the exemplar grid "
                          f"{(gh, gw)}")
@@ -1183,13 +1209,7 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
         raise ValueError(f"{name}: the fused readout does not take B={B}, {N} x {Nk} positions (positions must be multiples of 4)")
     planes = ops.OperandPlanes()
     keep = torch.is_grad_enabled() and (theta_raw.requires_grad or phi_raw.requires_grad)
-    if all(lazy) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw) and ops.proj_norm_fused_ok(phi_raw):
-        qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw, phi_raw, 1, planes, want_chan=keep)      # K23, as correspondence_match
-    else:
-        if all(lazy):
-            theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
-        qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
-        kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=False, want_chan=keep)
     inv_t = 1.0 / temperature
     inv_rt = inv_t if refine_temperature is None else 1.0 / refine_temperature
     with torch.no_grad():
@@ -1198,7 +1218,7 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
     off, lse_win = ops.soft_match_offset(qn, kn, idx, (gh, gw), inv_rt, radius, planes)
     warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
     index = idx.to(torch.int64).reshape(B, fh, fw)
-    offset = off.reshape(B, fh, fw, 2).permute(0, 3, 1, 2).contiguous()
+    offset = _rank_first(off, (B, fh, fw), 2)
     xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
     return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
             "match_window_prob": torch.exp(lse_win.detach() - lse.reshape(B, N)).reshape(B, fh, fw)}
@@ -1211,17 +1231,7 @@ def _nll_scope(cfg: HotPathConfig, symmetric=True):
     name = "match_loss"
     if not isinstance(symmetric, bool):
         raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
-    if cfg.match_kernel != 1:
-        raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope (the loss runs on the fused match_kernel 1 route)")
-    if not cfg.PONO_C:
-        raise ValueError(f"{name}: needs PONO_C (centring over the channels, as the fused match_kernel 1 route)")
-    for flag in ("warp_patch", "warp_bilinear"):
-        if getattr(cfg, flag):
-            raise ValueError(f"{name}: {flag} is out of scope (the plain flag set only, as sparse_warp)")
-    if cfg.warp_cycle_w > 0 or cfg.two_cycle or cfg.warp_mask_losstype == "cycle":
-        raise ValueError(f"{name}: the cycle terms (warp_cycle_w, two_cycle, warp_mask_losstype='cycle') are out of scope")
-    if ops.PRECISION != "f16x3":
-        raise ValueError(f"{name}: COCOS_PRECISION={ops.PRECISION} is out of scope (the loss reads the split-precision planes)")
+    _route_scope(name, cfg, "nll", plain_flags=True, match_fused=False)
 
 
 def _nll_targets(target, weight, B, fh, fw, Nk):
@@ -1262,8 +1272,8 @@ def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperatu
     ops.corr_pair_nll, with gradients to theta_raw and phi_raw through the producer of the operand planes.  Nothing HWxHW is
     allocated, forward or backward.
 
-    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1 (planes made as correspondence_match makes them: match_lse / back_lse
-    are correspondence_mutual's bit for bit).  target [B,h,w] int32 / int64: flat exemplar position per content cell, negative =
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1 (planes from _operand_planes, correspondence_mutual's producer: match_lse /
+    back_lse are its bit for bit).  target [B,h,w] int32 / int64: flat exemplar position per content cell, negative =
     unsupervised; weight [B,h,w] fp32 >= 0 or None.  Returns {match_nll, back_nll [B,h,w] (0 where unsupervised), match_lse [B,h,w],
     back_lse [B,gh,gw], match_target_prob = exp(-match_nll) (detached), loss_match (see nll_reduce)}.
 
@@ -1274,15 +1284,9 @@ def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperatu
     _nll_scope(cfg, symmetric)
     if exemplar is not None:
         raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the loss differentiates phi)")
-    lazy = isinstance(theta_raw, ops.LazyProj1x1), isinstance(phi_raw, ops.LazyProj1x1)
-    if lazy[0] != lazy[1]:
-        raise TypeError(f"{name}: theta and phi must both be tensors or both be ops.LazyProj1x1")
-    B, C, fh, fw = theta_raw.shape
-    gh, gw = phi_raw.shape[2:]
-    N, Nk = fh * fw, gh * gw
-    if C != ops.FUSED_K or phi_raw.shape[:2] != (B, C):
-        raise ValueError(f"{name}: needs theta / phi with {ops.FUSED_K} channels and one batch, got {tuple(theta_raw.shape)} and "
-                         f"{tuple(phi_raw.shape)}")
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    _fused_width(name, theta_raw, phi_raw)
     _nll_targets(target, weight, B, fh, fw, Nk)
     if not (_hip_fp32(theta_raw) and target.is_cuda and (weight is None or weight.is_cuda)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP tensors (fp32 features); the correspondence hot path has no CPU fallback")
@@ -1290,13 +1294,7 @@ def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperatu
         raise ValueError(f"{name}: the fused sweep does not take B={B}, {N} x {Nk} positions (positions must be multiples of 4)")
     planes = ops.OperandPlanes()
     keep = torch.is_grad_enabled() and (theta_raw.requires_grad or phi_raw.requires_grad)
-    if all(lazy) and theta_raw.x.shape == phi_raw.x.shape and ops.proj_norm_fused_ok(theta_raw) and ops.proj_norm_fused_ok(phi_raw):
-        qn, kn = ops.proj_center_l2norm_planes_pair(theta_raw, phi_raw, 1, planes, want_chan=keep)      # K23, as correspondence_match
-    else:
-        if all(lazy):
-            theta_raw, phi_raw = theta_raw.raw(), phi_raw.raw()
-        qn = ops.center_l2norm_planes(_flat(theta_raw), 1, planes)
-        kn = ops.center_l2norm_planes(_flat(phi_raw), 1, planes)
+    qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=False, want_chan=keep)
     tgt = target.reshape(B, N)
     row_nll, col_nll, row_lse, col_lse = ops.corr_pair_nll(qn, kn, tgt, 1.0 / temperature, planes, return_lse=True, check_target=False)
     return {"match_nll": row_nll.reshape(B, fh, fw), "back_nll": col_nll.reshape(B, fh, fw), "match_lse": row_lse.reshape(B, fh, fw),

@@ -911,13 +911,79 @@ def _readout_planes(name: str, qh, ql, kh, kl):
     return B, K, Nq, Nk, Nk * K if Be == B else 0
 
 
+def _readout_outputs(lead, k, device):
+    """(idx int32, val, lse) for a readout kernel to fill: idx and val `lead` (+ (k,) with k candidates per row), lse `lead`"""
+    full = tuple(lead) + ((k,) if k else ())
+    return (torch.empty(full, device=device, dtype=torch.int32), torch.empty(full, device=device, dtype=torch.float32),
+            torch.empty(tuple(lead), device=device, dtype=torch.float32))
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def _grid_pair(name: str, what: str, grid):
+    try:
+        h, w = grid
+    except (TypeError, ValueError):
+        h = w = None
+    if not (_is_int(h) and _is_int(w) and h >= 1 and w >= 1):
+        raise ValueError(f"{name}: {what}={grid!r}: expected a pair (h, w) of positive integers")
+    return h, w
+
+
+def _int_table(name: str, what: str, t, shape=None, any_int: bool = False):
+    """An index or label table -> contiguous int32.  TypeError unless `t` is an int32 / int64 tensor (`any_int`: any integer dtype),
+    ValueError unless it has `shape` (None: the caller's own check); the device is the caller's next refusal.  Wider types are
+    narrowed after a clamp into int32's range, which keeps a negative entry negative and a large one out of any range a kernel
+    clamps to (two label classes above 2^31 - 2 would collide: no label map has them)."""
+    if not torch.is_tensor(t) or ((t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex) if any_int
+                                  else t.dtype not in (torch.int32, torch.int64)):
+        raise TypeError(f"{name}: {what} must be an {'integer' if any_int else 'int32 or int64'} tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    return (t if t.dtype == torch.int32 else t.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
+
+
+def _gate(name: str, tensors, needs_f16x3: bool):
+    """The refusals that follow every TypeError / ValueError of an argument: each (tensor, what) lives on the GPU, then — where only
+    the split-precision kernel exists — the flavour"""
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    if needs_f16x3 and PRECISION != "f16x3":
+        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+
+
+def _operand_shapes(name: str, qn, kn, nq=None, nk=None, fit: str = "", width: bool = True):
+    """qn [B,256,Nq] and kn [B,256,Nk] of one batch and width (`nq` / `nk`: the positions a grid asks for, `fit` names it; `width`:
+    256 channels) -> (B, Nq, Nk); ValueError"""
+    if (qn.dim() != 3 or kn.dim() != 3 or qn.shape[:2] != kn.shape[:2] or (nq is not None and qn.shape[2] != nq)
+            or (nk is not None and kn.shape[2] != nk)):
+        raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk]{fit}, got {tuple(qn.shape)} and {tuple(kn.shape)}")
+    if width and qn.shape[1] != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    return qn.shape[0], qn.shape[2], kn.shape[2]
+
+
+def _fetch_planes(name: str, qn, kn, planes, detach: bool, same_batch: bool = False):
+    """(qn, kn, (qh, ql, kh, kl)): the position-major operand planes of the two operands — a producer's, where the handle is
+    registered in `planes`, else split here from the fp32 tensor (`detach`: a forward-only caller's)"""
+    if planes is None:
+        planes = OperandPlanes()
+    qn, kn = (t if planes.has(t) else _chk(t.detach() if detach else t, f"{name}: {what}") for t, what in ((qn, "qn"), (kn, "kn")))
+    with torch.no_grad():
+        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
+    if same_batch and pl[2].shape[0] != pl[0].shape[0]:
+        raise ValueError(f"{name}: query and key batch differ")
+    return qn, kn, pl
+
+
 def _corr_match_planes(qh, ql, kh, kl, inv_temperature: float):
     """K36a on operand planes: qh, ql [B,Nq,256], kh, kl [B or 1,Nk,256] (1: every sample reads the one key set, batch stride 0)
     -> (idx int32, max, lse), each [B,Nq]."""
     B, K, Nq, Nk, k_stride = _readout_planes("corr_match", qh, ql, kh, kl)
-    idx = torch.empty((B, Nq), device=qh.device, dtype=torch.int32)
-    mx = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
-    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    idx, mx, lse = _readout_outputs((B, Nq), None, qh.device)
     _call("corr_match", "cocos_corr_match_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
           mx.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, float(inv_temperature), SPLIT_OPERAND_SCALE, k_stride, _stream())
     return idx, mx, lse
@@ -928,15 +994,9 @@ def corr_match(qn, kn, inv_temperature: float, planes: OperandPlanes | None = No
     row log-sum-exp — corr_softmax_warp's logits without its value tensor (K36a; forward only).  qn [B,256,Nq], kn [B,256,Nk]
     unit-norm columns, or the handles of producer-made planes registered in `planes` (center_l2norm_planes, K23), as for
     corr_softmax_warp.  Shapes the kernel does not take (K != 256, Nk % 4 != 0) raise: materialise and use row_argmax_lse."""
-    for t, name in ((qn, "qn"), (kn, "kn")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"corr_match: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if planes is None:
-        planes = OperandPlanes()
+    _gate("corr_match", ((qn, "qn"), (kn, "kn")), False)
     with torch.no_grad():
-        qn, kn = (t if planes.has(t) else _chk(t.detach(), "corr_match") for t in (qn, kn))
-        return _corr_match_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
-                                  inv_temperature)
+        return _corr_match_planes(*_fetch_planes("corr_match", qn, kn, planes, True)[2], inv_temperature)
 
 
 def corr_match_shared(qh, ql, keys: PreparedKeys, inv_temperature: float):
@@ -960,9 +1020,7 @@ def row_argmax_lse(f: torch.Tensor):
     """(idx int32, max, lse), each f.shape[:-1], of the rows of a materialised logit matrix f [..., Nk] in one sweep (K36b):
     torch.max(f, -1) (the lowest index among equal maxima) and torch.logsumexp(f, -1).  Forward only."""
     f, lead, B, Nq, Nk = _readout_rows("row_argmax_lse", f)
-    idx = torch.empty(lead, device=f.device, dtype=torch.int32)
-    mx = torch.empty(lead, device=f.device, dtype=torch.float32)
-    lse = torch.empty(lead, device=f.device, dtype=torch.float32)
+    idx, mx, lse = _readout_outputs(lead, None, f.device)
     _call("row_argmax_lse", "cocos_row_argmax_lse", f.data_ptr(), idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, Nq, Nk, _stream())
     return idx, mx, lse
 
@@ -972,8 +1030,7 @@ def gather_patches(img: torch.Tensor, idx: torch.Tensor, h: int, w: int, down: i
     — a bitwise copy.  img [Be,C,H,W] fp32 with H == h*down, W == w*down and Be == B or 1 (one exemplar for all); idx [B,h*w] or
     [B,h,w], any integer type (values outside [0, h*w) are clamped into it)."""
     img = _chk(img.detach(), "gather_patches: img")
-    if not idx.is_cuda:
-        raise _lib.CocosHipError("gather_patches: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    _gate("gather_patches", ((idx, "idx"),), False)
     if idx.dtype.is_floating_point or idx.dtype == torch.bool:
         raise TypeError(f"gather_patches: idx must be an integer tensor, got {idx.dtype}")
     Be, C, H, W = img.shape
@@ -1010,9 +1067,7 @@ def _corr_topk_planes(qh, ql, kh, kl, inv_temperature: float, k: int):
     """K39a on operand planes (as _corr_match_planes) -> (idx int32 [B,Nq,k], val [B,Nq,k], lse [B,Nq])."""
     B, K, Nq, Nk, k_stride = _readout_planes("corr_topk", qh, ql, kh, kl)
     k = _check_topk("corr_topk", k, Nk)
-    idx = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
-    val = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
-    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    idx, val, lse = _readout_outputs((B, Nq), k, qh.device)
     _call("corr_topk", "cocos_corr_topk_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
           val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature), SPLIT_OPERAND_SCALE, k_stride, _stream())
     return idx, val, lse
@@ -1023,15 +1078,9 @@ def corr_topk(qn, kn, inv_temperature: float, k: int, planes: OperandPlanes | No
     descending order (the lower j first among bitwise-equal logits), their j, and the row log-sum-exp (K39a; forward only).  Rank 0
     and lse are corr_match's outputs bit for bit.  Operands as corr_match.  1 <= k <= MATCH_TOPK_MAX, k <= Nk (ValueError); a k that
     corr_topk_ok refuses and the shapes corr_match refuses raise: materialise and use row_topk_lse."""
-    for t, name in ((qn, "qn"), (kn, "kn")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"corr_topk: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if planes is None:
-        planes = OperandPlanes()
+    _gate("corr_topk", ((qn, "qn"), (kn, "kn")), False)
     with torch.no_grad():
-        qn, kn = (t if planes.has(t) else _chk(t.detach(), "corr_topk") for t in (qn, kn))
-        return _corr_topk_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
-                                 inv_temperature, k)
+        return _corr_topk_planes(*_fetch_planes("corr_topk", qn, kn, planes, True)[2], inv_temperature, k)
 
 
 def corr_topk_shared(qh, ql, keys: PreparedKeys, inv_temperature: float, k: int):
@@ -1042,29 +1091,13 @@ def corr_topk_shared(qh, ql, keys: PreparedKeys, inv_temperature: float, k: int)
 
 
 # K47  label-restricted readout: the same scan over the keys each query's label allows
-def _label_table(name: str, what: str, lab, B, N):
-    """TypeError / ValueError of a label tensor (before any device is looked at)"""
-    if not torch.is_tensor(lab) or lab.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: {what} must be an int32 or int64 tensor")
-    if tuple(lab.shape) != (B, N):
-        raise ValueError(f"{name}: {what} is {tuple(lab.shape)}, expected {(B, N)}")
-
-
-def _narrow_labels(lab):
-    # (int64 labels are narrowed after a clamp into int32's range, which keeps a negative label negative; two classes above 2^31 - 2
-    #  would collide: no label map has them)
-    return (lab if lab.dtype == torch.int32 else lab.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
-
-
 def _corr_topk_labels_planes(qh, ql, kh, kl, q_label, k_label, inv_temperature: float, k: int):
     """K47 on operand planes (as _corr_topk_planes) and int32 contiguous labels [B,Nq], [Be,Nk] on their device"""
     B, K, Nq, Nk, k_stride = _readout_planes("corr_topk_labelled", qh, ql, kh, kl)
     k = _check_topk("corr_topk_labelled", k, Nk)
     if tuple(q_label.shape) != (B, Nq) or tuple(k_label.shape) != (kh.shape[0], Nk):
         raise ValueError(f"corr_topk_labelled: labels {tuple(q_label.shape)}, {tuple(k_label.shape)} do not fit q{tuple(qh.shape)} k{tuple(kh.shape)}")
-    idx = torch.empty((B, Nq, k), device=qh.device, dtype=torch.int32)
-    val = torch.empty((B, Nq, k), device=qh.device, dtype=torch.float32)
-    lse = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    idx, val, lse = _readout_outputs((B, Nq), k, qh.device)
     _call("corr_topk_labelled", "cocos_corr_topk_labels_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
           q_label.data_ptr(), k_label.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature),
           SPLIT_OPERAND_SCALE, k_stride, _stream())
@@ -1080,23 +1113,13 @@ def corr_topk_labelled(qn, kn, q_label, k_label, inv_temperature: float, k: int,
     lse = -inf.  With nothing restricted the outputs are corr_topk's bit for bit.  Operands, k and refusals as corr_topk; labels of
     another dtype raise TypeError, of another shape ValueError."""
     name = "corr_topk_labelled"
-    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0]:
-        raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
-    B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
-    _label_table(name, "q_label", q_label, B, Nq)
-    _label_table(name, "k_label", k_label, B, Nk)
+    B, Nq, Nk = _operand_shapes(name, qn, kn, width=False)
+    q_label = _int_table(name, "q_label", q_label, (B, Nq))
+    k_label = _int_table(name, "k_label", k_label, (B, Nk))
     _check_topk(name, k, Nk)
-    for t, what in ((qn, "qn"), (kn, "kn"), (q_label, "q_label"), (k_label, "k_label")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if PRECISION != "f16x3":
-        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
-    if planes is None:
-        planes = OperandPlanes()
+    _gate(name, ((qn, "qn"), (kn, "kn"), (q_label, "q_label"), (k_label, "k_label")), True)
     with torch.no_grad():
-        qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
-        return _corr_topk_labels_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
-                                        _narrow_labels(q_label), _narrow_labels(k_label), inv_temperature, k)
+        return _corr_topk_labels_planes(*_fetch_planes(name, qn, kn, planes, True)[2], q_label, k_label, inv_temperature, k)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1122,10 +1145,7 @@ def _corr_match_mutual_planes(qh, ql, kh, kl, inv_temperature: float):
     if k_stride == 0 and B != 1:
         raise ValueError("corr_match_mutual: one key set for all samples is out of scope (dense keys only)")
     dev = qh.device
-    rows = (torch.empty((B, Nq), device=dev, dtype=torch.int32), torch.empty((B, Nq), device=dev, dtype=torch.float32),
-            torch.empty((B, Nq), device=dev, dtype=torch.float32))
-    cols = (torch.empty((B, Nk), device=dev, dtype=torch.int32), torch.empty((B, Nk), device=dev, dtype=torch.float32),
-            torch.empty((B, Nk), device=dev, dtype=torch.float32))
+    rows, cols = _readout_outputs((B, Nq), None, dev), _readout_outputs((B, Nk), None, dev)
     nbytes = _lib.load().cocos_corr_match_mutual_workspace_bytes(B, Nq, Nk)
     ws = torch.empty((max(nbytes, 4) // 4,), device=dev, dtype=torch.float32)
     _call("corr_match_mutual", "cocos_corr_match_mutual_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
@@ -1146,19 +1166,10 @@ def corr_match_mutual(qn, kn, inv_temperature: float, planes: OperandPlanes | No
         if not torch.is_tensor(t):
             raise TypeError(f"{name}: {what}: expected a tensor, got {type(t).__name__}")
     if planes is None or not (planes.has(qn) or planes.has(kn)):
-        if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0] or qn.shape[1] != kn.shape[1]:
-            raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
-    for t, what in ((qn, "qn"), (kn, "kn")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if PRECISION != "f16x3":
-        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
-    if planes is None:
-        planes = OperandPlanes()
+        _operand_shapes(name, qn, kn, width=False)
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
     with torch.no_grad():
-        qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
-        return _corr_match_mutual_planes(*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE),
-                                         inv_temperature)
+        return _corr_match_mutual_planes(*_fetch_planes(name, qn, kn, planes, True)[2], inv_temperature)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1295,30 +1306,14 @@ def _lse_operands(name: str, qn, kn):
     for t, what in ((qn, "qn"), (kn, "kn")):
         if not torch.is_tensor(t):
             raise TypeError(f"{name}: {what}: expected a tensor, got {type(t).__name__}")
-    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[0] != kn.shape[0] or qn.shape[1] != kn.shape[1]:
-        raise ValueError(f"{name}: expected qn [B,256,Nq] and kn [B,256,Nk], got {tuple(qn.shape)} and {tuple(kn.shape)}")
-    if qn.shape[1] != FUSED_K:
-        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    return _operand_shapes(name, qn, kn)
 
 
 def _lse_device(name: str, qn, kn, extra=()):
-    for t, what in ((qn, "qn"), (kn, "kn")) + tuple(extra):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if PRECISION != "f16x3":
-        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    _gate(name, ((qn, "qn"), (kn, "kn")) + tuple(extra), True)
     B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
     if not corr_match_mutual_ok(B, Nq, Nk):
         raise ValueError(f"{name}: B={B} Nq={Nq} Nk={Nk}: the sweep takes Nq and Nk that are multiples of 4 (corr_match_mutual_ok)")
-
-
-def _lse_planes(name: str, qn, kn, planes):
-    if planes is None:
-        planes = OperandPlanes()
-    qn, kn = (t if planes.has(t) else _chk(t, f"{name}: {what}") for t, what in ((qn, "qn"), (kn, "kn")))
-    with torch.no_grad():
-        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
-    return qn, kn, pl
 
 
 def corr_lse(qn, kn, inv_temperature: float, planes: OperandPlanes | None = None):
@@ -1330,7 +1325,7 @@ def corr_lse(qn, kn, inv_temperature: float, planes: OperandPlanes | None = None
     name = "corr_lse"
     _lse_operands(name, qn, kn)
     _lse_device(name, qn, kn)
-    qn, kn, pl = _lse_planes(name, qn, kn, planes)
+    qn, kn, pl = _fetch_planes(name, qn, kn, planes, False)
     return _CorrLse.apply(qn, kn, float(inv_temperature), *pl)
 
 
@@ -1347,27 +1342,14 @@ def corr_pair_nll(qn, kn, target, inv_temperature: float, planes: OperandPlanes 
     framework scatter, no atomics).  `return_lse`: also return (row_lse [B,Nq], col_lse [B,Nk]) without gradient.  Operands and refusals
     as corr_lse."""
     name = "corr_pair_nll"
-    _lse_operands(name, qn, kn)
-    if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: target must be an int32 or int64 tensor, got {target.dtype if torch.is_tensor(target) else type(target).__name__}")
-    B, Nq, Nk = qn.shape[0], qn.shape[2], kn.shape[2]
-    if tuple(target.shape) != (B, Nq):
-        raise ValueError(f"{name}: target is {tuple(target.shape)}, expected {(B, Nq)}")
+    B, Nq, Nk = _lse_operands(name, qn, kn)
+    table = _int_table(name, "target", target, (B, Nq))
     if check_target and target.numel() and int(target.max()) >= Nk:
         raise ValueError(f"{name}: target holds {int(target.max())}, expected values below Nk={Nk} (negative: unsupervised)")
     _lse_device(name, qn, kn, ((target, "target"),))
-    qn, kn, pl = _lse_planes(name, qn, kn, planes)
-    with torch.no_grad():
-        target = target.clamp(min=-1).to(torch.int32).contiguous()
-    row_nll, col_nll, row_lse, col_lse = _CorrPairNll.apply(qn, kn, target, float(inv_temperature), *pl)
+    qn, kn, pl = _fetch_planes(name, qn, kn, planes, False)
+    row_nll, col_nll, row_lse, col_lse = _CorrPairNll.apply(qn, kn, table, float(inv_temperature), *pl)
     return (row_nll, col_nll, row_lse, col_lse) if return_lse else (row_nll, col_nll)
-
-
-def _grid2(name: str, what: str, grid):
-    if (not isinstance(grid, (tuple, list)) or len(grid) != 2
-            or any(isinstance(g, bool) or not isinstance(g, int) or g < 1 for g in grid)):
-        raise ValueError(f"{name}: {what}={grid!r}: expected a pair (h, w) of positive integers")
-    return int(grid[0]), int(grid[1])
 
 
 def match_round_trip(row_idx, col_idx, qgrid, kgrid):
@@ -1376,18 +1358,12 @@ def match_round_trip(row_idx, col_idx, qgrid, kgrid):
     q_back[b,i] = col_idx[b,row_idx[b,i]], q_dist[b,i] the Chebyshev distance in cells between q_back[b,i] and i on the qgrid, k_back /
     k_dist the same for the key side.  Any integer dtype (narrowed to int32 after a clamp); indices outside their range are clamped."""
     name = "match_round_trip"
-    for t, what in ((row_idx, "row_idx"), (col_idx, "col_idx")):
-        if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
-            raise TypeError(f"{name}: {what} must be an integer tensor")
-    (hq, wq), (hk, wk) = _grid2(name, "qgrid", qgrid), _grid2(name, "kgrid", kgrid)
+    row_idx, col_idx = _int_table(name, "row_idx", row_idx, any_int=True), _int_table(name, "col_idx", col_idx, any_int=True)
+    (hq, wq), (hk, wk) = _grid_pair(name, "qgrid", qgrid), _grid_pair(name, "kgrid", kgrid)
     if row_idx.dim() != 2 or col_idx.dim() != 2 or row_idx.shape[0] != col_idx.shape[0] or row_idx.shape[1] != hq * wq or col_idx.shape[1] != hk * wk:
         raise ValueError(f"{name}: row_idx {tuple(row_idx.shape)}, col_idx {tuple(col_idx.shape)} do not fit the grids {hq}x{wq} and {hk}x{wk}")
-    for t, what in ((row_idx, "row_idx"), (col_idx, "col_idx")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    _gate(name, ((row_idx, "row_idx"), (col_idx, "col_idx")), False)
     B = row_idx.shape[0]
-    narrow = lambda t: (t if t.dtype == torch.int32 else t.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
-    row_idx, col_idx = narrow(row_idx), narrow(col_idx)
     q_back, q_dist = torch.empty_like(row_idx), torch.empty_like(row_idx)
     k_back, k_dist = torch.empty_like(col_idx), torch.empty_like(col_idx)
     _call("match_round_trip", "cocos_match_round_trip", row_idx.data_ptr(), col_idx.data_ptr(), q_back.data_ptr(), q_dist.data_ptr(),
@@ -1401,9 +1377,7 @@ def row_topk_lse(f: torch.Tensor, k: int):
     row_argmax_lse's outputs bit for bit.  Any Nk >= k, 1 <= k <= MATCH_TOPK_MAX (ValueError).  Forward only."""
     f, lead, B, Nq, Nk = _readout_rows("row_topk_lse", f)
     k = _check_topk("row_topk_lse", k, Nk)
-    idx = torch.empty(lead + (k,), device=f.device, dtype=torch.int32)
-    val = torch.empty(lead + (k,), device=f.device, dtype=torch.float32)
-    lse = torch.empty(lead, device=f.device, dtype=torch.float32)
+    idx, val, lse = _readout_outputs(lead, k, f.device)
     _call("row_topk_lse", "cocos_row_topk_lse", f.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, Nq, Nk, k, _stream())
     return idx, val, lse
 
@@ -1414,8 +1388,7 @@ def gather_blend_patches(img: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, 
     img [Be,C,H,W] fp32 with H == h*down, W == w_grid*down and Be == B or 1; idx [B,k,h,w_grid] (or [B,k,h*w_grid]), any integer
     type (values outside [0, h*w_grid) are clamped into it); w fp32 of idx's shape; 1 <= k <= MATCH_TOPK_MAX."""
     img = _chk(img.detach(), "gather_blend_patches: img")
-    if not idx.is_cuda:
-        raise _lib.CocosHipError("gather_blend_patches: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    _gate("gather_blend_patches", ((idx, "idx"),), False)
     if idx.dtype.is_floating_point or idx.dtype == torch.bool:
         raise TypeError(f"gather_blend_patches: idx must be an integer tensor, got {idx.dtype}")
     w = _chk(w.detach(), "gather_blend_patches: w")
@@ -1527,18 +1500,11 @@ def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandP
     if K != FUSED_K:
         raise ValueError(f"sparse_softmax_warp: needs {FUSED_K} channels, got {K}")
     _check_topk("sparse_softmax_warp", int(idx.shape[2]), Nk)
-    for t, name in ((qn, "qn"), (kn, "kn"), (v, "v"), (idx, "idx")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"sparse_softmax_warp: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if PRECISION != "f16x3":
-        raise _lib.CocosHipError("sparse_softmax_warp: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
-    if planes is None:
-        planes = OperandPlanes()
-    qn, kn = (t if planes.has(t) else _chk(t, f"sparse_softmax_warp: {name}") for t, name in ((qn, "qn"), (kn, "kn")))
+    _gate("sparse_softmax_warp", ((qn, "qn"), (kn, "kn"), (v, "v"), (idx, "idx")), True)
+    qn, kn, pl = _fetch_planes("sparse_softmax_warp", qn, kn, planes, False)
     v = _chk(v, "sparse_softmax_warp: v")
     with torch.no_grad():
         idx = idx.clamp(0, Nk - 1).to(torch.int32).contiguous()
-        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
     out, w = _SparseSoftmaxWarp.apply(qn, kn, v, idx, float(inv_temperature), *pl)
     return (out, w) if return_weights else out
 
@@ -1553,39 +1519,16 @@ PATCHMATCH_MAX_RADII = _lib.CONSTANTS["COCOS_PATCHMATCH_MAX_RADII"]
 PATCHMATCH_DEFAULTS = dict(strides=(1, 2, 1, 1), radii=3, radius0=4, seed=0)
 
 
-def _is_int(x) -> bool:
-    return isinstance(x, int) and not isinstance(x, bool)
-
-
-def _patchmatch_grids(name: str, grids):
+def _patchmatch_operands(name: str, qn, kn, grids, k):
+    """the shape checks patchmatch_step / patchmatch_topk share -> (hq, wq, hk, wk); ValueError before the library is called"""
     try:
-        (hq, wq), (hk, wk) = grids
+        qgrid, kgrid = grids
     except (TypeError, ValueError):
         raise ValueError(f"{name}: grids={grids!r}: expected ((hq, wq), (hk, wk))") from None
-    if not all(_is_int(n) and n >= 1 for n in (hq, wq, hk, wk)):
-        raise ValueError(f"{name}: grids={grids!r}: expected positive integers ((hq, wq), (hk, wk))")
-    return hq, wq, hk, wk
-
-
-def _patchmatch_operands(name: str, qn, kn, grids, k, planes):
-    """the shape checks patchmatch_step / patchmatch_topk share -> (planes, hq, wq, hk, wk); ValueError before the library is called"""
-    hq, wq, hk, wk = _patchmatch_grids(name, grids)
-    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[:2] != kn.shape[:2] or qn.shape[2] != hq * wq or kn.shape[2] != hk * wk:
-        raise ValueError(f"{name}: qn{tuple(qn.shape)} kn{tuple(kn.shape)} do not fit a {hq}x{wq} query grid and a {hk}x{wk} key grid "
-                         "(expected qn [B,256,hq*wq], kn [B,256,hk*wk])")
-    if qn.shape[1] != FUSED_K:
-        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    (hq, wq), (hk, wk) = _grid_pair(name, "grids", qgrid), _grid_pair(name, "grids", kgrid)
+    _operand_shapes(name, qn, kn, hq * wq, hk * wk, f" on a {hq}x{wq} query grid and a {hk}x{wk} key grid")
     _check_topk(name, k, hk * wk)
-    return (OperandPlanes() if planes is None else planes), hq, wq, hk, wk
-
-
-def _patchmatch_device(name: str, qn, kn):
-    """after every ValueError: the tensors themselves"""
-    for t, what in ((qn, "qn"), (kn, "kn")):
-        if not t.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    if PRECISION != "f16x3":
-        raise _lib.CocosHipError(f"{name}: only the split-precision flavour exists (COCOS_PRECISION=f16x3)")
+    return hq, wq, hk, wk
 
 
 def _patchmatch_search(name: str, stride, radii, radius0, seed, iteration=0):
@@ -1611,23 +1554,10 @@ def _patchmatch_launch(planes4, idx, hq, wq, hk, wk, inv_t, k, stride, radii, ra
     return idx_out, val_out
 
 
-def _patchmatch_planes(name: str, qn, kn, planes):
-    qn, kn = (t if planes.has(t) else _chk(t.detach(), name) for t in (qn, kn))
-    out = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
-    if out[2].shape[0] != out[0].shape[0]:
-        raise ValueError(f"{name}: query and key batch differ")
-    return out
-
-
 def _patchmatch_table(name: str, idx, B, Nq, k):
-    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: the index table must be an int32 or int64 tensor")
-    if tuple(idx.shape) != (B, Nq, k):
-        raise ValueError(f"{name}: the index table is {tuple(idx.shape)}, expected {(B, Nq, k)}")
-    if not idx.is_cuda:
-        raise _lib.CocosHipError(f"{name}: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    # (int64 tables are narrowed after a clamp into int32's range, which keeps every value on its side of [0, Nk): the kernel clamps)
-    return (idx if idx.dtype == torch.int32 else idx.clamp(-1, 2 ** 31 - 1).to(torch.int32)).contiguous()
+    idx = _int_table(name, "the index table", idx, (B, Nq, k))
+    _gate(name, ((idx, "idx"),), False)
+    return idx
 
 
 def patchmatch_step(qn, kn, idx, grids, inv_t: float, k: int, stride: int, radii: int, radius0: int, seed: int, iteration: int,
@@ -1641,14 +1571,14 @@ def patchmatch_step(qn, kn, idx, grids, inv_t: float, k: int, stride: int, radii
     pairs.  The draw is a pure function of (seed, iteration, query, rank), so a call is bitwise reproducible.  A pool with fewer than k
     distinct keys repeats its last pair.  Bad k, grids, stride, radii: ValueError before the library is called."""
     name = "patchmatch_step"
-    planes, hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k, planes)
+    hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k)
     _patchmatch_search(name, stride, radii, radius0, seed, iteration)
-    _patchmatch_device(name, qn, kn)
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
     with torch.no_grad():
         if idx is not None:
             idx = _patchmatch_table(name, idx, qn.shape[0], hq * wq, k)
-        return _patchmatch_launch(_patchmatch_planes(name, qn, kn, planes), idx, hq, wq, hk, wk, inv_t, k, stride, radii, radius0, seed,
-                                  iteration)
+        return _patchmatch_launch(_fetch_planes(name, qn, kn, planes, True, same_batch=True)[2], idx, hq, wq, hk, wk, inv_t, k, stride,
+                                  radii, radius0, seed, iteration)
 
 
 def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=PATCHMATCH_DEFAULTS["strides"],
@@ -1659,7 +1589,7 @@ def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=
     starting at half the longer side of the key grid, or a pair (radii, radius0).  Operands, grids and errors as patchmatch_step; an
     empty `strides` is a ValueError (a selection needs scores)."""
     name = "patchmatch_topk"
-    planes, hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k, planes)
+    hq, wq, hk, wk = _patchmatch_operands(name, qn, kn, grids, k)
     if isinstance(init, str) and init != "random" or not (isinstance(init, str) or torch.is_tensor(init)):
         raise ValueError(f"{name}: init={init!r}: expected 'random' or an integer tensor [B,Nq,k]")
     try:
@@ -1671,10 +1601,10 @@ def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=
     n_radii, radius0 = radii if isinstance(radii, (tuple, list)) and len(radii) == 2 else (radii, max(hk, wk) // 2)
     for t, stride in enumerate(strides):
         _patchmatch_search(name, stride, n_radii, radius0, seed, t)
-    _patchmatch_device(name, qn, kn)
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
     with torch.no_grad():
         idx = None if isinstance(init, str) else _patchmatch_table(name, init, qn.shape[0], hq * wq, k)
-        planes4 = _patchmatch_planes(name, qn, kn, planes)
+        planes4 = _fetch_planes(name, qn, kn, planes, True, same_batch=True)[2]
         val = None
         for t, stride in enumerate(strides):
             idx, val = _patchmatch_launch(planes4, idx, hq, wq, hk, wk, inv_t, k, stride, n_radii, radius0, seed, t)
@@ -1688,41 +1618,34 @@ def patchmatch_topk(qn, kn, inv_t: float, k: int, grids, init="random", strides=
 MATCH_REFINE_MAX_RADIUS = _lib.CONSTANTS["COCOS_MATCH_REFINE_MAX_RADIUS"]
 
 
-def _refine_grid(name: str, what: str, grid):
-    try:
-        h, w = grid
-    except (TypeError, ValueError):
-        raise ValueError(f"{name}: {what}={grid!r}: expected (rows, columns)") from None
-    if not (_is_int(h) and _is_int(w) and h >= 1 and w >= 1):
-        raise ValueError(f"{name}: {what}={grid!r}: expected two positive integers")
-    return h, w
-
-
 def _refine_table(name: str, idx, B, Nq):
-    """the centre table of K44 -> int32 [B,Nq] contiguous (TypeError / ValueError first, then the device)"""
-    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: idx must be an int32 or int64 tensor")
-    if idx.shape[0] != B or idx.numel() != B * Nq:
+    """the centre table of K44, [B,Nq] or [B,h,w] -> int32 [B,Nq] contiguous (TypeError / ValueError first, then the device)"""
+    idx = _int_table(name, "idx", idx)
+    if idx.dim() < 1 or idx.shape[0] != B or idx.numel() != B * Nq:
         raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
-    if not idx.is_cuda:
-        raise _lib.CocosHipError(f"{name}: idx: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    # (int64 tables are narrowed after a clamp into int32's range, which keeps every value on its side of the grid: the kernels clamp)
-    return (idx if idx.dtype == torch.int32 else idx.clamp(-1, 2 ** 31 - 1).to(torch.int32)).reshape(B, Nq).contiguous()
+    _gate(name, ((idx, "idx"),), False)
+    return idx.reshape(B, Nq)
 
 
 def _refine_operands(name: str, qn, kn, kgrid, inv_t, radius):
     """the checks of the window soft-argmax's arguments (K44, K46) -> (hk, wk); ValueError before the library is called"""
-    hk, wk = _refine_grid(name, "kgrid", kgrid)
+    hk, wk = _grid_pair(name, "kgrid", kgrid)
     if not _is_int(radius) or not 1 <= radius <= MATCH_REFINE_MAX_RADIUS:
         raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{MATCH_REFINE_MAX_RADIUS}")
     if not inv_t > 0:
         raise ValueError(f"{name}: inv_t={inv_t!r}: expected a positive number")
-    if qn.dim() != 3 or kn.dim() != 3 or qn.shape[:2] != kn.shape[:2] or kn.shape[2] != hk * wk:
-        raise ValueError(f"{name}: qn{tuple(qn.shape)} kn{tuple(kn.shape)} do not fit a {hk}x{wk} key grid "
-                         "(expected qn [B,256,Nq], kn [B,256,hk*wk])")
-    if qn.shape[1] != FUSED_K:
-        raise ValueError(f"{name}: needs {FUSED_K} channels, got {qn.shape[1]}")
+    _operand_shapes(name, qn, kn, None, hk * wk, f" on a {hk}x{wk} key grid")
     return hk, wk
+
+
+def _match_refine_planes(qh, ql, kh, kl, idx, hk: int, wk: int, radius: int, inv_t: float):
+    """K44 on operand planes and an int32 contiguous centre table [B,Nq] -> (off [B,Nq,2], lse_win [B,Nq])"""
+    B, Nq, K = qh.shape
+    off = torch.empty((B, Nq, 2), device=qh.device, dtype=torch.float32)
+    lse_win = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
+    _call("match_refine", "cocos_match_refine_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
+          off.data_ptr(), lse_win.data_ptr(), B, K, Nq, hk * wk, hk, wk, radius, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+    return off, lse_win
 
 
 def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):
@@ -1736,24 +1659,16 @@ def match_refine(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandP
     name = "match_refine"
     hk, wk = _refine_operands(name, qn, kn, kgrid, inv_t, radius)
     B, _, Nq = qn.shape
-    if planes is None:
-        planes = OperandPlanes()
-    _patchmatch_device(name, qn, kn)
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
     with torch.no_grad():
         idx = _refine_table(name, idx, B, Nq)
-        qh, ql, kh, kl = _patchmatch_planes(name, qn, kn, planes)
-        off = torch.empty((B, Nq, 2), device=qh.device, dtype=torch.float32)
-        lse_win = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
-        _call("match_refine", "cocos_match_refine_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
-              off.data_ptr(), lse_win.data_ptr(), B, qh.shape[2], Nq, hk * wk, hk, wk, radius, float(inv_t), SPLIT_OPERAND_SCALE,
-              _stream())
-    return off, lse_win
+        return _match_refine_planes(*_fetch_planes(name, qn, kn, planes, True, same_batch=True)[2], idx, hk, wk, radius, inv_t)
 
 
 def _subcell_shapes(name: str, img, off, grid, kgrid, down):
     """the checks of the sub-cell gather's arguments (K44, K46) -> (fh, fw, hk, wk, B); TypeError / ValueError before the library is called"""
-    fh, fw = _refine_grid(name, "grid", grid)
-    hk, wk = _refine_grid(name, "kgrid", kgrid)
+    fh, fw = _grid_pair(name, "grid", grid)
+    hk, wk = _grid_pair(name, "kgrid", kgrid)
     if not _is_int(down) or down < 1:
         raise ValueError(f"{name}: down={down!r}: expected an integer >= 1")
     if not torch.is_tensor(off) or off.dtype != torch.float32:
@@ -1795,11 +1710,7 @@ class _SoftMatchOffset(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qn, kn, idx, inv_t: float, radius: int, hk: int, wk: int, qh, ql, kh, kl):
-        B, Nq, K = qh.shape
-        off = torch.empty((B, Nq, 2), device=qh.device, dtype=torch.float32)
-        lse_win = torch.empty((B, Nq), device=qh.device, dtype=torch.float32)
-        _call("match_refine", "cocos_match_refine_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), idx.data_ptr(),
-              off.data_ptr(), lse_win.data_ptr(), B, K, Nq, hk * wk, hk, wk, radius, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+        off, lse_win = _match_refine_planes(qh, ql, kh, kl, idx, hk, wk, radius, inv_t)
         ctx.save_for_backward(qh, ql, kh, kl, idx)
         ctx.cfg = (float(inv_t), radius, hk, wk)
         ctx.mark_non_differentiable(lse_win)
@@ -1842,15 +1753,10 @@ def soft_match_offset(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: Ope
     name = "soft_match_offset"
     hk, wk = _refine_operands(name, qn, kn, kgrid, inv_t, radius)
     B, _, Nq = qn.shape
-    if planes is None:
-        planes = OperandPlanes()
-    _patchmatch_device(name, qn, kn)
-    qn, kn = (t if planes.has(t) else _chk(t, f"{name}: {what}") for t, what in ((qn, "qn"), (kn, "kn")))
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
     with torch.no_grad():
         idx = _refine_table(name, idx, B, Nq).clamp(0, hk * wk - 1)      # the kernels clamp as well: the table the key side inverts
-        pl = (*planes.get(qn, True, SPLIT_OPERAND_SCALE), *planes.get(kn, True, SPLIT_OPERAND_SCALE))
-        if pl[2].shape[0] != pl[0].shape[0]:
-            raise ValueError(f"{name}: query and key batch differ")
+    qn, kn, pl = _fetch_planes(name, qn, kn, planes, False, same_batch=True)
     return _SoftMatchOffset.apply(qn, kn, idx, float(inv_t), radius, hk, wk, *pl)
 
 
