@@ -75,6 +75,7 @@ HIP_SOURCES = [
     "match_refine_bwd_f16x3.hip",
     "corr_match_mutual_f16x3.hip",
     "corr_lse_bwd_f16x3.hip",
+    "corr_topk_bias_f16x3.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

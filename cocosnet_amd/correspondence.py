@@ -25,8 +25,8 @@ from torch.nn import init
 
 from . import inference, ops
 from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search,
-                       _upsample, correspondence_flow, correspondence_hot_path, correspondence_match, correspondence_mutual,
-                       correspondence_nll, correspondence_sparse)
+                       _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_hot_path, correspondence_match,
+                       correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_transport)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -399,8 +399,39 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_valid"] = _upsample(m.rows_mutual.to(torch.float32).unsqueeze(1).contiguous(), self.opt.down, False)
         return out
 
+    def transport_match(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, iters=5, tau=1.0, topk=1, hard_warp=False):
+        """match() on the entropic transport plan instead of the row softmax (K50, hot_path.correspondence_transport; UNITE's
+        replacement of this block's softmax): `iters` log-domain Sinkhorn iterations under uniform marginals (tau = 1 balanced, 0 < tau
+        < 1 KL-relaxed) give the potentials f, g, and every content position reads the row of z_ij = s_ij + g_j — an exemplar
+        position that many content positions want is priced out, so one exemplar cell no longer serves hundreds of queries.  One
+        projection of the network, under torch.no_grad(); nothing HWxHW.  Returns match()'s keys computed on z: match_index [B,h,w]
+        int64 ([B,k,h,w] with topk = k > 1), match_xy, match_prob = exp(z - match_lse), match_lse = log sum_j exp z_ij; with
+        `hard_warp` warp_hard and, for topk > 1, warp_topk (the blend weighted by the softmax over the k values of z); and
+        potential_q [B,h,w], potential_k [B,gh,gw], match_mass [B,h,w] (1 where the row marginal is met), key_mass [B,gh,gw] (the
+        transported mass each exemplar position receives over its fair share; 1 under tau = 1).  Scope: sparse_warp's (match_kernel 1
+        with PONO_C on the plain flag set, COCOS_PRECISION=f16x3, no prepared exemplar); everything else raises a ValueError naming
+        transport before the network runs.  match(), mutual_match(), forward() and sparse_warp() are unaffected."""
+        k = _topk_arg("transport_match", topk)
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _transport_scope("transport_match", cfg, {"iters": iters, "tau": tau}, False, channels=self.inter_channels)
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("transport_match: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        with torch.no_grad():
+            theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
+            res = correspondence_transport(theta_raw, phi_raw, cfg, temperature, iters=iters, tau=tau, topk=k)
+            m = res.pop("readout")
+            out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse, **res}
+            if hard_warp and k == 1:
+                fh, fw = m.index.shape[1:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+            elif hard_warp:
+                fh, fw = m.index.shape[2:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)
+                out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, torch.softmax(m.logit, dim=1), fh, fw, self.opt.down)
+        return out
+
     def sparse_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, search="dense", search_opts=None,
-                    restrict=None):
+                    restrict=None, transport=None):
         """The trainable k-sparse warp (hot_path.correspondence_sparse): per content position the `topk` best exemplar positions are
         selected without gradient, and a softmax over those k logits alone blends the pooled exemplar (and, under
         --warp_mask_losstype direct, the exemplar's labels) — attention over k keys instead of all HW, with gradients to the whole
@@ -410,8 +441,12 @@ class NoVGGCorrespondence(NetworkBase):
         `search` / `search_opts`: the candidate selector, "dense" (default: the scan over all keys) or "patchmatch" (K43) with its
         schedule, as hot_path.correspondence_sparse takes them.  `restrict` (K47; None changes nothing): "label" or a pair of label
         tensors, as match() takes them — the candidates come from the exemplar positions of the content position's label (dense
-        selector only), the result gains match_restricted [B,h,w], and the gradients are the same: the indices are data."""
+        selector only), the result gains match_restricted [B,h,w], and the gradients are the same: the indices are data.
+        `transport` (K50; None changes nothing): dict(iters=, tau=) — the candidates are the top-k of the transport plan's rows and the
+        blend is the biased softmax over them, with the Sinkhorn potentials detached (gradients reach the network through the k pair
+        logits and the values only); the result gains potential_k [B,gh,gw] and match_mass [B,h,w].  Dense selector, no restrict."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _transport_scope("sparse_warp", cfg, transport, False, search, restrict, self.inter_channels)
         _restrict_scope("sparse_warp", cfg, restrict, False, 0, search, self.inter_channels)
         _sparse_scope(cfg, topk)                  # out-of-scope flags are refused before the network runs
         _sparse_search(search, search_opts)
@@ -420,6 +455,8 @@ class NoVGGCorrespondence(NetworkBase):
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         kw = {} if restrict is None else {"restrict": restrict}
+        if transport is not None:
+            kw["transport"] = transport
         coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, search=search,
                                               search_opts=search_opts, **kw))
         return coor_out

@@ -147,13 +147,19 @@ __device__ __forceinline__ void col_reduce_tile(const f32x16& sa, int i_lane, fl
 // tiles, double-buffered by stage, and after the stage's barrier wave 0 merges them in ascending wave (= query) order and writes one
 // partial per (query block, key) to col_ws [3][B * nqb][Nk] (m, l, index).  The barrier of the NEXT stage orders wave 0's reads before
 // the writes of the stage after it.  Without MUTUAL col_ws is not read (null) and none of this is compiled.
-template <int K, bool LABELS, bool MUTUAL = false>
+// BIAS (K50): k_bias fp32 [B,Nk] (one [Nk] row when k_bstride is 0) is added to every logit of its key, z_ij = s_ij + bias_j, after the
+// past-Nk mask and before the tile maximum, the list and the sum — LABELS is the special case 0 / -inf.  The bias meets the RAW
+// accumulator: sa <- fma(bias, bias_raw, sa) with bias_raw = operand_scale^2 / inv_temperature, one rounding, so everything after it
+// (the list, the sums, the merges, val = raw * scale_nat) is the unbiased kernel's code; a bias of zeros leaves every register as it
+// was.  -inf excludes the key (fma(-inf, positive, finite) = -inf; a masked -inf plus the zero a read past Nk returns stays -inf).
+// Without BIAS k_bias is not read (null).
+template <int K, bool LABELS, bool MUTUAL = false, bool BIAS = false>
 __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
     const _Float16* __restrict__ qh, const _Float16* __restrict__ ql, const _Float16* __restrict__ kh,
     const _Float16* __restrict__ kl, const int* __restrict__ q_label, const int* __restrict__ k_label, int* __restrict__ idx_out, float* __restrict__ val_out, float* __restrict__ lse_out,
     int B, int Nq, int Nk, int k_out /* columns written: 1 .. K */, float scale_log2 /* inv_temperature * log2(e) / operand_scale^2 */,
     float scale_nat /* inv_temperature / operand_scale^2 */, size_t k_bstride /* halfs: Nk * 256, or 0 = one key set for all */,
-    float* __restrict__ col_ws = nullptr) {
+    float* __restrict__ col_ws = nullptr, const float* __restrict__ k_bias = nullptr, float bias_raw = 0.f /* operand_scale^2 / inv_temperature */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     _Float16* const kt = reinterpret_cast<_Float16*>(smem_raw);   // [2 stages][hi|lo][64 keys][KROW]
 
@@ -214,6 +220,10 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
         if (i_lane < Nq) q_lab = q_label[(size_t)b * Nq + i_lane];
         lab_rs = make_rsrc(k_label + (k_bstride ? (size_t)b * Nk : (size_t)0), (size_t)Nk * 4);
     }
+    // ---- bias: the keys' through a descriptor over this sample's Nk values, in the same four runs of four as the labels (a run past
+    //      Nk reads zeros, and those keys are -inf already)
+    __amdgpu_buffer_rsrc_t bias_rs;
+    if constexpr (BIAS) bias_rs = make_rsrc(k_bias + (k_bstride ? (size_t)b * Nk : (size_t)0), (size_t)Nk * 4);
 
     const int nstages = (Nk + CT_STAGE - 1) / CT_STAGE;
 #pragma unroll
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
         f32x16 sa;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sa[r] = 0.f;
-        u32x4 klab[4];           // labels of keys j0 + 8g + 4h .. + 3: rows 4g .. 4g + 3 of the accumulator
+        u32x4 klab[4];           // labels (BIAS: the biases' bits) of keys j0 + 8g + 4h .. + 3: rows 4g .. 4g + 3 of the accumulator
         // ---- S^T = K_tile . Q : 16 k-steps x 3 terms into one accumulator, in the forward kernel's order; the A fragments come
         //      from LDS RA - 1 steps ahead and the eight staged pieces of the next stage ride in the gaps, one every other step
 #pragma unroll
@@ -287,6 +297,10 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
                 if (s >= NS - 4)
                     klab[s - (NS - 4)] = __builtin_amdgcn_raw_buffer_load_b128(lab_rs, (j0 + 8 * (s - (NS - 4)) + 4 * h) * 4, 0, 0);
             }
+            if constexpr (BIAS) {      // the same slot of the schedule, the same registers
+                if (s >= NS - 4)
+                    klab[s - (NS - 4)] = __builtin_amdgcn_raw_buffer_load_b128(bias_rs, (j0 + 8 * (s - (NS - 4)) + 4 * h) * 4, 0, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- this lane's 16 keys: j0 + acc_row_base(r) + 4h, ascending in r.  Keys past Nk (zero rows: logit 0, which would beat
@@ -300,6 +314,14 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if (q_lab >= 0 && (int)klab[r >> 2][r & 3] != q_lab) sa[r] = -INFINITY;
+        }
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                // (the element is copied out first: a bit_cast applied to the vector-element expression itself reads element 0)
+                const unsigned bits = klab[r >> 2][r & 3];
+                sa[r] = __builtin_fmaf(__builtin_bit_cast(float, bits), bias_raw, sa[r]);
+            }
         }
         float tmax = sa[0];
 #pragma unroll
@@ -390,20 +412,20 @@ __global__ __launch_bounds__(CT_THREADS) void corr_topk_f16x3_kernel(
     }
 }
 
-template <int K, bool LABELS = false, bool MUTUAL = false>
+template <int K, bool LABELS = false, bool MUTUAL = false, bool BIAS = false>
 static int launch_corr_topk(const void* qh, const void* ql, const void* kh, const void* kl, int* idx_out, float* val_out,
                             float* lse_out, int B, int Nq, int Nk, int k, float inv_temperature, float operand_scale,
                             long long k_batch_stride, cocos_stream_t stream, const int* q_label = nullptr,
-                            const int* k_label = nullptr, float* col_ws = nullptr) {
+                            const int* k_label = nullptr, float* col_ws = nullptr, const float* k_bias = nullptr) {
     const int nqb = (Nq + CT_BQ - 1) / CT_BQ;
     const float s2 = operand_scale * operand_scale;
-    auto kern = corr_topk_f16x3_kernel<K, LABELS, MUTUAL>;
+    auto kern = corr_topk_f16x3_kernel<K, LABELS, MUTUAL, BIAS>;
     constexpr size_t smem = MUTUAL ? CT_SMEM_MUTUAL : CT_SMEM;
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(kern, dim3(B * nqb), dim3(CT_THREADS), smem, as_stream(stream), static_cast<const _Float16*>(qh),
                        static_cast<const _Float16*>(ql), static_cast<const _Float16*>(kh), static_cast<const _Float16*>(kl), q_label,
                        k_label, idx_out, val_out, lse_out, B, Nq, Nk, k, inv_temperature * kLog2e / s2, inv_temperature / s2, (size_t)k_batch_stride,
-                       col_ws);
+                       col_ws, k_bias, s2 / inv_temperature);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }

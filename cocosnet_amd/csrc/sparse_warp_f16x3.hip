@@ -23,11 +23,17 @@ constexpr int SW_WAVES = 4;              // rows (queries or keys) per workgroup
 constexpr int SW_THREADS = SW_WAVES * kWave;
 constexpr int SW_MAXK = COCOS_MATCH_TOPK_MAX;
 
+// BIAS (K50, cocos_sparse_softmax_warp_bias_fwd_f16x3): s_r += k_bias[b, j_r] before the softmax over r — the row-conditional
+// transport plan softmax_j(s_ij + g_j) restricted to the k candidates.  k_bias [B,Nk] fp32, or one [Nk] row when bias_bstride is 0;
+// finite or -inf.  A row whose k candidates all carry -inf has no largest logit to refer to: its w is the uniform 1 / k.  The bias is a
+// constant of the backward, which consumes the saved w.  Without BIAS the pointer is not read and the code is the K42 forward's.
+template <bool BIAS>
 __global__ __launch_bounds__(SW_THREADS) void sparse_warp_fwd_kernel(const _Float16* __restrict__ qh, const _Float16* __restrict__ ql,
                                                                      const _Float16* __restrict__ kh, const _Float16* __restrict__ kl,
                                                                      const float* __restrict__ vt, const int* __restrict__ idx,
                                                                      float* __restrict__ out_t, float* __restrict__ w_out,
-                                                                     long long rows, int Nq, int Nk, int Cv, int k, float logit_scale) {
+                                                                     long long rows, int Nq, int Nk, int Cv, int k, float logit_scale,
+                                                                     const float* __restrict__ k_bias = nullptr, long long bias_bstride = 0) {
     const int lane = threadIdx.x & (kWave - 1);
     const long long row = (long long)blockIdx.x * SW_WAVES + (threadIdx.x >> 6);      // b * Nq + i
     if (row >= rows) return;                                                          // (whole waves; the kernel has no barrier)
@@ -44,7 +50,15 @@ __global__ __launch_bounds__(SW_THREADS) void sparse_warp_fwd_kernel(const _Floa
             key[r] = kbase + clamp_key(idx[row * k + r], Nk);
             const f32x4 kv = load_row4(kh, kl, key[r], lane);
             s[r] = wave_sum(lane_dot4(q, kv)) * logit_scale;
+            if constexpr (BIAS) s[r] += k_bias[(row / Nq) * bias_bstride + (key[r] - kbase)];
             m = fmaxf(m, s[r]);
+        }
+    }
+    if constexpr (BIAS) {
+        if (m == -INFINITY) {      // every candidate excluded: uniform weights
+            m = 0.f;
+#pragma unroll
+            for (int r = 0; r < SW_MAXK; ++r) s[r] = 0.f;
         }
     }
     float sum = 0.f;
@@ -196,9 +210,31 @@ extern "C" int cocos_sparse_softmax_warp_fwd_f16x3(const void* qh, const void* q
     for (const void* p : {qh, ql, kh, kl})
         COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: q/k planes must be 16-byte aligned", name);
     const long long rows = (long long)B * Nq;
-    hipLaunchKernelGGL(sparse_warp_fwd_kernel, dim3(sparse_warp_blocks(rows)), dim3(SW_THREADS), 0, as_stream(stream),
+    hipLaunchKernelGGL(sparse_warp_fwd_kernel<false>, dim3(sparse_warp_blocks(rows)), dim3(SW_THREADS), 0, as_stream(stream),
                        (const _Float16*)qh, (const _Float16*)ql, (const _Float16*)kh, (const _Float16*)kl, v_t, idx, out_t, w, rows, Nq, Nk,
-                       Cv, k, inv_temperature / (operand_scale * operand_scale));
+                       Cv, k, inv_temperature / (operand_scale * operand_scale), (const float*)nullptr, 0ll);
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
+
+// K50: the same forward with s_r += k_bias[b, j_r]; bias_batch_stride (floats): Nk, or 0 = one [Nk] row for every sample
+extern "C" int cocos_sparse_softmax_warp_bias_fwd_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* v_t,
+                                                        const int* idx, const float* k_bias, float* out_t, float* w, int B, int K, int Nq,
+                                                        int Nk, int Cv, int k, float inv_temperature, float operand_scale,
+                                                        long long bias_batch_stride, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "sparse_softmax_warp_bias_fwd_f16x3";
+    COCOS_REQUIRE(qh && ql && kh && kl && v_t && idx && k_bias && out_t && w, COCOS_ERR_INVALID, "%s: null pointer", name);
+    if (int rc = sparse_warp_check(name, B, K, Nq, Nk, Cv, k, inv_temperature, operand_scale)) return rc;
+    COCOS_REQUIRE(bias_batch_stride == 0 || bias_batch_stride == (long long)Nk, COCOS_ERR_INVALID,
+                  "%s: bias_batch_stride %lld: expected 0 (one bias row for all samples) or the dense %d", name, bias_batch_stride, Nk);
+    for (const void* p : {qh, ql, kh, kl})
+        COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: q/k planes must be 16-byte aligned", name);
+    COCOS_REQUIRE((reinterpret_cast<uintptr_t>(k_bias) & 3) == 0, COCOS_ERR_INVALID, "%s: the bias must be 4-byte aligned", name);
+    const long long rows = (long long)B * Nq;
+    hipLaunchKernelGGL(sparse_warp_fwd_kernel<true>, dim3(sparse_warp_blocks(rows)), dim3(SW_THREADS), 0, as_stream(stream),
+                       (const _Float16*)qh, (const _Float16*)ql, (const _Float16*)kh, (const _Float16*)kl, v_t, idx, out_t, w, rows, Nq, Nk,
+                       Cv, k, inv_temperature / (operand_scale * operand_scale), k_bias, bias_batch_stride);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }

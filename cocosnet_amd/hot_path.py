@@ -16,6 +16,7 @@ the channel groups that share a softmax concatenated into a single V:
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import torch
@@ -630,7 +631,8 @@ class TopkMatchReadout:
 _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused match_kernel 1 route only",
           "restrict": ": restrict runs on the fused match_kernel 1 route only",
           "sparse": " (the sparse warp runs on the fused match_kernel 1 route)",
-          "nll": " (the loss runs on the fused match_kernel 1 route)"}
+          "nll": " (the loss runs on the fused match_kernel 1 route)",
+          "transport": " (transport runs on the fused match_kernel 1 route)"}
 
 
 def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool):
@@ -1080,7 +1082,7 @@ def _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k):
 
 
 def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                          exemplar=None, search="dense", search_opts=None, restrict=None):
+                          exemplar=None, search="dense", search_opts=None, restrict=None, transport=None):
     """The k-sparse, trainable variant of correspondence_hot_path's row pass (CoCosNet-v2 style): per content position the `topk` best
     exemplar positions are SELECTED without gradient by the match readout (K23 / K1 planes -> K39a, as correspondence_match), then a
     softmax over those k logits alone blends their values — ops.sparse_softmax_warp (K42), with gradients to theta_raw and phi_raw
@@ -1105,7 +1107,17 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     as correspondence_match takes them — the k candidates are selected among the exemplar positions of the content position's label
     (ops.corr_topk_labelled; positions whose label has fewer than topk exemplar positions fall back to the scan over all), and the
     warp and its gradients are the same K42 on those indices.  The result gains match_restricted [B,h,w] bool.  Scope: the dense
-    selector of the scope above; everything else raises a ValueError that names restrict."""
+    selector of the scope above; everything else raises a ValueError that names restrict.
+
+    `transport` (K50; None, the default, is the code path above, untouched): dict(iters=, tau=) — the softmax is replaced by entropic
+    optimal transport over the same correlation.  ops.corr_sinkhorn runs `iters` log-domain Sinkhorn iterations (tau = 1: balanced,
+    tau < 1: KL-relaxed) on the operand planes, the k candidates are the top-k of z_ij = s_ij + g_j (ops.corr_topk_biased) and the blend
+    is the biased softmax over them (ops.sparse_softmax_warp(k_bias=g)): the row-conditional transport plan on its k largest entries.
+    The potentials are DETACHED: gradients reach theta, phi and the values through the k pair logits and the blend, with g a constant —
+    nothing differentiates through the iterations.  The result gains potential_k [B,gh,gw] (g) and match_mass [B,h,w] (1 where the row
+    marginal is met).  Scope: the dense selector of the scope above, restrict = None; everything else raises a ValueError that names
+    transport."""
+    _transport_scope("correspondence_sparse", cfg, transport, exemplar is not None, search, restrict, theta_raw.shape[1])
     _restrict_scope("correspondence_sparse", cfg, restrict, exemplar is not None, 0, search, theta_raw.shape[1])
     k = _sparse_scope(cfg, topk)
     pm = _sparse_search(search, search_opts)
@@ -1127,7 +1139,8 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
         raise ops._lib.CocosHipError("correspondence_sparse: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     if not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(k):
         raise ValueError(f"correspondence_sparse: the fused top-k readout does not take B={B}, {N} x {Nk} positions, k={k} "
-                         "(positions must be multiples of 4)" + ("; restrict runs on no other route" if restrict is not None else ""))
+                         "(positions must be multiples of 4)" + ("; restrict runs on no other route" if restrict is not None else "")
+                         + ("; transport runs on no other route" if transport is not None else ""))
     # K1 with autograd (_operand_planes without the K23 pair: lazy operands are projected): the position-major operand planes are
     # written once and serve the selection and the warp alike (the same planes, so the same candidates as correspondence_match, bit
     # for bit); qn / kn are the handles of those planes, and each keeps its channel-major planes for its own backward when it is
@@ -1137,10 +1150,13 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     inv_t = 1.0 / temperature
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
     with torch.no_grad():
-        restricted = None
+        restricted = g = None
         if labels is not None:      # K47: the same selection among the exemplar positions of the position's label
             q_eff, k_eff, restricted = restrict_fallback(*labels, k)
             idx, _, _ = ops.corr_topk_labelled(qn, kn, q_eff, k_eff, inv_t, k, planes)
+        elif transport is not None:      # K50: the potentials (no gradient), then the k largest entries of every row of the plan
+            f, g, _ = ops.corr_sinkhorn(qn, kn, inv_t, transport["iters"], transport["tau"], planes)
+            idx, _, row_lse = ops.corr_topk_biased(qn, kn, g, inv_t, k, planes)
         elif pm is None:
             idx, _, _ = ops.corr_topk(qn, kn, inv_t, k, planes)                # selection: no gradient
         else:
@@ -1148,7 +1164,10 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
                                          _patchmatch_coarse_init(_raw(theta_raw), _raw(phi_raw), inv_t, k), pm["strides"],
                                          (pm["radii"], pm["radius0"]), pm["seed"], planes)
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
-    o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True)
+    if g is None:
+        o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True)
+    else:
+        o, w = ops.sparse_softmax_warp(qn, kn, v, idx, inv_t, planes, return_weights=True, k_bias=g)
     n_ref = ref_img.shape[1]
     y, o_mask = _split_channels(o, n_ref) if direct_mask else (o, None)
     out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
@@ -1158,7 +1177,79 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     out["match_weight"] = _rank_first(w, (B, fh, fw), k)
     if restricted is not None:
         out["match_restricted"] = restricted.reshape(B, fh, fw)
+    if g is not None:
+        out["potential_k"] = g.reshape(B, gh, gw)
+        out["match_mass"] = torch.exp(f + row_lse + math.log(N)).reshape(B, fh, fw)
     return out
+
+
+# ---- K50: transport match — entropic optimal transport over the correlation instead of the row softmax ---------------------------
+def _transport_scope(name: str, cfg: HotPathConfig, transport, has_exemplar: bool, search="dense", restrict=None, channels=None):
+    """ValueError for a `transport` that is neither None nor a dict with exactly the keys iters (integer in 1..ops.SINKHORN_MAX_ITERS)
+    and tau (0 < tau <= 1), and — with one — for everything outside its scope (K50: sparse_warp's route, no prepared exemplar, the
+    dense selector, no restriction); checked before any tensor is looked at.  Every message names `transport`."""
+    if transport is None:
+        return
+    if not isinstance(transport, dict) or set(transport) != {"iters", "tau"}:
+        what = sorted(transport) if isinstance(transport, dict) else type(transport).__name__
+        raise ValueError(f"{name}: transport={what}: expected None or dict(iters=, tau=)")
+    ops._sinkhorn_args(f"{name}: transport", transport["iters"], transport["tau"])
+    _route_scope(f"{name}: transport", cfg, "transport", plain_flags=True, match_fused=False)
+    if has_exemplar:
+        raise ValueError(f"{name}: transport with a prepared exemplar is out of scope (not built)")
+    if search != "dense":
+        raise ValueError(f"{name}: transport with search={search!r} is out of scope: the potentials live in the dense scan")
+    if restrict is not None:
+        raise ValueError(f"{name}: transport with restrict is out of scope (not built)")
+    _route_channels(f"{name}: transport", "transport", channels)
+
+
+def correspondence_transport(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, iters=5, tau=1.0, topk=1):
+    """The match readout of the entropic transport plan over the correlation (K50; UNITE's replacement of CoCosNet's softmax): where
+    correspondence_match reads the rows of softmax_j(s_ij), this reads the rows of softmax_j(s_ij + g_j) with g the exemplar-side
+    potential of `iters` log-domain Sinkhorn iterations under uniform marginals (ops.corr_sinkhorn; tau = 1 balanced, tau < 1
+    KL-relaxed) — an exemplar position that many content positions want pays for it in g.  Forward only, nothing HWxHW.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1 (planes from _operand_planes, correspondence_match's producer).
+    Returns a dict: `readout`, a MatchReadout (topk = 1) or TopkMatchReadout over z = s + g — index, max_logit / logit = z,
+    prob = exp(z - lse), lse = log sum_j exp z_ij; potential_q [B,h,w] (f) and potential_k [B,gh,gw] (g); match_mass [B,h,w] =
+    exp(f_i + lse_i) / mu_i, 1 where the row marginal is met; key_mass [B,gh,gw] = exp(g_j + log sum_i exp(s_ij + f_i)) / nu_j, the
+    same for the columns (one more column launch): the transported mass each exemplar position receives, 1 under tau = 1.
+    Launches: the planes' producer, 2 iters + 1 for the potentials, one top-k over z (topk > 1; with topk = 1 the last row launch
+    serves), one column launch.
+
+    Scope: correspondence_sparse's (match_kernel 1, PONO_C, the plain flag set, COCOS_PRECISION=f16x3, 256 channels, positions a
+    multiple of 4, no prepared exemplar); everything else raises a ValueError that names transport.  CPU tensors raise CocosHipError."""
+    name = "correspondence_transport"
+    k = _topk_arg(name, topk)
+    _transport_scope(name, cfg, {"iters": iters, "tau": tau}, False, channels=theta_raw.shape[1])
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    _fused_width(name, theta_raw, phi_raw)
+    if k > Nk:
+        raise ValueError(f"{name}: topk={k} exceeds the {Nk} exemplar positions")
+    if not _hip_fp32(theta_raw):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    if N % 4 or Nk % 4 or not ops.corr_split_ok(B, C, N, Nk, 1, False) or not ops.corr_topk_ok(k):
+        raise ValueError(f"{name}: transport: the fused readout does not take B={B}, {N} x {Nk} positions, topk={k} (positions must be "
+                         "multiples of 4), and transport runs on no other route")
+    inv_t = 1.0 / temperature
+    with torch.no_grad():
+        planes = ops.OperandPlanes()
+        qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=True, want_chan=False)
+        f, g, row_lse = ops.corr_sinkhorn(qn, kn, inv_t, iters, tau, planes)
+        idx, z, lse = ops.corr_topk_biased(qn, kn, g, inv_t, k, planes)       # (k = 1: lse is row_lse bit for bit)
+        _, _, col_lse = ops.corr_topk_biased(kn, qn, f, inv_t, 1, planes)
+        shape = (B, fh, fw)
+        if k == 1:
+            m = _readout(idx[..., 0], z[..., 0], lse, shape, (gh, gw))
+        else:
+            val = _rank_first(z, shape, k)
+            m = TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.reshape(shape).unsqueeze(1)),
+                                 logit=val, lse=lse.reshape(shape), grid=(gh, gw))
+        return {"readout": m, "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
+                "match_mass": torch.exp(f + row_lse + math.log(N)).reshape(shape),
+                "key_mass": torch.exp(g + col_lse + math.log(Nk)).reshape(B, gh, gw)}
 
 
 # ---- K46: trainable sub-cell correspondence (a flow-style readout with gradients) --------------------------------------------------

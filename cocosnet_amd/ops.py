@@ -8,6 +8,7 @@ the reference (models/networks/correspondence.py:274,284).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import sys
 import threading
@@ -1123,6 +1124,95 @@ def corr_topk_labelled(qn, kn, q_label, k_label, inv_temperature: float, k: int,
 
 
 # ------------------------------------------------------------------------------------------
+# K50  biased readout and the Sinkhorn iteration on top of it: entropic optimal transport over the correlation, no HW x HW
+# ------------------------------------------------------------------------------------------
+#: the largest number of Sinkhorn iterations corr_sinkhorn runs (two launches each)
+SINKHORN_MAX_ITERS = 64
+
+
+def _corr_topk_bias_planes(qh, ql, kh, kl, k_bias, inv_temperature: float, k: int, name: str = "corr_topk_biased"):
+    """K50 on operand planes (as _corr_topk_planes) and a contiguous fp32 bias [Be,Nk] on their device (Be: the key planes' batch)"""
+    B, K, Nq, Nk, k_stride = _readout_planes(name, qh, ql, kh, kl)
+    k = _check_topk(name, k, Nk)
+    if tuple(k_bias.shape) != (kh.shape[0], Nk):
+        raise ValueError(f"{name}: k_bias {tuple(k_bias.shape)} does not fit k{tuple(kh.shape)}")
+    idx, val, lse = _readout_outputs((B, Nq), k, qh.device)
+    _call("corr_topk_biased", "cocos_corr_topk_bias_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), k_bias.data_ptr(),
+          idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, K, Nq, Nk, k, float(inv_temperature), SPLIT_OPERAND_SCALE, k_stride, _stream())
+    return idx, val, lse
+
+
+def _bias_table(name: str, k_bias, shape):
+    """A per-key bias -> contiguous fp32 without a graph.  TypeError unless it is a float32 tensor, ValueError unless it has `shape` and
+    needs no gradient (it is a constant of every op that takes it); the device is the caller's next refusal."""
+    if not torch.is_tensor(k_bias) or k_bias.dtype != torch.float32:
+        raise TypeError(f"{name}: k_bias must be a float32 tensor, got {k_bias.dtype if torch.is_tensor(k_bias) else type(k_bias).__name__}")
+    if tuple(k_bias.shape) != tuple(shape):
+        raise ValueError(f"{name}: k_bias is {tuple(k_bias.shape)}, expected {tuple(shape)}")
+    if k_bias.requires_grad:
+        raise ValueError(f"{name}: k_bias requires a gradient; the bias is not differentiable (pass k_bias.detach())")
+    return k_bias.contiguous()
+
+
+def corr_topk_biased(qn, kn, k_bias, inv_temperature: float, k: int, planes: OperandPlanes | None = None):
+    """corr_topk over z_ij = inv_temperature <qn_i, kn_j> + k_bias[b,j] (K50; forward only) -> (idx int32 [B,Nq,k], val [B,Nq,k] = z,
+    lse [B,Nq] = log sum_j exp z_ij).  k_bias [B,Nk] float32: finite values of any sign, or -inf to exclude a key (a row with every key
+    excluded has lse = val = -inf and indices in range; no NaN from finite or -inf input).  The bias is added to the logits inside the
+    scan, before the candidate list and the sum; a bias of zeros gives corr_topk's outputs bit for bit.  Operands, k and refusals as
+    corr_topk_labelled; a bias of another dtype raises TypeError, of another shape or one that requires a gradient ValueError."""
+    name = "corr_topk_biased"
+    B, Nq, Nk = _operand_shapes(name, qn, kn, width=False)
+    k_bias = _bias_table(name, k_bias, (B, Nk))
+    _check_topk(name, k, Nk)
+    _gate(name, ((qn, "qn"), (kn, "kn"), (k_bias, "k_bias")), True)
+    with torch.no_grad():
+        return _corr_topk_bias_planes(*_fetch_planes(name, qn, kn, planes, True)[2], k_bias, inv_temperature, k)
+
+
+def _sinkhorn_args(name: str, iters, tau):
+    """ValueError unless `iters` is an integer in 1..SINKHORN_MAX_ITERS and 0 < tau <= 1 -> (iters, tau)"""
+    if not _is_int(iters) or not 1 <= iters <= SINKHORN_MAX_ITERS:
+        raise ValueError(f"{name}: iters={iters!r}: expected an integer in 1..{SINKHORN_MAX_ITERS}")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau <= 1:
+        raise ValueError(f"{name}: tau={tau!r}: expected a number in (0, 1] (1: balanced transport)")
+    return iters, float(tau)
+
+
+def _sinkhorn_planes(qh, ql, kh, kl, inv_temperature: float, iters: int, tau: float):
+    """The iteration of corr_sinkhorn on dense operand planes [B,Nq,256], [B,Nk,256] -> (f [B,Nq], g [B,Nk], row_lse [B,Nq])"""
+    name = "corr_sinkhorn"
+    B, Nq, Nk = qh.shape[0], qh.shape[1], kh.shape[1]
+    log_mu, log_nu = -math.log(Nq), -math.log(Nk)
+    g = torch.zeros((B, Nk), device=qh.device, dtype=torch.float32)
+    for _ in range(iters):
+        f = tau * (log_mu - _corr_topk_bias_planes(qh, ql, kh, kl, g, inv_temperature, 1, name)[2])       # rows: sum over the keys
+        g = tau * (log_nu - _corr_topk_bias_planes(kh, kl, qh, ql, f, inv_temperature, 1, name)[2])       # columns: operands exchanged
+    return f, g, _corr_topk_bias_planes(qh, ql, kh, kl, g, inv_temperature, 1, name)[2]
+
+
+def corr_sinkhorn(qn, kn, inv_temperature: float, iters: int, tau: float = 1.0, planes: OperandPlanes | None = None):
+    """Log-domain Sinkhorn over s_ij = inv_temperature <qn_i, kn_j> with uniform marginals mu = 1 / Nq, nu = 1 / Nk (K50; forward only,
+    under torch.no_grad()) -> (f [B,Nq], g [B,Nk], row_lse [B,Nq]).  With g = 0, `iters` times:
+        f_i = tau (log mu_i - log sum_j exp(s_ij + g_j)),   g_j = tau (log nu_j - log sum_i exp(s_ij + f_i))
+    tau = 1 is balanced entropic transport (the column marginals of P_ij = exp(s_ij + f_i + g_j) are exact after every iteration),
+    tau < 1 the KL-relaxed form rho / (rho + eps).  row_lse_i = log sum_j exp(s_ij + g_j) against the FINAL g: the normaliser of the
+    row-conditional plan softmax_j(s_ij + g_j), and exp(f_i + row_lse_i) / mu_i is the row's mass (1 where its marginal is met).
+    The operand planes are made once; every half-step is one launch of the K = 1 biased readout (the column half-step with the two
+    plane pairs exchanged and f as the key bias), the affine update runs in torch on [B,N] vectors, row_lse costs one more launch:
+    2 iters + 1 launches, nothing Nq x Nk.  Operands as corr_topk (dense keys of the queries' batch); iters an integer in
+    1..SINKHORN_MAX_ITERS, 0 < tau <= 1, Nq and Nk multiples of 4 (ValueError)."""
+    name = "corr_sinkhorn"
+    B, Nq, Nk = _operand_shapes(name, qn, kn, width=False)
+    iters, tau = _sinkhorn_args(name, iters, tau)
+    if Nq % 4 or Nk % 4:
+        raise ValueError(f"{name}: Nq={Nq} and Nk={Nk} must be multiples of 4 (each side is the key side of one half-step)")
+    _gate(name, ((qn, "qn"), (kn, "kn")), True)
+    with torch.no_grad():
+        pl = _fetch_planes(name, qn, kn, planes, True, same_batch=True)[2]
+        return _sinkhorn_planes(*pl, float(inv_temperature), iters, tau)
+
+
+# ------------------------------------------------------------------------------------------
 # K48  mutual match: both softmax directions from one correlation sweep, and the round trip
 # ------------------------------------------------------------------------------------------
 #: hot_path.correspondence_mutual: True = one sweep of the fused kernel serves both directions where it runs; False = every call
@@ -1435,14 +1525,19 @@ class _SparseSoftmaxWarp(torch.autograd.Function):
     planes qh, ql, kh, kl.  Saved for the backward: the four planes, v^T, idx and w [B,Nq,k] — nothing with an Nq x Nk extent."""
 
     @staticmethod
-    def forward(ctx, qn, kn, v, idx, inv_t: float, qh, ql, kh, kl):
+    def forward(ctx, qn, kn, v, idx, inv_t: float, qh, ql, kh, kl, k_bias=None):
         B, Nq, K = qh.shape
         Nk, Cv, k = kh.shape[1], v.shape[1], idx.shape[2]
         vt = _transpose(v)
         out_t = torch.empty((B, Nq, Cv), device=v.device, dtype=torch.float32)
         w = torch.empty((B, Nq, k), device=v.device, dtype=torch.float32)
-        _call("sparse_softmax_warp_fwd", "cocos_sparse_softmax_warp_fwd_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
-              vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), B, K, Nq, Nk, Cv, k, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+        if k_bias is None:
+            _call("sparse_softmax_warp_fwd", "cocos_sparse_softmax_warp_fwd_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+                  vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), B, K, Nq, Nk, Cv, k, float(inv_t), SPLIT_OPERAND_SCALE, _stream())
+        else:      # K50: the bias is a constant — the backward below consumes the saved w and never sees it
+            _call("sparse_softmax_warp_bias_fwd", "cocos_sparse_softmax_warp_bias_fwd_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(),
+                  kl.data_ptr(), vt.data_ptr(), idx.data_ptr(), k_bias.data_ptr(), out_t.data_ptr(), w.data_ptr(), B, K, Nq, Nk, Cv, k,
+                  float(inv_t), SPLIT_OPERAND_SCALE, Nk, _stream())
         ctx.save_for_backward(qh, ql, kh, kl, vt, idx, w)
         ctx.inv_t = float(inv_t)
         ctx.mark_non_differentiable(w)
@@ -1476,10 +1571,11 @@ class _SparseSoftmaxWarp(torch.autograd.Function):
                 del dk_t
             if need_v:
                 dv = _transpose(dv_t)
-        return dqn, dkn, dv, None, None, None, None, None, None
+        return dqn, dkn, dv, None, None, None, None, None, None, None
 
 
-def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandPlanes | None = None, return_weights: bool = False):
+def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandPlanes | None = None, return_weights: bool = False,
+                        k_bias=None):
     """out [B,Cv,Nq] = sum_r w[b,i,r] * v[b,:,idx[b,i,r]] with w = softmax over r of inv_temperature * <qn[b,:,i], kn[b,:,idx[b,i,r]]>:
     attention over the k keys per query that a top-k readout selected (K42) — the k-sparse softmax of match(blend="topk"), with
     gradients for qn, kn and v (each computed only when needed; idx is data).  qn [B,256,Nq], kn [B,256,Nk] fp32 with unit-norm
@@ -1487,7 +1583,11 @@ def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandP
     operand planes that chose the candidates); v [B,Cv,Nk] fp32; idx [B,Nq,k] int32 / int64 with 1 <= k <= MATCH_TOPK_MAX, k <= Nk —
     any values: repeats inside a row are legal, values outside [0, Nk) are clamped into it.  Nothing Nq x Nk is allocated, forward or
     backward; dkn and dv are gathered over the inverse table of idx in a fixed order (no atomics: bitwise reproducible).
-    `return_weights`: also return w [B,Nq,k] (no gradient)."""
+    `return_weights`: also return w [B,Nq,k] (no gradient).
+    `k_bias` (K50; None, the default, is the code path above, untouched): float32 [B,Nk], finite or -inf — w = softmax over r of
+    s_r + k_bias[b, idx[b,i,r]], the row-conditional transport plan on the k candidates when the bias is corr_sinkhorn's g.  The bias
+    is NOT differentiable (one that requires a gradient raises ValueError): the gradients to qn, kn and v are those of the blend with
+    the bias held constant.  A row whose candidates all carry -inf blends them uniformly."""
     if idx.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"sparse_softmax_warp: idx must be int32 or int64, got {idx.dtype}")
     if qn.dim() != 3 or kn.dim() != 3 or v.dim() != 3 or idx.dim() != 3:
@@ -1500,12 +1600,14 @@ def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandP
     if K != FUSED_K:
         raise ValueError(f"sparse_softmax_warp: needs {FUSED_K} channels, got {K}")
     _check_topk("sparse_softmax_warp", int(idx.shape[2]), Nk)
-    _gate("sparse_softmax_warp", ((qn, "qn"), (kn, "kn"), (v, "v"), (idx, "idx")), True)
+    if k_bias is not None:
+        k_bias = _bias_table("sparse_softmax_warp", k_bias, (B, Nk))
+    _gate("sparse_softmax_warp", ((qn, "qn"), (kn, "kn"), (v, "v"), (idx, "idx")) + (((k_bias, "k_bias"),) if k_bias is not None else ()), True)
     qn, kn, pl = _fetch_planes("sparse_softmax_warp", qn, kn, planes, False)
     v = _chk(v, "sparse_softmax_warp: v")
     with torch.no_grad():
         idx = idx.clamp(0, Nk - 1).to(torch.int32).contiguous()
-    out, w = _SparseSoftmaxWarp.apply(qn, kn, v, idx, float(inv_temperature), *pl)
+    out, w = _SparseSoftmaxWarp.apply(qn, kn, v, idx, float(inv_temperature), *pl, k_bias)
     return (out, w) if return_weights else out
 
 

@@ -1263,6 +1263,19 @@ int cocos_row_topk_lse(const float* logits, int* idx, float* val, float* lse, in
 int cocos_corr_topk_labels_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const int* q_label, const int* k_label,
                                  int* idx_out, float* val_out, float* lse_out, int B, int K, int Nq, int Nk, int k,
                                  float inv_temperature, float operand_scale, long long k_batch_stride, cocos_stream_t stream);
+/* K50 biased readout (corr_topk_bias_f16x3.hip, the BIAS instantiations): cocos_corr_topk_f16x3 over z_ij = s_ij + k_bias[b,j].
+ *     k_bias fp32 [B,Nk] (k_batch_stride == 0: the one [Nk] row of the shared key set), 4-byte aligned, read through a bounds-checked
+ *     descriptor.  val holds z (natural units), lse = log sum_j exp z_ij, idx / val the k best z in K39's order (z descending, the lower
+ *     key among bitwise-equal z).  The bias meets the raw accumulator in one fma (raw += bias * operand_scale^2 / inv_temperature), so a
+ *     bias of zeros gives cocos_corr_topk_f16x3's three outputs bit for bit.  A finite bias of any sign is legal; -inf excludes the key
+ *     (K47's mask is the bias 0 / -inf); a row with every key excluded has lse = -inf, val = -inf and indices in [0, Nk); finite or -inf
+ *     input never produces a NaN.  +inf and NaN are not sanitised; idx stays in [0, Nk).  One launch is one half-step of a log-domain
+ *     Sinkhorn iteration: f_i = tau (log mu_i - lse_i) with the other side's potential g as the bias; the column half-step is the same
+ *     entry with the operand planes exchanged.  Arguments, limits and error codes of cocos_corr_topk_f16x3; a null k_bias is
+ *     COCOS_ERR_INVALID; all checked before any HIP call. */
+int cocos_corr_topk_bias_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* k_bias, int* idx_out,
+                               float* val_out, float* lse_out, int B, int K, int Nq, int Nk, int k, float inv_temperature,
+                               float operand_scale, long long k_batch_stride, cocos_stream_t stream);
 int cocos_gather_blend_patches(const float* img, const int* idx, const float* w, float* out, int B, int C, int H, int W, int down,
                                int k, long long img_batch_stride, cocos_stream_t stream);
 
@@ -1357,6 +1370,14 @@ int cocos_pair_logits_bwd_query_f16x3(const void* kh, const void* kl, const int*
 int cocos_sparse_softmax_warp_fwd_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* v_t,
                                         const int* idx, float* out_t, float* w, int B, int K, int Nq, int Nk, int Cv, int k,
                                         float inv_temperature, float operand_scale, cocos_stream_t stream);
+/* K50: the forward above with s_r += k_bias[b, j_r] (the clamped j_r) before the softmax over r — the row-conditional transport plan
+ *     softmax_j(s_ij + g_j) on the k candidates.  k_bias fp32, 4-byte aligned, [B,Nk] with bias_batch_stride == Nk or one [Nk] row with
+ *     bias_batch_stride == 0 (anything else, and a null bias, is COCOS_ERR_INVALID); finite or -inf.  A row whose k candidates all
+ *     carry -inf gets the uniform w = 1 / k.  The two backward entries are unchanged: they consume the saved w, the bias is a constant. */
+int cocos_sparse_softmax_warp_bias_fwd_f16x3(const void* qh, const void* ql, const void* kh, const void* kl, const float* v_t,
+                                             const int* idx, const float* k_bias, float* out_t, float* w, int B, int K, int Nq, int Nk,
+                                             int Cv, int k, float inv_temperature, float operand_scale, long long bias_batch_stride,
+                                             cocos_stream_t stream);
 int cocos_sparse_softmax_warp_bwd_query_f16x3(const void* kh, const void* kl, const float* v_t, const float* dout_t, const int* idx,
                                               const float* w, float* ds, float* dq_t /* nullable */, int B, int K, int Nq, int Nk,
                                               int Cv, int k, float inv_temperature, float operand_scale, cocos_stream_t stream);
