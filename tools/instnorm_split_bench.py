@@ -16,7 +16,6 @@ csrc/instnorm_split.hip (forward 12 B/element, backward 20) over the time betwee
 import argparse
 import json
 import os
-import statistics
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,25 +23,16 @@ sys.path.insert(0, REPO)
 import torch
 import torch.nn.functional as F
 
+import benchlib
 from cocosnet_amd import ops
 
 SHAPES = [(8, 64, 256, 256), (4, 64, 512, 512), (4, 128, 256, 256), (4, 256, 256, 256)]
 ROUNDS, ITERS, WARMUP = 7, 10, 3
 
 
-def _time(f, n=ITERS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
 def _summary(ms):
-    med = statistics.median(ms)
-    return {"median_ms": round(med, 4), "spread": round((max(ms) - min(ms)) / med, 4), "rounds_ms": [round(v, 4) for v in ms]}
+    s = benchlib.summary(ms)
+    return {"median_ms": round(s.median, 4), "spread": round(s.spread, 4), "rounds_ms": [round(v, 4) for v in ms]}
 
 
 def bench_shape(shape):
@@ -70,7 +60,7 @@ def bench_shape(shape):
     ms = {(gs, n): [] for gs, n, _ in runs}
     for r in range(ROUNDS):
         for gs, n, f in (runs if r % 2 == 0 else runs[::-1]):
-            ms[(gs, n)].append(_time(f))
+            ms[(gs, n)].append(benchlib.time_calls(f, ITERS))
     out = {"shape": list(shape), "elements": x.numel(), "MB_per_tensor": round(x.numel() * 4 / 1e6, 1)}
     for gs in arms:
         out[gs] = {n: _summary(ms[(gs, n)]) for n in arms[gs]}
@@ -127,7 +117,7 @@ def module_ab(rounds=3, steps=6, warmup=3):
                 for _ in range(warmup):
                     step()
                 torch.cuda.synchronize()
-                ms[on].append(_time(step, steps))
+                ms[on].append(benchlib.time_calls(step, steps))
     finally:
         ops.INSTNORM_SPLIT = saved
     return {"scope": "NoVGGCorrespondence fwd+bwd, batch 8, 256x256, ADE20k flags (bench.py --scope netcorr's step)",

@@ -15,13 +15,13 @@ per iteration, `spread` = (max - min) / median."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import torch
 
+import benchlib
 from cocosnet_amd import labels, producers
 
 ROUNDS, ITERS, WARMUP = 7, 10, 3
@@ -30,19 +30,9 @@ SHAPES = {"layer1": dict(cout=64, size=256, sample=1, reflect=0, relu=False),
           "mlp_shared": dict(cout=128, size=256, sample=4, reflect=1, relu=True)}
 
 
-def _time(f, n=ITERS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
 def _summary(ms):
-    med = statistics.median(ms)
-    return {"median_ms": round(med, 4), "spread": round((max(ms) - min(ms)) / med, 4), "rounds_ms": [round(v, 4) for v in ms]}
+    s = benchlib.summary(ms)
+    return {"median_ms": round(s.median, 4), "spread": round(s.spread, 4), "rounds_ms": [round(v, 4) for v in ms]}
 
 
 def _interleaved(runs):
@@ -54,7 +44,7 @@ def _interleaved(runs):
     order = list(runs.items())
     for r in range(ROUNDS):
         for n, f in (order if r % 2 == 0 else order[::-1]):
-            ms[n].append(_time(f))
+            ms[n].append(benchlib.time_calls(f, ITERS))
     return {n: _summary(v) for n, v in ms.items()}
 
 
@@ -118,7 +108,7 @@ def module_ab(rounds=3, steps=6, warmup=3):
                 for _ in range(warmup):
                     step()
                 torch.cuda.synchronize()
-                ms[on].append(_time(step, steps))
+                ms[on].append(benchlib.time_calls(step, steps))
     finally:
         labels.LABEL_CONV = saved
     return {"scope": "NoVGGCorrespondence fwd+bwd, batch 8, 256x256, ADE20k flags (bench.py --scope netcorr's step)",

@@ -16,6 +16,8 @@ import sys
 
 import torch
 
+import benchlib
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -58,17 +60,9 @@ def make_step(shape, dev, B=8, S=256, nc=151):
     return step, inputs
 
 
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
 def stats(ms):
-    return f"median {statistics.median(ms):8.3f} ms  min {min(ms):8.3f}  max {max(ms):8.3f}  (n = {len(ms)})"
+    s = benchlib.summary(ms)
+    return f"median {s.median:8.3f} ms  min {s.min:8.3f}  max {s.max:8.3f}  (n = {len(ms)})"
 
 
 def main():
@@ -87,35 +81,33 @@ def main():
         calls[0] += 1
         return real_call(name, *args)
 
+    def counted(step):
+        calls[0], _lib.call = 0, counting
+        try:
+            step()
+        finally:
+            _lib.call = real_call
+
     for shape in ("ade20k", "celebahq"):
         step, inputs = make_step(shape, dev)
         ms, peak, ncalls = {"unfused": [], "fused": []}, {}, {}
         for rep in range(a.warmup + a.reps):
             for arm in ("unfused", "fused"):              # interleaved: both arms see the same clocks and allocator state
                 losses.FUSED = arm == "fused"
-                t = timed(step)
+                t = benchlib.time_calls(step, 1)
                 if rep >= a.warmup:
                     ms[arm].append(t)
         for arm in ("unfused", "fused"):
             losses.FUSED = arm == "fused"
             for _, t in loss_case.leaves(inputs):         # the previous step's gradients go first: the peak then counts this step's
                 t.grad = None
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated()
-            torch.cuda.reset_peak_memory_stats()
-            calls[0], _lib.call = 0, counting
-            try:
-                step()
-            finally:
-                _lib.call = real_call
-            torch.cuda.synchronize()
-            peak[arm], ncalls[arm] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20, calls[0]
+            peak[arm], ncalls[arm] = benchlib.peak_bytes(lambda: counted(step)) / 2 ** 20, calls[0]
         losses.FUSED = True
         for arm in ("unfused", "fused"):
             lines.append(f"{shape:9s} {arm:8s} {stats(ms[arm])}  C-ABI calls {ncalls[arm]:3d}  peak above the inputs (gradients included) {peak[arm]:9.1f} MiB")
-        mu, mf = statistics.median(ms["unfused"]), statistics.median(ms["fused"])
-        lines.append(f"{shape:9s} fused / unfused = {mf / mu:.3f}; spread of the unfused arm (max - min) / median = "
-                     f"{(max(ms['unfused']) - min(ms['unfused'])) / mu:.3f}")
+        unfused = benchlib.summary(ms["unfused"])
+        lines.append(f"{shape:9s} fused / unfused = {statistics.median(ms['fused']) / unfused.median:.3f}; spread of the unfused arm "
+                     f"(max - min) / median = {unfused.spread:.3f}")
         if shape == "ade20k":
             # the fm + perc group on its own against a copy of the same bytes
             fake, realf = inputs["fake_features"], [t.detach() for t in inputs["real_features"]]
@@ -131,7 +123,7 @@ def main():
             t_copy, t_fwd, t_bwd = [], [], []
             for rep in range(a.warmup + a.reps):
                 for fn, acc in ((copy, t_copy), (fwd, t_fwd), (bwd, t_bwd)):
-                    t = timed(fn)
+                    t = benchlib.time_calls(fn, 1)
                     if rep >= a.warmup:
                         acc.append(t)
             rate = lambda nbytes, t: nbytes / (statistics.median(t) * 1e-3) / 1e12

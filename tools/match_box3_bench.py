@@ -18,43 +18,19 @@ import sys
 
 import torch
 
+import benchlib
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = [(8, 64, 64), (1, 128, 128)]
 KC, INV_T = 2304.0, 100.0
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out
-    return peak
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k37_match_box3_timing.json"))
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--window", type=float, default=0.2, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k37_match_box3_timing.json"), min_rounds=0, rounds=7, window=0.2)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("match_box3_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_box3_bench")
     from cocosnet_amd import ops
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_match
     dev = torch.device("cuda", 0)
@@ -91,16 +67,8 @@ def main():
             "match_new_cols": lambda: match(True, "cols"),
             "match_parent_cols": lambda: match(False, "cols"),
         }
-        counts = {}
-        for name, fn in rows.items():            # warm-up of every row at this shape, and the iteration count of its window
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-            counts[name] = max(3, int(args.window * 1e3 / max(_time(fn, 3), 1e-3)))
-        samples = {name: [] for name in rows}
-        for _ in range(args.rounds):             # alternating: one window of every row per round
-            for name, fn in rows.items():
-                samples[name].append(_time(fn, counts[name]))
+        counts = benchlib.window_counts(rows, args.window, args.warmup, probe=3)
+        samples = benchlib.alternating(rows, counts, args.rounds)
         new, old = match(True, "rows"), match(False, "rows")
         parity = {"equal_indices": float((new.index == old.index).float().mean()),
                   "max_abs_lse_diff": float((new.lse - old.lse).abs().max()),
@@ -109,7 +77,8 @@ def main():
         entry = {"B": B, "grid": [h, w], "N": N, "matrix_bytes": B * N * N * 4,
                  "rows": {name: {"median": statistics.median(v), "min": min(v), "max": max(v), "iters_per_window": counts[name], "windows": v}
                           for name, v in samples.items()},
-                 "peak_bytes_above_inputs": {"match_new": _peak(lambda: match(True, "rows")), "match_parent": _peak(lambda: match(False, "rows"))},
+                 "peak_bytes_above_inputs": {"match_new": benchlib.peak_bytes(lambda: match(True, "rows")),
+                                             "match_parent": benchlib.peak_bytes(lambda: match(False, "rows"))},
                  "new_vs_parent": parity}
         result["shapes"].append(entry)
         print(f"B = {B}, {h} x {w}:")

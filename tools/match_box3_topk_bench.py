@@ -16,13 +16,12 @@ The rule the file records: a k at which `k41` is slower than `chain` at either s
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -32,45 +31,16 @@ INV_T, KC = 100.0, 2304.0
 KS = (2, 4, 8)
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out
-    return peak
-
-
-def register_table():
-    """[(K, chunked, VGPRs, AGPRs, SGPRs, scratch bytes / lane, LDS bytes, waves / SIMD)] of every box3_topk_kernel instantiation (K = 1
-    is K37) from hipcc's kernel-resource-usage remarks (device code only); None without hipcc.  LDS is dynamic: the report says 0."""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
+def register_rows():
+    """[(K, chunked, VGPRs, AGPRs, SGPRs, scratch bytes / lane, waves / SIMD)] of every box3_topk_kernel instantiation (K = 1 is K37) from
+    hipcc's kernel-resource-usage remarks (device code only); None without hipcc.  LDS is dynamic: the report says 0."""
+    usage = benchlib.resource_usage("box3_fused_f16x3.hip", keep=("box3_topk_kernel",))
+    if usage is None:
         return None
     rows = []
-    with tempfile.TemporaryDirectory(prefix="cocos_k41_") as tmp:
-        unit = "box3_fused_f16x3.hip"
-        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-        for name, body in re.findall(r"Function Name: (\S*box3_topk_kernel\S*)(.*?)LDS Size[^:\n]*: (?:\d+)", text, flags=re.S):
-            get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-            k, chunked = re.search(r"kernelILi(\d+)ELb([01])E", name).groups()
-            rows.append((int(k), int(chunked), get(r" VGPRs"), get("AGPRs"), get("TotalSGPRs"), get("ScratchSize"), get("Occupancy")))
+    for u in usage:
+        k, chunked = re.search(r"kernelILi(\d+)ELb([01])E", u.name).groups()
+        rows.append((int(k), int(chunked), u.vgprs, u.agprs, u.sgprs, u.scratch, u.occupancy))
     return sorted(rows)
 
 
@@ -109,21 +79,13 @@ def bench_shape(B, H, W, args, lines):
         arms[f"kernel k41 {k} T"] = lambda k=k: kernel(k, True)
     shipped = [k for k in KS if ops.box3_topk_ok(k)]
 
-    counts = {}
-    for name, fn in arms.items():                # warm-up of every arm, and the iteration count of its window
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-    samples = {name: [] for name in arms}
-    for _ in range(args.rounds):                 # alternating: one window of every arm per round
-        for name, fn in arms.items():
-            samples[name].append(_time(fn, counts[name]))
+    counts = benchlib.window_counts(arms, args.window, args.warmup)
+    samples = benchlib.alternating(arms, counts, args.rounds)
     med = {name: statistics.median(v) for name, v in samples.items()}
-    peaks = {"k37": _peak(lambda: match(True, 1))}
+    peaks = {"k37": benchlib.peak_bytes(lambda: match(True, 1))}
     for k in KS:
-        peaks[f"k41 {k}"] = _peak(lambda: match(True, k))
-        peaks[f"chain {k}"] = _peak(lambda: match(False, k))
+        peaks[f"k41 {k}"] = benchlib.peak_bytes(lambda: match(True, k))
+        peaks[f"chain {k}"] = benchlib.peak_bytes(lambda: match(False, k))
     # both routes agree on what they return (the picks may differ where two logits are closer than the kernels' error)
     x, y = match(True, 8), match(False, 8)
     parity = (float((x.index == y.index).float().mean()), float((x.logit - y.logit).abs().max()), float((x.lse - y.lse).abs().max()))
@@ -144,15 +106,9 @@ def bench_shape(B, H, W, args, lines):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k41_match_box3_topk.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k41_match_box3_topk.txt"))
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_box3_topk_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_box3_topk_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_box3_topk_bench")
     from cocosnet_amd import ops
     lines = [f"# tools/match_box3_topk_bench.py on {torch.cuda.get_device_name(0)}: match_kernel 3, PONO_C",
              f"# ms per call: median of {args.rounds} alternating windows of ~{args.window} s after {args.warmup} warm-up calls (min .. max of the windows)",
@@ -163,7 +119,7 @@ def main():
         torch.cuda.empty_cache()
     lines.append("# rule: a k at which k41 is slower than the chain at either shape leaves ops.box3_topk_ok — "
                  + (f"k = {sorted(slower)} must leave it" if slower else "none is: every instantiation stays"))
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, __launch_bounds__(256, 2); the budget at 2 waves per SIMD is 256 "
                  "VGPRs + AGPRs; LDS is dynamic: 8 Nk bytes of statistics, 32 KiB in the chunked flavour, + 18 KiB transposed)")
     if table is None:
@@ -171,12 +127,7 @@ def main():
     else:
         lines += [f"{'K37 (K = 1)' if k == 1 else f'K41 K = {k}':12s} {'chunked' if c else 'whole  '}  VGPRs {v:3d}  AGPRs {ag:3d}  SGPRs {sg:3d}  "
                   f"scratch {s} B/lane  waves/SIMD {o}" for k, c, v, ag, sg, s, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -15,13 +15,12 @@ rounds (>= 20) after a warm-up:
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -31,51 +30,26 @@ KERNELS = (("match_refine_bwd_f16x3.hip", ("match_refine_bwd_query_kernel", "mat
            ("gather_patches.hip", ("gather_patches_subcell_bwd_off_kernel",)))
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, SGPRs, scratch bytes / lane, waves / SIMD)] of the new kernels from hipcc's kernel-resource-usage remarks; None
     without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
-        return None
     rows = []
-    with tempfile.TemporaryDirectory(prefix="cocos_k46_") as tmp:
-        for unit, wanted in KERNELS:
-            cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                   os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-            text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-            for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-                want = next((w for w in wanted if w in name), None)
-                if want is None:
-                    continue
-                get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-                inst = re.search(r"kernelILi(\d+)E", name)
-                rows.append((want + (f"<{inst.group(1)}>" if inst else ""), get(r" VGPRs"), get("TotalSGPRs"), get("ScratchSize"),
-                             get("Occupancy")))
+    for unit, wanted in KERNELS:
+        usage = benchlib.resource_usage(unit, keep=wanted)
+        if usage is None:
+            return None
+        for u in usage:
+            want = next(w for w in wanted if w in u.name)
+            inst = re.search(r"kernelILi(\d+)E", u.name)
+            rows.append((want + (f"<{inst.group(1)}>" if inst else ""), u.vgprs, u.sgprs, u.scratch, u.occupancy))
     return sorted(rows)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k46_match_flow.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k46_match_flow.txt"))
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_flow_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_flow_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_flow_bench")
     from cocosnet_amd import _lib, ops
     from cocosnet_amd import correspondence as cc
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_flow, correspondence_sparse
@@ -147,34 +121,21 @@ def main():
              "(the key kernel walks such a list serially for every key around it)",
              "# row reads of the query kernel: 2 B N (2 r + 1)^2 rows of 1 KiB (scores, then dq) = "
              + ", ".join(f"{2 * B * N * (2 * r + 1) ** 2 * 1024 / 1e9:.2f} GB at r = {r}" for r in (1, 2, 3))]
-    counts = {}
-    for name, fn in arms.items():            # warm-up of every arm, and the iteration count of its window
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-    samples = {name: [] for name in arms}
-    for _ in range(args.rounds):                 # alternating: one window of every arm per round
-        for name, fn in arms.items():
-            samples[name].append(_time(fn, counts[name]))
+    counts = benchlib.window_counts(arms, args.window, args.warmup)
+    samples = benchlib.alternating(arms, counts, args.rounds)
     med = {name: statistics.median(v) for name, v in samples.items()}
     for name in arms:
         v = samples[name]
         lines.append(f"{name:24s} {med[name]:9.4f} ms  ({min(v):.4f} .. {max(v):.4f}; {counts[name]} calls per window)")
     lines.append("ratios (medians): " + "   ".join(f"flow {r} / sparse k=4 = {med[f'flow {r} fwd+bwd'] / med['sparse k=4 fwd+bwd']:.3f}"
                                                      for r in (1, 2, 3)))
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:40s} VGPRs {v:3d}  SGPRs {s:3d}  scratch {sc} B/lane  waves/SIMD {o}" for name, v, s, sc, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

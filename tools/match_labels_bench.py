@@ -14,13 +14,12 @@ Tile skipping is not built, so there is no on / off pair of rows.
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -28,34 +27,17 @@ sys.path.insert(0, REPO)
 DOWN, NC, INV_T = 4, 7, 100.0
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of corr_topk_f16x3.hip from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
+    usage = benchlib.resource_usage("corr_topk_f16x3.hip")
+    if usage is None:
         return None
-    with tempfile.TemporaryDirectory(prefix="cocos_k47_") as tmp:
-        unit = "corr_topk_f16x3.hip"
-        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
     rows = []
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-        get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-        inst = re.search(r"kernelILi(\d+)ELb([01])E", name)
-        label = f"corr_topk_f16x3_kernel<{inst.group(1)}, {'true' if inst.group(2) == '1' else 'false'}>" if inst else name
-        rows.append((label, get(r" VGPRs"), get("AGPRs"), get("ScratchSize"), get("Occupancy")))
+    for u in usage:
+        inst = re.search(r"kernelILi(\d+)ELb([01])E", u.name)
+        label = f"corr_topk_f16x3_kernel<{inst.group(1)}, {'true' if inst.group(2) == '1' else 'false'}>" if inst else u.name
+        rows.append((label, u.vgprs, u.agprs, u.scratch, u.occupancy))
     return rows
 
 
@@ -74,17 +56,11 @@ def blocky_segmentation(B, H, W, blocks, seed, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k47_match_labels.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k47_match_labels.txt"))
     ap.add_argument("--shape", default="8x64", help="B x grid side")
     ap.add_argument("--ks", default="1,4")
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_labels_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_labels_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_labels_bench")
     from cocosnet_amd import hot_path, ops
     dev = torch.device("cuda", 0)
     B, side = (int(v) for v in args.shape.split("x"))
@@ -114,16 +90,8 @@ def main():
                 "7 blocky classes": lambda: ops.corr_topk_labelled(qn, kn, q_eff, k_eff, INV_T, k, planes)}
         a, b_ = arms["unlabelled"](), arms["one label"]()
         lines.append("one label == unlabelled bitwise: " + str(all(torch.equal(x, y) for x, y in zip(a, b_))))
-        counts = {}
-        for name, fn in arms.items():            # warm-up of every arm, and the iteration count of its window
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-            counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-        samples = {name: [] for name in arms}
-        for _ in range(args.rounds):                 # alternating: one window of every arm per round
-            for name, fn in arms.items():
-                samples[name].append(_time(fn, counts[name]))
+        counts = benchlib.window_counts(arms, args.window, args.warmup)
+        samples = benchlib.alternating(arms, counts, args.rounds)
         med = {name: statistics.median(v) for name, v in samples.items()}
         for name in arms:
             v = samples[name]
@@ -133,18 +101,13 @@ def main():
                      f"7 blocky classes / unlabelled = {med['7 blocky classes'] / med['unlabelled']:.4f}   "
                      f"spread of the unlabelled windows (max - min) / median = {(max(base) - min(base)) / med['unlabelled']:.4f}")
 
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:36s} VGPRs {v:3d}  AGPRs {a:3d}  scratch {s} B/lane  waves/SIMD {o}" for name, v, a, s, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

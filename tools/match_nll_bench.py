@@ -12,38 +12,25 @@ Alternating windows, median and spread, as tools/match_mutual_bench.py; peak all
 """
 import argparse
 import os
-import statistics
 import sys
 
 import torch
 
+import benchlib
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from tools.match_mutual_bench import _time  # noqa: E402
 
 INV_T = 100.0
 F16_MFMA_PEAK_TFLOPS = 2516.6      # MI355X dense f16 matrix peak (vendor figure); the split product spends three terms per useful one
 
 
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k49_match_nll_timing.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k49_match_nll_timing.txt"), min_rounds=0)
     ap.add_argument("--shapes", default="8x64,1x128", help="comma-separated B x grid side")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("match_nll_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_nll_bench")
     from cocosnet_amd import ops
     dev = torch.device("cuda", 0)
     lines = [f"# tools/match_nll_bench.py on {torch.cuda.get_device_name(0)}: K = 256, inv_t = {INV_T:g}; ms per call: median of {args.rounds} "
@@ -77,28 +64,21 @@ def main():
         sweep = lambda: ops._corr_lse_bwd_planes(*pl, rows[2], cols[2], ga, gb, INV_T)
         arms = {"(b) corr_pair_nll fwd+bwd": fused, "(c) the sweep alone": sweep}
         try:
-            mem_a = _peak(materialised)
+            mem_a = benchlib.peak_bytes(materialised) / 2 ** 20
             arms = dict({"(a) materialised fwd+bwd": materialised}, **arms)
         except torch.cuda.OutOfMemoryError:
             mem_a = None
-        mem_b = _peak(fused)
+        mem_b = benchlib.peak_bytes(fused) / 2 ** 20
         lines.append(f"## B = {B}, {side} x {side} grid (Nq = Nk = {N})")
         lines.append("peak allocation growth of one forward + backward: (a) " + ("out of memory" if mem_a is None else f"{mem_a:.1f} MiB")
                      + f"   (b) {mem_b:.1f} MiB")
-        counts = {}
-        for name, fn in arms.items():
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-            counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-        samples = {name: [] for name in arms}
-        for _ in range(args.rounds):
-            for name, fn in arms.items():
-                samples[name].append(_time(fn, counts[name]))
-        med = {name: statistics.median(v) for name, v in samples.items()}
-        for name, v in samples.items():
-            lines.append(f"{name:28s} {med[name]:9.4f} ms  ({min(v):.4f} .. {max(v):.4f}; spread (max - min) / median = "
-                         f"{(max(v) - min(v)) / med[name]:.4f}; {counts[name]} calls per window)")
+        counts = benchlib.window_counts(arms, args.window, args.warmup)
+        samples = benchlib.alternating(arms, counts, args.rounds)
+        stats = {name: benchlib.summary(v) for name, v in samples.items()}
+        med = {name: s.median for name, s in stats.items()}
+        for name, s in stats.items():
+            lines.append(f"{name:28s} {s.median:9.4f} ms  ({s.min:.4f} .. {s.max:.4f}; spread (max - min) / median = "
+                         f"{s.spread:.4f}; {counts[name]} calls per window)")
         useful = 2 * 2.0 * B * N * N * 256
         tf = useful / (med["(c) the sweep alone"] * 1e-3) / 1e12
         lines.append(f"the sweep: {useful / 1e9:.1f} GFLOP useful -> {tf:.1f} TFLOP/s = {100 * tf / (F16_MFMA_PEAK_TFLOPS / 3):.1f} % of the f16 MFMA peak / 3 "
@@ -107,12 +87,7 @@ def main():
             lines.append(f"(b) / (a) = {med['(b) corr_pair_nll fwd+bwd'] / med['(a) materialised fwd+bwd']:.4f}")
         del q, k, q0, k0, pl, rows, cols
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

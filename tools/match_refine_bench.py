@@ -13,13 +13,12 @@ rounds (>= 20) after a warm-up:
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -27,50 +26,25 @@ sys.path.insert(0, REPO)
 B, CROP, NC, INV_T = 8, 256, 151, 100.0
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, SGPRs, scratch bytes / lane, waves / SIMD)] of the two new kernels from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
-        return None
     rows = []
-    with tempfile.TemporaryDirectory(prefix="cocos_k44_") as tmp:
-        for unit, want in (("match_refine_f16x3.hip", "match_refine_kernel"), ("gather_patches.hip", "gather_patches_subcell_kernel")):
-            cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                   os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-            text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-            for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-                if want not in name:
-                    continue
-                get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-                inst = re.search(r"kernelILi(\d+)E", name)
-                rows.append((want + (f"<{inst.group(1)}>" if inst else ""), get(r" VGPRs"), get("TotalSGPRs"), get("ScratchSize"),
-                             get("Occupancy")))
+    for unit, want in (("match_refine_f16x3.hip", "match_refine_kernel"), ("gather_patches.hip", "gather_patches_subcell_kernel")):
+        usage = benchlib.resource_usage(unit, keep=(want,))
+        if usage is None:
+            return None
+        for u in usage:
+            inst = re.search(r"kernelILi(\d+)E", u.name)
+            rows.append((want + (f"<{inst.group(1)}>" if inst else ""), u.vgprs, u.sgprs, u.scratch, u.occupancy))
     return rows
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k44_match_refine.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k44_match_refine.txt"))
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_refine_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_refine_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_refine_bench")
     from cocosnet_amd import correspondence as cc
     from cocosnet_amd import ops
     dev = torch.device("cuda", 0)
@@ -108,16 +82,8 @@ def main():
              "(min .. max of the windows)",
              f"# row reads of ops.match_refine: B N (2 r + 1)^2 rows of 1 KiB (hi + lo) = "
              + ", ".join(f"{B * N * (2 * r + 1) ** 2 * 1024 / 1e9:.2f} GB at r = {r}" for r in (1, 2, 3))]
-    counts = {}
-    for name, fn in arms.items():            # warm-up of every arm, and the iteration count of its window
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-    samples = {name: [] for name in arms}
-    for _ in range(args.rounds):                 # alternating: one window of every arm per round
-        for name, fn in arms.items():
-            samples[name].append(_time(fn, counts[name]))
+    counts = benchlib.window_counts(arms, args.window, args.warmup)
+    samples = benchlib.alternating(arms, counts, args.rounds)
     med = {name: statistics.median(v) for name, v in samples.items()}
     for name in arms:
         v = samples[name]
@@ -125,18 +91,13 @@ def main():
     lines.append("ratios (medians): " + "   ".join(f"match refine={r} / match = {med[f'match refine={r}'] / med['match']:.3f}" for r in (1, 2)))
     lines.append("effective row-read rate of the kernel: " + "   ".join(
         f"r = {r}: {B * N * (2 * r + 1) ** 2 * 1024 / 1e9 / (med[f'refine {r} (kernel)'] * 1e-3):.0f} GB/s" for r in (1, 2, 3)))
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:32s} VGPRs {v:3d}  SGPRs {s:3d}  scratch {sc} B/lane  waves/SIMD {o}" for name, v, s, sc, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

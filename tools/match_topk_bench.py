@@ -16,13 +16,12 @@ The rule the file records: a k at which `k39a` is slower than `materialise+k39b`
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -31,59 +30,21 @@ B, H, W, INV_T = 8, 64, 64, 100.0
 KS = (2, 4, 8)
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out
-    return peak
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of every instantiation in corr_topk_f16x3.hip (K = 1 is K36a) from
     hipcc's kernel-resource-usage remarks (device code only, a few seconds); None without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
+    usage = benchlib.resource_usage("corr_topk_f16x3.hip")
+    if usage is None:
         return None
-    rows = []
-    with tempfile.TemporaryDirectory(prefix="cocos_k39_") as tmp:
-        unit = "corr_topk_f16x3.hip"
-        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-        for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-            get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-            k = int(re.search(r"kernelILi(\d+)E", name).group(1))
-            rows.append((k, get(r" VGPRs"), get("AGPRs"), get("ScratchSize"), get("Occupancy")))
-    return [("K36a (K = 1)" if k == 1 else f"K39a K = {k}", *rest) for k, *rest in sorted(rows)]
+    rows = sorted((int(re.search(r"kernelILi(\d+)E", u.name).group(1)), u.vgprs, u.agprs, u.scratch, u.occupancy) for u in usage)
+    return [("K36a (K = 1)" if k == 1 else f"K39a K = {k}", *rest) for k, *rest in rows]
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k39_match_topk.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k39_match_topk.txt"))
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_topk_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_topk_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_topk_bench")
     from cocosnet_amd import hot_path, ops
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_match
     dev = torch.device("cuda", 0)
@@ -119,22 +80,14 @@ def main():
         arms[f"kernel k39a {k}"] = lambda k=k: ops._corr_topk_planes(qh, ql, kh, kl, INV_T, k)
     fused_ks = [k for k in KS if ops.corr_topk_ok(k)]
 
-    counts = {}
-    for name, fn in arms.items():                # warm-up of every arm, and the iteration count of its window
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-    samples = {name: [] for name in arms}
-    for _ in range(args.rounds):                 # alternating: one window of every arm per round
-        for name, fn in arms.items():
-            samples[name].append(_time(fn, counts[name]))
+    counts = benchlib.window_counts(arms, args.window, args.warmup)
+    samples = benchlib.alternating(arms, counts, args.rounds)
     med = {name: statistics.median(v) for name, v in samples.items()}
-    peaks = {"k36a": _peak(lambda: match(True, 1))}
+    peaks = {"k36a": benchlib.peak_bytes(lambda: match(True, 1))}
     for k in KS:
-        peaks[f"k39a {k}"] = _peak(lambda: match(True, k))
-        peaks[f"materialise+k39b {k}"] = _peak(lambda: match(False, k))
-        peaks[f"parent {k}"] = _peak(lambda: parent(k))
+        peaks[f"k39a {k}"] = benchlib.peak_bytes(lambda: match(True, k))
+        peaks[f"materialise+k39b {k}"] = benchlib.peak_bytes(lambda: match(False, k))
+        peaks[f"parent {k}"] = benchlib.peak_bytes(lambda: parent(k))
     # the fused and the materialised route agree on what they return (the picks may differ where two logits are closer than the kernels' error)
     a, b = match(True, 8), match(False, 8)
     parity = (float((a.index == b.index).float().mean()), float((a.logit - b.logit).abs().max()), float((a.lse - b.lse).abs().max()))
@@ -156,18 +109,13 @@ def main():
     lines.append("# rule: a k at which k39a is slower than materialise+k39b at this shape leaves ops.corr_topk_ok — "
                  + (f"k = {slower} must leave it" if slower else "none is: every fused instantiation stays"))
     lines.append(f"# fused against materialised route at k = 8: equal indices {parity[0]:.6f}, max |logit diff| {parity[1]:.3e}, max |lse diff| {parity[2]:.3e}")
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; the budget at 2 waves per SIMD is 256 VGPRs + AGPRs)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:12s} VGPRs {v:3d}  AGPRs {a:3d}  scratch {s} B/lane  waves/SIMD {o}" for name, v, a, s, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -15,10 +15,11 @@ Arms, all timed with device events inside ONE process, alternating round by roun
 import argparse
 import math
 import os
-import statistics
 import sys
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -27,39 +28,12 @@ INV_T = 100.0
 ITERS = 5
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del out
-    return peak
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k50_match_transport_bench.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k50_match_transport_bench.txt"))
     ap.add_argument("--shape", default="8x64", help="B x grid side")
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("match_transport_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("match_transport_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("match_transport_bench")
     from cocosnet_amd import ops
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_transport
     dev = torch.device("cuda", 0)
@@ -105,33 +79,20 @@ def main():
                 "(d) correspondence_transport": lambda: correspondence_transport(theta, phi, cfg, 1.0 / INV_T, iters=ITERS),
                 "(e) materialised iters=5": materialised}
         del ref
-        counts, peaks = {}, {}
-        for name, fn in arms.items():            # warm-up of every arm, and the iteration count of its window
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-            counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-            peaks[name] = _peak(fn)
-        samples = {name: [] for name in arms}
-        for _ in range(args.rounds):                 # alternating: one window of every arm per round
-            for name, fn in arms.items():
-                samples[name].append(_time(fn, counts[name]))
-    med = {name: statistics.median(v) for name, v in samples.items()}
-    for name in arms:
-        v = samples[name]
-        lines.append(f"{name:30s} {med[name]:9.4f} ms  ({min(v):.4f} .. {max(v):.4f}; spread (max - min) / median = "
-                     f"{(max(v) - min(v)) / med[name]:.4f}; {counts[name]} calls per window)  peak {peaks[name] / 2 ** 20:8.1f} MiB")
+        counts = benchlib.window_counts(arms, args.window, args.warmup)
+        peaks = {name: benchlib.peak_bytes(fn) for name, fn in arms.items()}
+        samples = benchlib.alternating(arms, counts, args.rounds)
+    stats = {name: benchlib.summary(v) for name, v in samples.items()}
+    med = {name: s.median for name, s in stats.items()}
+    for name, s in stats.items():
+        lines.append(f"{name:30s} {s.median:9.4f} ms  ({s.min:.4f} .. {s.max:.4f}; spread (max - min) / median = "
+                     f"{s.spread:.4f}; {counts[name]} calls per window)  peak {peaks[name] / 2 ** 20:8.1f} MiB")
     flops = 2.0 * B * N * N * 256
     lines.append(f"half-step: {flops / med['(a) half-step'] / 1e9:.0f} TFLOP/s of useful work; (a) / (b) = "
                  f"{med['(a) half-step'] / med['(b) unbiased readout']:.4f}; (c) / 11 (a) = "
                  f"{med['(c) corr_sinkhorn iters=5'] / (11 * med['(a) half-step']):.4f}; (e) / (c) = "
                  f"{med['(e) materialised iters=5'] / med['(c) corr_sinkhorn iters=5']:.2f}")
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,8 @@ import sys
 
 import torch
 
+import benchlib
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cocosnet_amd import ops, spade  # noqa: E402
 
@@ -43,19 +45,11 @@ class _Traffic:
         ops.norm_spade_apply, ops.norm_spade_bwd_apply = self._apply, self._bwd_apply
 
 
-def _time(step, warmup, iters, reps):
+def _timed_runs(step, warmup, iters, reps):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    runs = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        runs.append(e0.elapsed_time(e1) / iters)
+    runs = [benchlib.time_calls(step, iters) for _ in range(reps)]
     return statistics.median(runs), runs
 
 
@@ -65,7 +59,7 @@ def _measure(name, step, warmup, iters, reps):
         spade.NORM_FUSED = fused
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
-        ms, runs = _time(step, warmup, iters, reps)
+        ms, runs = _timed_runs(step, warmup, iters, reps)
         peak = torch.cuda.max_memory_allocated() / 2**30
         key = "fused" if fused else "module+K17"
         res.setdefault(key, {"ms": [], "runs": [], "peak_GiB": peak})

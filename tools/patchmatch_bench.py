@@ -18,13 +18,12 @@ theta / phi of a randomly initialised network and on a planted translation plus 
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -33,34 +32,16 @@ DOWN, NC, INV_T, K = 4, 151, 100.0, 4
 SCHEDULE = (1, 2, 1, 1, 2, 1)      # recall is reported for every prefix of this list of strides
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of patchmatch_f16x3.hip from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
+    usage = benchlib.resource_usage("patchmatch_f16x3.hip")
+    if usage is None:
         return None
-    with tempfile.TemporaryDirectory(prefix="cocos_k43_") as tmp:
-        unit = "patchmatch_f16x3.hip"
-        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
     rows = []
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-        get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-        inst = re.search(r"kernelILi(\d+)E", name)
-        rows.append((f"patchmatch_step_kernel<{inst.group(1) if inst else '?'}>", get(r" VGPRs"), get("AGPRs"), get("ScratchSize"),
-                     get("Occupancy")))
+    for u in usage:
+        inst = re.search(r"kernelILi(\d+)E", u.name)
+        rows.append((f"patchmatch_step_kernel<{inst.group(1) if inst else '?'}>", u.vgprs, u.agprs, u.scratch, u.occupancy))
     return rows
 
 
@@ -100,16 +81,10 @@ def recall_lines(tag, theta, phi, ops, hot_path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k43_patchmatch.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k43_patchmatch.txt"))
     ap.add_argument("--shapes", default="8x64,1x128,1x256", help="comma-separated B x grid side")
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("patchmatch_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("patchmatch_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("patchmatch_bench")
     from cocosnet_amd import correspondence as cc
     from cocosnet_amd import hot_path, ops
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_sparse
@@ -166,18 +141,12 @@ def main():
                 "sparse patchmatch": lambda: sparse("patchmatch")}
         counts = {}
         try:
-            for name, fn in arms.items():            # warm-up of every arm, and the iteration count of its window
-                for _ in range(args.warmup):
-                    fn()
-                torch.cuda.synchronize()
-                counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
+            for name, fn in arms.items():            # one arm at a time: a refusal below names its arm
+                counts.update(benchlib.window_counts({name: fn}, args.window, args.warmup))
         except (ValueError, ops._lib.CocosHipError) as e:      # a shape one of the routes refuses: said, not timed
             lines.append(f"{name}: refused at this shape: {e}")
             continue
-        samples = {name: [] for name in arms}
-        for _ in range(args.rounds):                 # alternating: one window of every arm per round
-            for name, fn in arms.items():
-                samples[name].append(_time(fn, counts[name]))
+        samples = benchlib.alternating(arms, counts, args.rounds)
         med = {name: statistics.median(v) for name, v in samples.items()}
         for name in arms:
             v = samples[name]
@@ -202,18 +171,13 @@ def main():
         lines += recall_lines("theta / phi of a randomly initialised network (ade20k options, 256 x 256 crop)", theta_raw.raw(), phi_raw.raw(),
                               ops, hot_path)
 
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:28s} VGPRs {v:3d}  AGPRs {a:3d}  scratch {s} B/lane  waves/SIMD {o}" for name, v, a, s, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

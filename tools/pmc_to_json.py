@@ -1,4 +1,4 @@
-"""rocprofv3 --pmc CSVs (one pass per counter set, see tools/profile_round.sh) -> per-kernel JSON with the
+"""rocprofv3 --pmc CSVs (one pass per counter set, see tools/final_artifacts.sh) -> per-kernel JSON with the
 gfx950 corrections of MI355X_MICROARCH.md applied:
   * GRBM_GUI_ACTIVE is summed over the 8 XCDs            -> cycles per XCD = value / 8
   * SQ_VALU_MFMA_BUSY_CYCLES is summed over 1024 SIMDs   -> busy cycles per SIMD = value / 1024

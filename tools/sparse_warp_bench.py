@@ -16,13 +16,12 @@ plus the peak memory above the inputs of both routes and, when hipcc is at hand,
 import argparse
 import os
 import re
-import shutil
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
+
+import benchlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -31,56 +30,20 @@ B, H, W, DOWN, NC, INV_T = 8, 64, 64, 4, 151, 100.0
 KS = (1, 2, 4, 8)
 
 
-def _time(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def _peak(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base
-
-
-def register_table():
+def register_rows():
     """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of sparse_warp_f16x3.hip from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
-    from cocosnet_amd import build
-    hipcc = next((c for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
+    usage = benchlib.resource_usage("sparse_warp_f16x3.hip")
+    if usage is None:
         return None
-    with tempfile.TemporaryDirectory(prefix="cocos_k42_") as tmp:
-        unit = "sparse_warp_f16x3.hip"
-        cmd = [hipcc, *build.HIP_FLAGS, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-               os.path.join(build.CSRC_DIR, unit), "-o", os.path.join(tmp, unit + ".o")]
-        text = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
-    rows = []
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)LDS Size", text, flags=re.S):
-        get = lambda what: int(re.search(what + r"[^:\n]*: (\d+)", body).group(1))
-        rows.append((re.search(r"\d+([a-z_0-9]+_kernel)", name).group(1), get(r" VGPRs"), get("AGPRs"), get("ScratchSize"), get("Occupancy")))
-    return rows
+    return [(re.search(r"\d+([a-z_0-9]+_kernel)", u.name).group(1), u.vgprs, u.agprs, u.scratch, u.occupancy) for u in usage]
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "k42_sparse_warp.txt"))
-    ap.add_argument("--rounds", type=int, default=21)
-    ap.add_argument("--window", type=float, default=0.05, help="seconds of work per timed window")
-    ap.add_argument("--warmup", type=int, default=3)
+    benchlib.common_args(ap, os.path.join("profiles", "k42_sparse_warp.txt"))
     args = ap.parse_args()
-    if args.rounds < 20:
-        raise SystemExit("sparse_warp_bench: the medians are over at least 20 rounds")
-    if not torch.cuda.is_available():
-        raise SystemExit("sparse_warp_bench: no GPU visible (a timing needs the device; there is no fallback)")
+    benchlib.require_gpu("sparse_warp_bench")
     from cocosnet_amd import _lib, ops
     from cocosnet_amd.hot_path import HotPathConfig, correspondence_hot_path, correspondence_sparse
     dev = torch.device("cuda", 0)
@@ -132,22 +95,14 @@ def main():
         arms[f"sparse {k}"] = lambda k=k: sparse(k)
     arms.update(key_arms)
 
-    counts = {}
-    for name, fn in arms.items():                # warm-up of every arm, and the iteration count of its window
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize()
-        counts[name] = max(2, int(args.window * 1e3 / max(_time(fn, 2), 1e-3)))
-    samples = {name: [] for name in arms}
-    for _ in range(args.rounds):                 # alternating: one window of every arm per round
-        for name, fn in arms.items():
-            samples[name].append(_time(fn, counts[name]))
+    counts = benchlib.window_counts(arms, args.window, args.warmup)
+    samples = benchlib.alternating(arms, counts, args.rounds)
     med = {name: statistics.median(v) for name, v in samples.items()}
     theta.grad = phi.grad = None
-    peaks = {"dense": _peak(dense)}
+    peaks = {"dense": benchlib.peak_bytes(dense)}
     for k in KS:
         theta.grad = phi.grad = None
-        peaks[f"sparse {k}"] = _peak(lambda: sparse(k))
+        peaks[f"sparse {k}"] = benchlib.peak_bytes(lambda: sparse(k))
 
     lines = [f"# tools/sparse_warp_bench.py on {torch.cuda.get_device_name(0)}: B = {B}, {H} x {W} grid (HW = {N}), match_kernel 1, PONO_C, "
              f"warp_mask_losstype direct (Cv = {3 + NC}); one HW x HW fp32 matrix is {B * N * N * 4 / 2**20:.0f} MiB",
@@ -163,18 +118,13 @@ def main():
         lines.append(f"k = {k}: sparse / dense = {med[f'sparse {k}'] / med['dense']:.3f}   peak sparse / dense = "
                      f"{peaks[f'sparse {k}'] / peaks['dense']:.4f}   key kernel hub / topk = "
                      f"{med[f'key kernel hub {k}'] / med[f'key kernel topk {k}']:.2f}")
-    table = register_table()
+    table = register_rows()
     lines.append("# registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)")
     if table is None:
         lines.append("(no hipcc on this host)")
     else:
         lines += [f"{name:32s} VGPRs {v:3d}  AGPRs {a:3d}  scratch {s} B/lane  waves/SIMD {o}" for name, v, a, s, o in table]
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write(text)
-    print("wrote", args.out)
+    benchlib.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,8 @@ import sys
 
 import torch
 
+import benchlib
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -39,16 +41,6 @@ def _set(arm):
 def _call(net, x):
     """the five features; with every layer, p5 (the deepest key) is computed too and dropped"""
     return net(x, KEYS + ["p5"])[:5] if _ALL[0] else net(x, KEYS)
-
-
-def _timed(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
 
 
 def main():
@@ -96,17 +88,12 @@ def main():
     for _ in range(a.rounds):
         for arm in ARMS:
             _set(arm)
-            res[arm]["step_ms"].append(_timed(step, a.iters))
-            res[arm]["fwd_only_ms"].append(_timed(fwd_only, a.iters))
-            res[arm]["fwd_bwd_ms"].append(_timed(fwd_bwd, a.iters))
+            res[arm]["step_ms"].append(benchlib.time_calls(step, a.iters))
+            res[arm]["fwd_only_ms"].append(benchlib.time_calls(fwd_only, a.iters))
+            res[arm]["fwd_bwd_ms"].append(benchlib.time_calls(fwd_bwd, a.iters))
     for arm in ARMS:
         _set(arm)
-        torch.cuda.synchronize()
-        base = torch.cuda.memory_allocated()
-        torch.cuda.reset_peak_memory_stats()
-        step()
-        torch.cuda.synchronize()
-        res[arm]["peak_mib"] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+        res[arm]["peak_mib"] = benchlib.peak_bytes(step) / 2 ** 20
         for k in ("step_ms", "fwd_only_ms", "fwd_bwd_ms"):
             res[arm][k + "_median"] = statistics.median(res[arm][k])
     same = {}

@@ -8,11 +8,12 @@ Reports per flag set and arm: ms per step (median of the rounds), the spread of 
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
 import torch
+
+import benchlib
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cocosnet_amd import ops                                                     # noqa: E402
@@ -88,12 +89,13 @@ def main():
                 ops.WARP_HEAD_MODES = modes
                 times[modes].append(window(step, a.window))
         ops.WARP_HEAD_MODES = True
-        med = {m: statistics.median(v) for m, v in times.items()}
+        stats = {m: benchlib.summary(v) for m, v in times.items()}
+        med = {m: s.median for m, s in stats.items()}
         res[name] = {
             "B": SETS[name][1], "grid": SETS[name][2],
             "framework_route_ms": round(med[False], 4), "new_route_ms": round(med[True], 4),
             "difference_ms": round(med[True] - med[False], 4),
-            "spread_ms": {("new" if m else "framework"): round(max(v) - min(v), 4) for m, v in times.items()},
+            "spread_ms": {("new" if m else "framework"): round(s.max - s.min, 4) for m, s in stats.items()},
             "peak_MiB": {("new" if m else "framework"): round(p / 2 ** 20, 1) for m, p in peak.items()},
         }
         print(json.dumps({name: res[name]}), flush=True)
