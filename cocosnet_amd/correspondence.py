@@ -24,9 +24,10 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_scope, _sparse_search,
-                       _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_hot_path, correspondence_match,
-                       correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_transport)
+from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_box3_scope, _sparse_scope,
+                       _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_hot_path,
+                       correspondence_match, correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_sparse_box3,
+                       correspondence_transport)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -459,6 +460,23 @@ class NoVGGCorrespondence(NetworkBase):
             kw["transport"] = transport
         coor_out.update(correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, search=search,
                                               search_opts=search_opts, **kw))
+        return coor_out
+
+    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4):
+        """sparse_warp on the reference's default route, match_kernel 3 (K51, hot_path.correspondence_sparse_box3): per content position
+        the `topk` best exemplar positions are selected without gradient, as match(topk=topk) selects them, and a softmax over those k
+        box logits alone blends the pooled exemplar (and, under --warp_mask_losstype direct, the exemplar's labels), with gradients to
+        the whole network through theta and phi and nothing HWxHW kept for the backward.  Returns sparse_warp's dictionary: {warp_out
+        [B,3,H,W], warp_mask [B,nc,h,w] (direct), match_index [B,k,h,w] int64, match_weight [B,k,h,w]} (+ loss_novgg_featpair where
+        project() makes it).  Scope: match_kernel 3 with PONO_C on the plain flag set; everything else raises ValueError before the
+        network runs (no fall-back).  forward(), match() and sparse_warp() are unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _sparse_box3_scope("sparse_warp_box3", cfg, topk, False, self.inter_channels)      # refused before the network runs
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("sparse_warp_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        coor_out = {}
+        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        coor_out.update(correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk))
         return coor_out
 
     def flow_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, radius=1, refine_temperature=None):

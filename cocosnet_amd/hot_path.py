@@ -632,14 +632,16 @@ _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused ma
           "restrict": ": restrict runs on the fused match_kernel 1 route only",
           "sparse": " (the sparse warp runs on the fused match_kernel 1 route)",
           "nll": " (the loss runs on the fused match_kernel 1 route)",
-          "transport": " (transport runs on the fused match_kernel 1 route)"}
+          "transport": " (transport runs on the fused match_kernel 1 route)",
+          "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)"}
 
 
-def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool):
-    """ValueError for a flag set off the fused match_kernel-1 route, in this order: match_kernel, PONO_C, with `plain_flags` the warp
-    modes and the cycle terms, COCOS_PRECISION, with `match_fused` the ops.MATCH_FUSED switch; every message ends in _ROUTE[member]"""
+def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool, kernel: int = 1):
+    """ValueError for a flag set off the fused match_kernel-1 route (`kernel` = 3: the match_kernel-3 route of K51), in this order:
+    match_kernel, PONO_C, with `plain_flags` the warp modes and the cycle terms, COCOS_PRECISION, with `match_fused` the
+    ops.MATCH_FUSED switch; every message ends in _ROUTE[member]"""
     route = _ROUTE[member]
-    if cfg.match_kernel != 1:
+    if cfg.match_kernel != kernel:
         raise ValueError(f"{name}: match_kernel {cfg.match_kernel} is out of scope{route}")
     if not cfg.PONO_C:
         raise ValueError(f"{name}: needs PONO_C{route}")
@@ -1180,6 +1182,70 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     if g is not None:
         out["potential_k"] = g.reshape(B, gh, gw)
         out["match_mass"] = torch.exp(f + row_lse + math.log(N)).reshape(B, fh, fw)
+    return out
+
+
+# ---- K51: the trainable k-sparse warp on the match_kernel-3 route -------------------------------------------------------------------
+def _sparse_box3_scope(name: str, cfg: HotPathConfig, topk, has_exemplar: bool = False, channels=None):
+    """ValueError for everything outside the scope of the match_kernel-3 sparse warp (K51: match_kernel 3, PONO_C, the plain flag set,
+    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels); checked before any tensor is looked at -> k"""
+    k = _topk_arg(name, topk)
+    _route_scope(name, cfg, "sparse_box3", plain_flags=True, match_fused=False, kernel=3)
+    if has_exemplar:
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the sparse warp differentiates phi)")
+    _route_channels(name, "sparse_box3", channels)
+    return k
+
+
+def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
+                               exemplar=None):
+    """correspondence_sparse on the reference's default route, match_kernel 3 (K51): per content position the `topk` best exemplar
+    positions are SELECTED without gradient exactly as correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk) selects
+    them (that function is called: K41 on the one x-box tensor T where ops.box3_fused_ok and ops.box3_topk_ok(topk) hold, the
+    materialised chain elsewhere; T is gone when it returns), then a softmax over those k box logits alone blends their values —
+    ops.box3_sparse_softmax_warp, with gradients to theta_raw and phi_raw through the pair logits and through the statistics of the
+    unfolded vectors (K12, made here with autograd).  Nothing HWxHW is kept for, or allocated in, the backward.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 (or ops.LazyProj1x1: the selection takes them as correspondence_match does, the warp
+    projects them).  Returns correspondence_sparse's dictionary: {warp_out [B,3,H,W], warp_mask [B,nc,h,w] when
+    cfg.warp_mask_losstype == "direct" (or show_warpmask), match_index [B,k,h,w] int64, match_weight [B,k,h,w] (no gradient)}.
+
+    Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, plain flag set (no warp_patch / warp_bilinear / cycle terms),
+    no prepared exemplar: everything else raises ValueError — there is no fall-back route.  CPU tensors raise CocosHipError.  Not built
+    on this route: restrict, transport, search="patchmatch", refine."""
+    name = "correspondence_sparse_box3"
+    k = _sparse_box3_scope(name, cfg, topk, exemplar is not None, theta_raw.shape[1])
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    down = cfg.down
+    _fused_width(name, theta_raw, phi_raw)
+    if k > Nk:
+        raise ValueError(f"{name}: topk={k} exceeds the {Nk} exemplar positions")
+    if tuple(ref_img.shape[2:]) != (gh * down, gw * down) or ref_img.shape[3] % 4 != 0:
+        raise ValueError(f"{name}: ref_img {tuple(ref_img.shape)} is not down={down} times the exemplar grid {(gh, gw)} (width a multiple of 4)")
+    if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
+    # lazy operands are projected first, with autograd (K0; the handle caches the projection, so this must not happen inside the
+    # selection's no_grad block); the selection still gets the operands as they came, which is what makes its candidates those of
+    # correspondence_match on the same arguments bit for bit
+    th, ph = _raw(theta_raw), _raw(phi_raw)
+    with torch.no_grad():
+        m = correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=k)      # selection: no gradient; its T is dropped inside
+        idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
+        del m
+        v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
+    kc = float(C * 9)
+    mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
+    nu, b = _unfold3_stats(ph, kc)
+    o, w = ops.box3_sparse_softmax_warp(th, ph, mu, a, nu, b, v, idx, 1.0 / temperature, return_weights=True)
+    n_ref = ref_img.shape[1]
+    y, o_mask = _split_channels(o, n_ref) if direct_mask else (o, None)
+    out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
+    if direct_mask:
+        out["warp_mask"] = o_mask.reshape(B, -1, fh, fw)
+    out["match_index"] = _rank_first(idx, (B, fh, fw), k)
+    out["match_weight"] = _rank_first(w, (B, fh, fw), k)
     return out
 
 

@@ -3576,6 +3576,112 @@ def unfold3_stats(x, k_unfolded: float, eps: float = NORM_EPS):
 
 
 # ------------------------------------------------------------------------------------------
+# K51  k-sparse correspondence warp with gradients on the match_kernel-3 route: K42's blend on the box logit of single pairs
+# ------------------------------------------------------------------------------------------
+class _Box3SparseSoftmaxWarp(torch.autograd.Function):
+    """K51.  Saved for the backward: the position-major copies of theta and phi, v^T, idx, w, c [B,Nq,k] and the four statistics —
+    nothing with an Nq x Nk extent.  Every gradient comes from the same launch whichever others are asked for (the same bits);
+    a launch that serves no needed gradient is skipped."""
+
+    @staticmethod
+    def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_t: float):
+        B, K, fh, fw = theta_raw.shape
+        gh, gw = phi_raw.shape[2:]
+        Nq, Nk, Cv, k = fh * fw, gh * gw, v.shape[1], idx.shape[2]
+        th_t, ph_t, vt = _transpose(theta_raw.reshape(B, K, Nq)), _transpose(phi_raw.reshape(B, K, Nk)), _transpose(v)
+        out_t = torch.empty((B, Nq, Cv), device=v.device, dtype=torch.float32)
+        w, c = (torch.empty((B, Nq, k), device=v.device, dtype=torch.float32) for _ in range(2))
+        _call("box3_sparse_softmax_warp_fwd", "cocos_box3_sparse_softmax_warp_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(),
+              a.data_ptr(), nu.data_ptr(), b.data_ptr(), vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), c.data_ptr(), B, K,
+              fh, fw, gh, gw, Cv, k, float(inv_t), _stream())
+        ctx.save_for_backward(th_t, ph_t, vt, idx, w, c, mu, a, nu, b)
+        ctx.cfg = (fh, fw, gh, gw, float(inv_t))
+        ctx.mark_non_differentiable(w)
+        return _transpose(out_t), w
+
+    @staticmethod
+    def backward(ctx, dout, _dw):
+        th_t, ph_t, vt, idx, w, c, mu, a, nu, b = ctx.saved_tensors
+        need_th, need_ph, need_mu, need_a, need_nu, need_b, need_v = ctx.needs_input_grad[:7]
+        fh, fw, gh, gw, inv_t = ctx.cfg
+        B, Nq, K = th_t.shape
+        Nk, Cv, k = ph_t.shape[1], vt.shape[2], idx.shape[2]
+        dout_t = _transpose(_chk(dout, "box3_sparse_softmax_warp: dout"))
+        new = lambda *shape: torch.empty(shape, device=dout.device, dtype=torch.float32)
+        dth = dph = dmu = da = dnu = db = dv = g = hb = None
+        if need_th or need_ph or need_mu or need_a or need_nu or need_b:
+            g = new(B, Nq, k)
+            hb = new(B, Nq, k) if need_b else None
+            dmu = new(B, Nq) if need_mu else None
+            da = new(B, Nq) if need_a else None
+            _call("box3_sparse_softmax_warp_bwd_pair", "cocos_box3_sparse_softmax_warp_bwd_pair", vt.data_ptr(), dout_t.data_ptr(),
+                  idx.data_ptr(), w.data_ptr(), c.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(), g.data_ptr(), _ptr(hb), _ptr(dmu),
+                  _ptr(da), B, K, fh, fw, gh, gw, Cv, k, inv_t, _stream())
+        if need_th:
+            dth_t = new(B, Nq, K)
+            _call("box3_sparse_softmax_warp_bwd_theta", "cocos_box3_sparse_softmax_warp_bwd_theta", ph_t.data_ptr(), idx.data_ptr(),
+                  g.data_ptr(), dth_t.data_ptr(), B, K, fh, fw, gh, gw, k, _stream())
+            dth = _transpose(dth_t).reshape(B, K, fh, fw)
+            del dth_t
+        if need_ph or need_v or need_nu or need_b:
+            entries, offsets = _inverse_index_table(idx, Nk)      # K42's table: one per backward, shared by the nine taps
+            dph_t = new(B, Nk, K) if need_ph else None
+            dv_t = new(B, Nk, Cv) if need_v else None
+            dnu = new(B, Nk) if need_nu else None
+            db = new(B, Nk) if need_b else None
+            _call("box3_sparse_softmax_warp_bwd_key", "cocos_box3_sparse_softmax_warp_bwd_key", th_t.data_ptr(), dout_t.data_ptr(), _ptr(g),
+                  _ptr(hb), w.data_ptr(), mu.data_ptr(), entries.data_ptr(), offsets.data_ptr(), _ptr(dph_t), _ptr(dv_t), _ptr(dnu),
+                  _ptr(db), B, K, fh, fw, gh, gw, Cv, k, _stream())
+            if need_ph:
+                dph = _transpose(dph_t).reshape(B, K, gh, gw)
+                del dph_t
+            if need_v:
+                dv = _transpose(dv_t)
+        return dth, dph, dmu, da, dnu, db, dv, None, None
+
+
+def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_temperature: float, return_weights: bool = False):
+    """out [B,Cv,fh*fw] = sum_r w[b,p,r] * v[b,:,idx[b,p,r]] with w = softmax over r of the match_kernel-3 logit of the pair
+    (p, idx[b,p,r]): z[p,q] = inv_temperature * a_p * b_q * (R[p,q] - 9*256 * mu_p * nu_q), R the sum over the nine taps d of
+    <theta_raw[:,p+d], phi_raw[:,q+d]> where both p+d and q+d lie inside their grids (box3_logits' value — F.unfold(3, padding=1),
+    centre, normalise, dot — for one pair): attention over the k keys per query that box3_topk selected (K51), with gradients for
+    theta_raw, phi_raw, mu, a, nu, b and v (each computed only when needed; idx is data).  theta_raw [B,256,fh,fw], phi_raw
+    [B,256,gh,gw] fp32, any grids, equal or not; (mu, a) [B,fh*fw] and (nu, b) [B,gh*gw] as unfold3_stats returns them for theta_raw
+    and phi_raw (made by it from tensors that require a gradient, they carry the statistics' share of the gradient back); v
+    [B,Cv,gh*gw] fp32; idx [B,fh*fw,k] int32 / int64 with 1 <= k <= MATCH_TOPK_MAX, k <= gh*gw — any values: repeats inside a row are
+    legal, values outside [0, gh*gw) are clamped into it.  Nothing Nq x Nk is allocated, forward or backward; the gradients are
+    gathered in a fixed order (no atomics: bitwise reproducible).  `return_weights`: also return w [B,fh*fw,k] (no gradient)."""
+    name = "box3_sparse_softmax_warp"
+    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: idx must be an int32 or int64 tensor, got {idx.dtype if torch.is_tensor(idx) else type(idx).__name__}")
+    if theta_raw.dim() != 4 or phi_raw.dim() != 4 or v.dim() != 3 or idx.dim() != 3:
+        raise ValueError(f"{name}: expected theta_raw [B,256,fh,fw], phi_raw [B,256,gh,gw], v [B,Cv,gh*gw], idx [B,fh*fw,k]; got "
+                         f"{tuple(theta_raw.shape)}, {tuple(phi_raw.shape)}, {tuple(v.shape)}, {tuple(idx.shape)}")
+    B, K, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    Nq, Nk = fh * fw, gh * gw
+    if (phi_raw.shape[:2] != (B, K) or Nq < 1 or Nk < 1 or v.shape[0] != B or v.shape[2] != Nk or v.shape[1] < 1
+            or idx.shape[:2] != (B, Nq)):
+        raise ValueError(f"{name}: shape mismatch theta_raw{tuple(theta_raw.shape)} phi_raw{tuple(phi_raw.shape)} v{tuple(v.shape)} "
+                         f"idx{tuple(idx.shape)}")
+    if K != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
+    _check_topk(name, int(idx.shape[2]), Nk)
+    stats = ((mu, "mu", Nq), (a, "a", Nq), (nu, "nu", Nk), (b, "b", Nk))
+    for t, what, n in stats:
+        if tuple(t.shape) != (B, n):
+            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {(B, n)} (ops.unfold3_stats of "
+                             f"{'theta_raw' if what in ('mu', 'a') else 'phi_raw'})")
+    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + tuple((t, what) for t, what, _ in stats) + ((v, "v"), (idx, "idx")), False)
+    theta_raw, phi_raw, v = (_chk(t, f"{name}: {what}") for t, what in ((theta_raw, "theta_raw"), (phi_raw, "phi_raw"), (v, "v")))
+    mu, a, nu, b = (_chk(t, f"{name}: {what}") for t, what, _ in stats)
+    with torch.no_grad():
+        idx = idx.clamp(0, Nk - 1).to(torch.int32).contiguous()
+    out, w = _Box3SparseSoftmaxWarp.apply(theta_raw, phi_raw, mu, a, nu, b, v, idx, float(inv_temperature))
+    return (out, w) if return_weights else out
+
+
+# ------------------------------------------------------------------------------------------
 # K7  softmax + warp from materialised key-major logits   (correspondence.py:307 + :318 ...)
 # ------------------------------------------------------------------------------------------
 class _LogitsSoftmaxWarp(torch.autograd.Function):

@@ -1388,6 +1388,51 @@ int cocos_sparse_softmax_warp_bwd_key_f16x3(const void* qh, const void* ql, cons
 int cocos_transpose_f32(const float* in, float* out, int B, int R, int C, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K51 k-sparse correspondence warp with gradients on the match_kernel-3 route (box3_sparse_warp.hip): K42's blend on the logit of the
+ *     3x3-unfolded, centred, normalised vectors, taken for one pair.  Content grid fh x fw (Nq = fh fw, position p = py fw + px),
+ *     exemplar grid gh x gw (Nk = gh gw), any sizes >= 1, equal or not; taps d in {-1,0,1}^2:
+ *         R[p,q] = sum_d [p+d inside the content grid] [q+d inside the exemplar grid] <theta[:,p+d], phi[:,q+d]>
+ *         z[p,q] = inv_temperature a_p b_q (R[p,q] - kc mu_p nu_q),  kc = 9 * 256,
+ *         w = softmax over r of z[p, j_r],  j_r = idx[b,p,r],  out[b,:,p] = sum_r w_r v[b,:,j_r]
+ *     with (mu, a) [B,Nq] and (nu, b) [B,Nk] the statistics cocos_unfold3_stats_fwd returns for theta and phi (cocos_box3_logits_fwd's
+ *     logit).  "Inside" is decided on the 2-D coordinates, never on the flat index.  Nothing Nq x Nk exists.
+ *     Common to the four kernels: th_t [B,Nq,256], ph_t [B,Nk,256] are theta / phi as fp32 POSITION-major rows, 16-byte aligned, and so
+ *     is every other fp32 tensor with channels: v_t [B,Nk,Cv], out_t / dout_t [B,Nq,Cv], dth_t [B,Nq,256], dph_t [B,Nk,256], dv_t
+ *     [B,Nk,Cv] (cocos_transpose_f32 makes them from / turns them into the channel-major tensors); idx [B,Nq,k] int32, ANY values
+ *     (repeats inside a row are legal, values outside [0, Nk) are clamped into it).  fp32 arithmetic in a fixed order, no atomics:
+ *     results are bitwise reproducible.  Null pointers, dims < 1 (an empty grid), k outside 1..COCOS_MATCH_TOPK_MAX or above Nk:
+ *     COCOS_ERR_INVALID; K != 256, or B Nq k / B Nk at or above 2^31: COCOS_ERR_UNSUPPORTED — all before any HIP call.
+ *   cocos_box3_sparse_softmax_warp_fwd: one wave per query; writes out_t, w [B,Nq,k] and c [B,Nq,k] = R - kc mu_p nu_j.
+ *   cocos_box3_sparse_softmax_warp_bwd_pair: one wave per query; dw_r = <dout_t[p], v_t[j_r]>, dz_r = w_r (dw_r - sum_r' w_r' dw_r');
+ *       writes g [B,Nq,k] = dz inv_temperature a_p b_j (the coefficient on R) and, each unless null, hb [B,Nq,k] = dz inv_temperature
+ *       a_p c (the pair's share of db_j), dmu [B,Nq] = -kc sum_r g_r nu_j, da [B,Nq] = sum_r dz_r inv_temperature b_j c_r.
+ *   cocos_box3_sparse_softmax_warp_bwd_theta: one wave per content position m, a gather:
+ *       dth_t[m] = sum over d (raster order) with p = m - d in the content grid, over r ascending, of
+ *                  g[p,r] [j_{p,r} + d in the exemplar grid] phi[j_{p,r} + d];  a position nobody reaches gets zeros, written here.
+ *   cocos_box3_sparse_softmax_warp_bwd_key: one wave per exemplar position n, a gather over the INVERSE table of idx (entries, offsets:
+ *       as cocos_sparse_softmax_warp_bwd_key_f16x3 takes them):
+ *       dph_t[n] = sum over d (raster order) with q = n - d in the exemplar grid, over list(q) in table order, of
+ *                  g[p,r] [p + d in the content grid] theta[p + d];
+ *       and from list(n) alone dv_t[n] = sum w dout_t[p], dnu [B,Nk] = -kc sum g mu_p, db [B,Nk] = sum hb.  Each output may be null
+ *       (not all four), with the inputs only it reads: dph_t reads th_t, g; dv_t reads dout_t, w; dnu reads g, mu; db reads hb.  A key
+ *       nobody names gets zeros.  A key all queries name is one serial list of Nq entries, walked for up to nine taps.  Positions and
+ *       offsets are clamped into the tables.
+ * ------------------------------------------------------------------------------------- */
+int cocos_box3_sparse_softmax_warp_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu,
+                                       const float* b, const float* v_t, const int* idx, float* out_t, float* w, float* c, int B, int K,
+                                       int fh, int fw, int gh, int gw, int Cv, int k, float inv_temperature, cocos_stream_t stream);
+int cocos_box3_sparse_softmax_warp_bwd_pair(const float* v_t, const float* dout_t, const int* idx, const float* w, const float* c,
+                                            const float* a, const float* nu, const float* b, float* g, float* hb /* nullable */,
+                                            float* dmu /* nullable */, float* da /* nullable */, int B, int K, int fh, int fw, int gh,
+                                            int gw, int Cv, int k, float inv_temperature, cocos_stream_t stream);
+int cocos_box3_sparse_softmax_warp_bwd_theta(const float* ph_t, const int* idx, const float* g, float* dth_t, int B, int K, int fh, int fw,
+                                             int gh, int gw, int k, cocos_stream_t stream);
+int cocos_box3_sparse_softmax_warp_bwd_key(const float* th_t, const float* dout_t, const float* g, const float* hb, const float* w,
+                                           const float* mu, const int* entries, const int* offsets, float* dph_t /* nullable */,
+                                           float* dv_t /* nullable */, float* dnu /* nullable */, float* db /* nullable */, int B, int K,
+                                           int fh, int fw, int gh, int gw, int Cv, int k, cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K43 PatchMatch candidate search for the k-sparse warp (patchmatch_f16x3.hip): ONE Jacobi iteration per call — a second selector
  *     next to cocos_corr_topk_f16x3 whose work is O(Nq k (5 + radii)) dot products whatever Nk is (CoCosNet-v2's replacement of the
  *     dense scan).  Query grid hq x wq (Nq = hq wq, position i = y wq + x), key grid hk x wk (Nk = hk wk); operand planes, score
