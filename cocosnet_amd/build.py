@@ -65,10 +65,9 @@ HIP_SOURCES = [
     "weight_prepare_multi.hip",
     "reflect_pad.hip",
     "spectral_norm.hip",
-    "gather_patches.hip",
+    "gather_warp.hip",
     "corr_topk_f16x3.hip",
     "row_topk_lse.hip",
-    "gather_blend_patches.hip",
     "sparse_warp_f16x3.hip",
     "patchmatch_f16x3.hip",
     "match_refine_f16x3.hip",

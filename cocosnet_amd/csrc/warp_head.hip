@@ -267,11 +267,6 @@ __global__ __launch_bounds__(256) void warp_head_bwd_kernel(const float* __restr
 
 }  // namespace cocos
 
-// y [B, Ci, h*down, w*down] = nearest up-sampling of channels [0, Ci) of o [B, C, h, w] (Ci <= C; (w * down) % 4 == 0).
-extern "C" int cocos_warp_head_fwd(const float* o, float* y, int B, int Ci, int C, int h, int w, int down, cocos_stream_t stream) {
-    return cocos_warp_head_fwd_ex(o, y, nullptr, B, Ci, C, h, w, down, COCOS_WARP_HEAD_NEAREST, stream);
-}
-
 // The head forward in one of three modes (COCOS_WARP_HEAD_*).  y: nearest / bilinear up-sampling of channels [0, Ci) of o [B, C, h, w]
 // -> [B, Ci, h*down, w*down], or (patch) F.fold of those Ci = c * down^2 rows -> [B, c, h*down, w*down].  y_bi (nearest mode only,
 // optional): the bilinear up-sampling as well, from the same launch.
@@ -305,21 +300,12 @@ extern "C" int cocos_warp_head_fwd_ex(const float* o, float* y, float* y_bi, int
     return COCOS_OK;
 }
 
-// g_img [B, Ci, h*down, w*down] (d loss / d warp_out), g_mask [B, Cs, h, w] (d loss / d warp_mask), o [B, Ci+Cs, h, w] ->
-// dout [B, Ci+Cs, h, w], drow [B, h*w] = sum_c dout * o (fp64 accumulation), *amax_inout = max(*amax_inout, max|dout|)
-// (a cell holding a finite value >= 0).  w % 4 == 0; all tensors 16-byte aligned.
-extern "C" int cocos_warp_head_bwd(const float* g_img, const float* g_mask, const float* o, float* dout, float* drow,
-                                   float* amax_inout_dev, int B, int Ci, int Cs, int h, int w, int down, cocos_stream_t stream) {
-    using namespace cocos;
-    COCOS_REQUIRE((g_img || Ci == 0) && (g_mask || Cs == 0), COCOS_ERR_INVALID, "warp_head_bwd: null pointer");
-    return cocos_warp_head_bwd_ex(g_img, g_mask, nullptr, o, dout, drow, amax_inout_dev, B, Ci, Cs, h, w, down, COCOS_WARP_HEAD_NEAREST,
-                                  stream);
-}
-
-// The head backward in one of three modes: the adjoint of cocos_warp_head_fwd_ex's y (window sums | bilinear gather | un-fold) on
-// rows [0, Ci) of dout, plus g_y [B, Ci, h*w] when given (the image channels' second consumer); g_mask on rows [Ci, Ci+Cs); drow and
-// the amax cell as cocos_warp_head_bwd.  In patch mode g_img is [B, Ci / down^2, h*down, w*down].  g_img, g_mask and g_y may each be
-// NULL (a zero gradient); Cs may be 0.
+// The head backward in one of three modes: g_img [B, Ci, h*down, w*down] (d loss / d warp_out), g_mask [B, Cs, h, w] (d loss /
+// d warp_mask), o [B, Ci+Cs, h, w] -> dout [B, Ci+Cs, h, w], drow [B, h*w] = sum_c dout * o (fp64 accumulation), *amax_inout =
+// max(*amax_inout, max|dout|) (a cell holding a finite value >= 0).  Rows [0, Ci) of dout are the adjoint of cocos_warp_head_fwd_ex's
+// y (window sums | bilinear gather | un-fold), plus g_y [B, Ci, h*w] when given (the image channels' second consumer); rows
+// [Ci, Ci+Cs) are g_mask.  In patch mode g_img is [B, Ci / down^2, h*down, w*down].  g_img, g_mask and g_y may each be NULL (a zero
+// gradient); Cs may be 0.  w % 4 == 0; all tensors 16-byte aligned.
 extern "C" int cocos_warp_head_bwd_ex(const float* g_img, const float* g_mask, const float* g_y, const float* o, float* dout,
                                       float* drow, float* amax_inout_dev, int B, int Ci, int Cs, int h, int w, int down, int mode,
                                       cocos_stream_t stream) {

@@ -499,10 +499,7 @@ def correspondence_hot_path(theta_raw, phi_raw, ref_img, real_img, seg_map, ref_
     else:
         head = (direct_mask and not cfg.warp_patch and not cfg.warp_bilinear and not want_cycle
                 and not show_bi and ops.warp_head_ok(o_r1, n_ref, fh, fw, down) and n_ref < o_r1.shape[1])
-    if head and not modes:
-        out["warp_out"], out["warp_mask"] = ops.warp_head(o_r1, n_ref, fh, fw, down)
-        y = y_img = None          # (only the cycle terms read them: excluded above)
-    elif head:
+    if head:
         want_bi = show_bi and head_mode == "nearest"
         res = ops.warp_head(o_r1, n_ref, fh, fw, down, mode=head_mode, want_y=want_cycle, want_bi=want_bi)
         if show_bi:               # (bilinear / patch mode: warp_out is the side output already, :326-327)

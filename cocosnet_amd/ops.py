@@ -1026,14 +1026,21 @@ def row_argmax_lse(f: torch.Tensor):
     return idx, mx, lse
 
 
+def _gather_gate(name: str, img, idx):
+    """What the copy and the blend refuse alike before their shapes, in this order: img fp32 on the GPU, idx on the GPU and of an
+    integer type -> img detached and contiguous"""
+    img = _chk(img.detach(), f"{name}: img")
+    _gate(name, ((idx, "idx"),), False)
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise TypeError(f"{name}: idx must be an integer tensor, got {idx.dtype}")
+    return img
+
+
 def gather_patches(img: torch.Tensor, idx: torch.Tensor, h: int, w: int, down: int):
     """The hard warp (K36c): out [B,C,H,W] whose cell (y, x) of the h x w grid is the down x down patch of img at the cell idx[b, y*w+x]
     — a bitwise copy.  img [Be,C,H,W] fp32 with H == h*down, W == w*down and Be == B or 1 (one exemplar for all); idx [B,h*w] or
     [B,h,w], any integer type (values outside [0, h*w) are clamped into it)."""
-    img = _chk(img.detach(), "gather_patches: img")
-    _gate("gather_patches", ((idx, "idx"),), False)
-    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
-        raise TypeError(f"gather_patches: idx must be an integer tensor, got {idx.dtype}")
+    img = _gather_gate("gather_patches", img, idx)
     Be, C, H, W = img.shape
     B = idx.shape[0]
     if (H, W) != (h * down, w * down) or idx.numel() != B * h * w or Be not in (B, 1):
@@ -1477,10 +1484,7 @@ def gather_blend_patches(img: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, 
     img at the cell idx[b,r,y,x]), accumulated in fp32 in the order r = 0, 1, ... — with k = 1 and w = 1 gather_patches bit for bit.
     img [Be,C,H,W] fp32 with H == h*down, W == w_grid*down and Be == B or 1; idx [B,k,h,w_grid] (or [B,k,h*w_grid]), any integer
     type (values outside [0, h*w_grid) are clamped into it); w fp32 of idx's shape; 1 <= k <= MATCH_TOPK_MAX."""
-    img = _chk(img.detach(), "gather_blend_patches: img")
-    _gate("gather_blend_patches", ((idx, "idx"),), False)
-    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
-        raise TypeError(f"gather_blend_patches: idx must be an integer tensor, got {idx.dtype}")
+    img = _gather_gate("gather_blend_patches", img, idx)
     w = _chk(w.detach(), "gather_blend_patches: w")
     Be, C, H, W = img.shape
     B = idx.shape[0]
@@ -4127,53 +4131,17 @@ def upsample_nearest(x, scale: int):
 
 
 
-
-class _WarpHead(torch.autograd.Function):
-    """(warp_out, warp_mask) from the first row pass's output o [B,Ci+Cs,h*w] (correspondence.py:327, :334): nearest up-sampling
-    of the Ci image channels and a VIEW of the Cs mask channels.  Backward: ONE kernel (cocos_warp_head_bwd) writes d o from
-    the two loss gradients and leaves max|d o| and D = sum_c d o * o (fp64) for the K2 / K19 backward that consumes d o next —
-    round 5 ran cocos_upsample_nearest_bwd, cocos_concat2_amax and cocos_rowdot_f64 for these."""
-
-    @staticmethod
-    def forward(ctx, o, n_img: int, h: int, w: int, down: int):
-        o = _chk(o, "warp_head: o")
-        B, C, N = o.shape
-        y = torch.empty((B, n_img, h * down, w * down), device=o.device, dtype=torch.float32)
-        _call("upsample_nearest_fwd", "cocos_warp_head_fwd", o.data_ptr(), y.data_ptr(), B, n_img, C, h, w, down, _stream())
-        ctx.save_for_backward(o)
-        ctx.cfg = (int(n_img), int(h), int(w), int(down))
-        return y, o[:, n_img:].view(B, C - n_img, h, w)
-
-    @staticmethod
-    def backward(ctx, g_img, g_mask):
-        o, = ctx.saved_tensors
-        n_img, h, w, down = ctx.cfg
-        B, C, N = o.shape
-        if g_img is None:
-            g_img = torch.zeros((B, n_img, h * down, w * down), device=o.device, dtype=torch.float32)
-        if g_mask is None:
-            g_mask = torch.zeros((B, C - n_img, h, w), device=o.device, dtype=torch.float32)
-        g_img, g_mask = _chk(g_img, "warp_head: d warp_out"), _chk(g_mask, "warp_head: d warp_mask")
-        dout = torch.empty_like(o)
-        drow = torch.empty((B, N), device=o.device, dtype=torch.float32)
-        cell = _zero_cell(o.device)
-        _call("warp_head_bwd", "cocos_warp_head_bwd", g_img.data_ptr(), g_mask.data_ptr(), o.data_ptr(), dout.data_ptr(), drow.data_ptr(),
-              cell.data_ptr(), B, n_img, C - n_img, h, w, down, _stream())
-        if PRECISION == "f16x3":
-            _remember_amax(dout, cell)
-        _tls.known_rowdot = (weakref.ref(dout), dout._version, o.data_ptr(), drow)
-        return dout, None, None, None, None
-
-
 _HEAD_MODES = {m: _C["COCOS_WARP_HEAD_" + m.upper()] for m in ("nearest", "bilinear", "patch")}
 
 
 class _WarpHeadModes(torch.autograd.Function):
-    """_WarpHead for every flag set (K30): warp_out by nearest / bilinear up-sampling or as the fold of non-overlapping patches, the
-    mask channels (if any) as a view, optionally the image channels themselves as a view (`want_y`: the column pass's values under
-    --warp_cycle_w) and the bilinear side output of inference --show_corr (`want_bi`, nearest mode).  Backward: ONE kernel
-    (cocos_warp_head_bwd_ex) sums both gradients of the image channels — the adjoint of the up-sampling, as a fixed-order gather, and
-    d y — next to d warp_mask, and leaves max|d o| and D for the K2 / K19 backward as _WarpHead does."""
+    """The head of a row / column pass's output o [B,Ci+Cs,h*w] (correspondence.py:327, :334; K30: every flag set): warp_out by nearest /
+    bilinear up-sampling of the Ci image channels or as the fold of non-overlapping patches, the Cs mask channels (if any) as a VIEW,
+    optionally the image channels themselves as a view (`want_y`: the column pass's values under --warp_cycle_w) and the bilinear side
+    output of inference --show_corr (`want_bi`, nearest mode).  Backward: ONE kernel (cocos_warp_head_bwd_ex) sums both gradients of
+    the image channels — the adjoint of the up-sampling, as a fixed-order gather, and d y — next to d warp_mask (a gradient autograd
+    did not deliver is NULL: zero), and leaves max|d o| and D = sum_c d o * o (fp64) for the K2 / K19 backward that consumes d o next —
+    round 5 ran cocos_upsample_nearest_bwd, cocos_concat2_amax and cocos_rowdot_f64 for these."""
 
     @staticmethod
     def forward(ctx, o, n_img: int, h: int, w: int, down: int, mode: str, want_y: bool, want_bi: bool):
@@ -4221,13 +4189,11 @@ def warp_head_ok(o: torch.Tensor, n_img: int, h: int, w: int, down: int, mode: s
 
 
 def warp_head(o, n_img: int, h: int, w: int, down: int, mode: str = "nearest", want_y: bool = False, want_bi: bool = False):
-    """(warp_out, warp_mask or None[, y_view][, warp_out_bi]) of a row / column pass's output o [B,C,h*w]: see _WarpHead and
-    _WarpHeadModes.  warp_out is [B,n_img,h*down,w*down] (mode 'nearest' | 'bilinear') or the fold [B,n_img/down^2,h*down,w*down]
+    """(warp_out, warp_mask or None[, y_view][, warp_out_bi]) of a row / column pass's output o [B,C,h*w]: see _WarpHeadModes.
+    warp_out is [B,n_img,h*down,w*down] (mode 'nearest' | 'bilinear') or the fold [B,n_img/down^2,h*down,w*down]
     ('patch'); warp_mask [B,C-n_img,h,w] and y_view [B,n_img,h*w] are views of o."""
     if mode not in _HEAD_MODES:
         raise ValueError(f"warp_head: unknown mode {mode!r}")
-    if mode == "nearest" and not want_y and not want_bi and n_img < o.shape[1]:
-        return _WarpHead.apply(o, int(n_img), int(h), int(w), int(down))
     if want_bi and mode != "nearest":
         raise ValueError("warp_head: want_bi goes with mode='nearest' (the other modes' warp_out is the side output already)")
     res = _WarpHeadModes.apply(o, int(n_img), int(h), int(w), int(down), mode, bool(want_y), bool(want_bi))

@@ -556,26 +556,21 @@ int cocos_pono_spade_bwd_amax(const float* x, const float* gamma, const float* b
  * ------------------------------------------------------------------------------------- */
 int cocos_upsample_nearest_fwd(const float* x, float* y, int planes, int h, int w, int scale, cocos_stream_t stream);
 int cocos_upsample_nearest_bwd(const float* dy, float* dx, int planes, int h, int w, int scale, cocos_stream_t stream);
-/* The head of the first row pass (csrc/warp_head.hip; correspondence.py:327, :334 and their autograd).
- *   cocos_warp_head_fwd: y [B,Ci,h*down,w*down] = nearest up-sampling of channels [0,Ci) of o [B,C,h,w] ((w*down) % 4 == 0).
- *   cocos_warp_head_bwd: g_img [B,Ci,h*down,w*down] = d loss / d warp_out, g_mask [B,Cs,h,w] = d loss / d warp_mask,
- *       o [B,Ci+Cs,h,w] -> dout [B,Ci+Cs,h,w] (window sums | copy), drow [B,h*w] = sum_c dout * o accumulated in fp64 (the D of
- *       the softmax backward), *amax_inout = max(*amax_inout, max|dout|) — one pass instead of cocos_upsample_nearest_bwd +
- *       cocos_concat2_amax + cocos_rowdot_f64.  w % 4 == 0, tensors 16-byte aligned. */
-int cocos_warp_head_fwd(const float* o, float* y, int B, int Ci, int C, int h, int w, int down, cocos_stream_t stream);
-int cocos_warp_head_bwd(const float* g_img, const float* g_mask, const float* o, float* dout, float* drow, float* amax_inout_dev,
-                        int B, int Ci, int Cs, int h, int w, int down, cocos_stream_t stream);
-/* K30: the same head for --warp_bilinear and --warp_patch (:184-186, :321, :357) and for row / column passes without mask channels.
- *   mode = COCOS_WARP_HEAD_NEAREST   y = nearest up-sampling (cocos_warp_head_fwd / _bwd are this mode)
+/* The head of a row / column pass (csrc/warp_head.hip; correspondence.py:327, :334 and their autograd; K30: also --warp_bilinear and
+ * --warp_patch, :184-186, :321, :357, and passes without mask channels).
+ *   mode = COCOS_WARP_HEAD_NEAREST   y [B,Ci,h*down,w*down] = nearest up-sampling of channels [0,Ci) of o [B,C,h,w]
  *          COCOS_WARP_HEAD_BILINEAR  y = F.interpolate(o[:, :Ci], scale_factor=down, mode="bilinear", align_corners=False); the
  *                                    backward is its adjoint as a gather in a fixed order (no atomics: reproducible bit for bit)
  *          COCOS_WARP_HEAD_PATCH     y [B,Ci/down^2,h*down,w*down] = F.fold(o[:, :Ci], (h*down, w*down), down, stride=down), a copy:
  *                                    y[b,c,yy*down+i,xx*down+j] = o[b, c*down^2 + i*down + j, yy*w + xx]; Ci % down^2 == 0
  *   cocos_warp_head_fwd_ex: y_bi (optional, nearest mode only) receives the bilinear up-sampling from the same launch (the inference
  *       --show_corr pair).  Ci <= C, (w*down) % 4 == 0, outputs 16-byte aligned.
- *   cocos_warp_head_bwd_ex: as cocos_warp_head_bwd, and g_y [B,Ci,h*w] (optional) is added to rows [0,Ci) of dout before drow and
- *       max|dout| are taken — the image channels' second gradient when they are also the column pass's values (:353-362).  g_img,
- *       g_mask and g_y may each be NULL (a zero gradient), Cs may be 0.  w % 4 == 0, tensors 16-byte aligned. */
+ *   cocos_warp_head_bwd_ex: g_img [B,Ci,h*down,w*down] = d loss / d warp_out, g_mask [B,Cs,h,w] = d loss / d warp_mask,
+ *       o [B,Ci+Cs,h,w] -> dout [B,Ci+Cs,h,w] (the adjoint of y | copy), drow [B,h*w] = sum_c dout * o accumulated in fp64 (the D of
+ *       the softmax backward), *amax_inout = max(*amax_inout, max|dout|) — one pass instead of cocos_upsample_nearest_bwd +
+ *       cocos_concat2_amax + cocos_rowdot_f64.  g_y [B,Ci,h*w] (optional) is added to rows [0,Ci) of dout before drow and max|dout|
+ *       are taken — the image channels' second gradient when they are also the column pass's values (:353-362).  g_img, g_mask and
+ *       g_y may each be NULL (a zero gradient), Cs may be 0.  w % 4 == 0, tensors 16-byte aligned. */
 #define COCOS_WARP_HEAD_NEAREST 0
 #define COCOS_WARP_HEAD_BILINEAR 1
 #define COCOS_WARP_HEAD_PATCH 2
@@ -1213,7 +1208,7 @@ int cocos_label_conv3x3_bwd(const int* index, const float* dy, const float* y_sa
  *   cocos_row_argmax_lse (K36b, row_topk_lse.hip at K = 1): the same three results from a materialised matrix logits [B,Nq,Nk] in one
  *       sweep (16-byte loads when Nk % 4 == 0 and the base is 16-byte aligned): max is an element of the row, bit for bit;
  *       same tie and range rules.  Any Nq, Nk >= 1.  For every route that holds its logits in memory anyway.
- *   cocos_gather_patches (K36c, gather_patches.hip): the hard warp at full resolution, a bitwise copy:
+ *   cocos_gather_patches (K36c, gather_warp.hip): the hard warp at full resolution, a bitwise copy:
  *         out[b,c,y down+dy,x down+dx] = img[b_e,c,(j / w) down+dy,(j % w) down+dx],  j = idx[b, y w + x],  h = H / down, w = W / down
  *       img [Be,C,H,W] with img_batch_stride = C H W (b_e = b) or 0 (Be = 1: b_e = 0; anything else is COCOS_ERR_INVALID),
  *       idx [B,h w] int32, out [B,C,H,W].  An index outside [0, h w) is clamped into it.  H, W multiples of down
@@ -1240,7 +1235,7 @@ int cocos_gather_patches(const float* img, const int* idx, float* out, int B, in
  *   cocos_row_topk_lse (K39b, row_topk_lse.hip, K = 1, 2, 4, 8): the same from a materialised matrix logits [B,Nq,Nk] in one sweep; val holds
  *       elements of the row, bit for bit; idx[..,0], val[..,0], lse are cocos_row_argmax_lse's outputs bit for bit.  Any Nq >= 1,
  *       any Nk >= k.
- *   cocos_gather_blend_patches (K39c, gather_blend_patches.hip): the k-sparse warp at full resolution,
+ *   cocos_gather_blend_patches (K39c, gather_warp.hip): the k-sparse warp at full resolution,
  *         out[b,c,y down+dy,x down+dx] = sum_r w[b,r,y,x] img[b_e,c,(j_r / wg) down+dy,(j_r % wg) down+dx],  j_r = idx[b,r,y,x],
  *       hg = H / down, wg = W / down; idx [B,k,hg,wg] int32 (clamped into [0, hg wg)), w [B,k,hg,wg] fp32, img / out /
  *       img_batch_stride as cocos_gather_patches.  fp32, fixed order: acc = w_0 p_0, then acc = fma(w_r, p_r, acc), r = 1 .. k-1;
@@ -1460,7 +1455,7 @@ int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const void* kh, 
                                 int radius0, int seed, int iteration, float inv_temperature, float operand_scale, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K44 Sub-cell match refinement (match_refine_f16x3.hip, gather_patches.hip): a soft-argmax over the window of keys around a hard
+ * K44 Sub-cell match refinement (match_refine_f16x3.hip, gather_warp.hip): a soft-argmax over the window of keys around a hard
  *     match, and the full-resolution warp sampled at the refined position.
  *   cocos_match_refine_f16x3: qh, ql [B,Nq,256], kh, kl [B,Nk,256] operand planes and score arithmetic as K42 / K43 (the logit
  *     cocos_sparse_softmax_warp_fwd_f16x3 forms for the same pair, bit for bit); idx [B,Nq] int32 the centre key of every query,
@@ -1489,7 +1484,7 @@ int cocos_gather_patches_subcell(const float* img, const int* idx, const float* 
                                  int wk, int down, long long img_batch_stride, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K46 Gradients of the sub-cell refinement (match_refine_bwd_f16x3.hip, gather_patches.hip): K44's offset becomes trainable — the
+ * K46 Gradients of the sub-cell refinement (match_refine_bwd_f16x3.hip, gather_warp.hip): K44's offset becomes trainable — the
  *     backward of cocos_match_refine_f16x3 to the two operands and of cocos_gather_patches_subcell to the offset.
  *     Common to the two match kernels: planes, idx, grids, radius and scales as cocos_match_refine_f16x3; W = (2 radius + 1)^2 window
  *     slots per query, slot s = (dy + radius) (2 radius + 1) + (dx + radius); ds [B,Nq,W] fp32; dq_t [B,Nq,256], dk_t [B,Nk,256]

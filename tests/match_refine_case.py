@@ -1,5 +1,5 @@
 """A numpy fp64 restatement of K44 for the tests (cocosnet_amd/csrc/match_refine_f16x3.hip and gather_patches_subcell_kernel of
-gather_patches.hip): which keys are in a query's window, the window softmax and its expected offset, and the bilinear gather at the
+gather_warp.hip): which keys are in a query's window, the window softmax and its expected offset, and the bilinear gather at the
 sub-cell position.
 
     window(j, r)    the keys (yk + dy, xk + dx), |dy|, |dx| <= r, inside the hk x wk grid, around j clamped into [0, hk wk);

@@ -123,7 +123,7 @@ HOT = {
     "mk1_raw_no_pono": (1, 8, 16, dict(warp_mask_losstype="direct", PONO_C=False), PAIR_NAMES, "raw", {}),
     "mk3_raw": (3, 4, 64, DIRECT, PAIR_NAMES, "raw", {}),
     "mk3_materialised": (3, 8, 16, DIRECT, PAIR_NAMES, "raw", {}),
-    # round 6's head (ops.WARP_HEAD_MODES off): _WarpHead, and the framework route whose backward concatenates (concat_channels_amax)
+    # round 6's head (ops.WARP_HEAD_MODES off): the nearest ops.warp_head, and the framework route whose backward concatenates (concat_channels_amax)
     "mk1_head_r6": (1, 8, 16, DIRECT, PAIR_NAMES, "lazy", dict(WARP_HEAD_MODES=False)),
     "mk1_concat_r6": (1, 8, 16, dict(warp_mask_losstype="direct", warp_bilinear=True), PAIR_NAMES, "lazy", dict(WARP_HEAD_MODES=False)),
     # the backward that recomputes its logits

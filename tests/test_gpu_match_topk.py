@@ -495,3 +495,141 @@ def test_every_new_op_inside_red_zones(name, monkeypatch):
     rz.test_red_zones(name, monkeypatch)
     want = {"corr_topk": "cocos_corr_topk_f16x3", "row_topk_lse": "cocos_row_topk_lse", "gather_blend_patches": "cocos_gather_blend_patches"}[name.split("-")[0]]
     assert want in set(rz.COVERAGE[name][0])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the warp family
+# The copy, the blend and the sub-cell pair share one translation unit (gather_warp.hip), one pixel decode and one clamped match: the
+# copy is the unweighted instantiation of the blend kernel.  Small odd shapes: 2 x 3 channels, a 3 x 5 grid of 2 x 2 cells.
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _index_copy(img, idx, grid, kgrid, down):
+    """The hard warp by indexing alone (no arithmetic touches a pixel): cell (y, x) of `grid` receives the cell idx[b, y, x] (clamped)
+    of the `kgrid` exemplar."""
+    (fh, fw), (hk, wk) = grid, kgrid
+    Bq, (Be, C) = idx.shape[0], img.shape[:2]
+    up = lambda t: t.repeat_interleave(down, 1).repeat_interleave(down, 2)
+    j = idx.reshape(Bq, fh, fw).long().clamp(0, hk * wk - 1)
+    sy = up(torch.div(j, wk, rounding_mode="floor")) * down + (torch.arange(fh * down, device=img.device) % down).view(1, -1, 1)
+    sx = up(j % wk) * down + (torch.arange(fw * down, device=img.device) % down).view(1, 1, -1)
+    b = torch.arange(Bq, device=img.device).view(-1, 1, 1, 1) * (1 if Be == Bq else 0)
+    return img[b, torch.arange(C, device=img.device).view(1, -1, 1, 1), sy[:, None], sx[:, None]]
+
+
+def _special_case(Be):
+    """img with a NaN of a non-default payload, a negative NaN, a -0 and both infinities in cells that idx names — through -1 and h*w
+    (clamped to the first and the last cell) in sample 0, directly in sample 1"""
+    Bq, C, h, w, down = 2, 3, 3, 5, 2
+    img = _randn(Be, C, h * down, w * down, seed=70 + Be)
+    bits = _bits(img)
+    for b in range(Be):
+        bits[b, 0, 0, 1], bits[b, 1, 1, 0] = 0x7FC12345, -0x3FEDCB         # cell 0: quiet NaNs with payloads, + and - (0xFFC01235)
+        bits[b, 2, 4, 9], bits[b, 0, 5, 8], bits[b, 1, 5, 9] = -(2 ** 31), 0x7F800000, -0x800000      # cell 14: -0, +inf, -inf
+    idx = torch.randint(0, h * w, (Bq, h, w), generator=torch.Generator().manual_seed(71)).to(DEV)
+    idx[0, 0, 0], idx[0, 1, 2], idx[1, 2, 4], idx[1, 0, 3] = -1, h * w, 0, h * w - 1
+    return img, idx, (Bq, C, h, w, down)
+
+
+@pytest.mark.parametrize("Be", [1, 2])
+def test_copy_instantiation_moves_bits_and_blend_of_one_agrees_on_finite_pixels(Be):
+    """img_batch_stride 0 (Be = 1) and dense (Be = 2): the copy equals the index gather on the int32 view — NaN payloads, -0 and the
+    infinities included; the blend with k = 1 and w = 1 equals the copy at every finite pixel (1 * p is p there; a NaN's payload is
+    not promised)."""
+    from cocosnet_amd import ops
+    img, idx, (Bq, C, h, w, down) = _special_case(Be)
+    out = ops.gather_patches(img, idx, h, w, down)
+    want = _index_copy(img, idx, (h, w), (h, w), down)
+    assert int(torch.isnan(want).sum()) >= 4 and int(torch.isinf(want).sum()) >= 4 and int((_bits(want) == -(2 ** 31)).sum()) >= 2
+    assert torch.equal(_bits(out), _bits(want))
+    one = ops.gather_blend_patches(img, idx.reshape(Bq, 1, h, w), torch.ones(Bq, 1, h, w, device=DEV), h, w, down)
+    finite = torch.isfinite(out)
+    assert torch.equal(_bits(one)[finite], _bits(out)[finite]) and bool(torch.isnan(one[torch.isnan(out)]).all())
+    assert torch.equal(one[torch.isinf(out)], out[torch.isinf(out)])
+
+
+def _fma_f32(a, b, c):
+    """fma(a, b, c) of fp32 numpy arrays, correctly rounded: the product is exact in fp64; its sum with c is split into hi + lo
+    (two-sum), and where hi lies exactly half way between two fp32 numbers the sign of lo decides instead of the tie rule"""
+    import numpy as np
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    hi = p + c
+    t = hi - p
+    lo = (p - (hi - t)) + (c - t)
+    r = hi.astype(np.float32)
+    other = np.nextafter(r, np.where(hi > r, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+    tie = (np.abs(hi - r.astype(np.float64)) == np.abs(other.astype(np.float64) - hi)) & (lo != 0) & (hi != r)
+    towards_other = (lo > 0) == (other > r)
+    return np.where(tie & towards_other, other, r).astype(np.float32)
+
+
+@pytest.mark.parametrize("Be", [1, 2])
+def test_blend_of_three_patches_in_the_written_order_bitwise(Be):
+    """acc = w_0 p_0 (one fp32 product), then acc = fma(w_r, p_r, acc), r = 1, 2: restated in numpy with every rounding where the
+    kernel has it — bit for bit, so a changed order of the taps or a product rounded before its add shows"""
+    import numpy as np
+    from cocosnet_amd import ops
+    Bq, C, h, w, down, k = 2, 3, 3, 5, 2, 3
+    img = _randn(Be, C, h * down, w * down, seed=80 + Be)
+    idx = torch.randint(0, h * w, (Bq, k, h, w), generator=torch.Generator().manual_seed(81)).to(DEV)
+    idx[0, 1, 0, 0], idx[1, 2, 2, 4] = -1, h * w
+    wt = torch.softmax(_randn(Bq, k, h, w, seed=82) * 2, dim=1)
+    out = ops.gather_blend_patches(img, idx, wt, h, w, down)
+    px = [_index_copy(img, idx[:, r], (h, w), (h, w), down).cpu().numpy() for r in range(k)]
+    wr = [wt[:, r].reshape(Bq, 1, h, w).repeat_interleave(down, 2).repeat_interleave(down, 3).expand(-1, C, -1, -1).cpu().numpy() for r in range(k)]
+    acc = (wr[0] * px[0]).astype(np.float32)
+    for r in range(1, k):
+        acc = _fma_f32(wr[r], px[r], acc)
+    assert np.array_equal(out.cpu().numpy().view(np.int32), acc.view(np.int32))
+
+
+def test_subcell_pair_on_two_grids_with_border_and_nan_offsets():
+    """A 3 x 4 content grid against a 2 x 5 exemplar grid, down = 2; offsets 0, +-0.5 (exact pixel positions: the right derivative),
+    one pushing past each border and one NaN.  off == 0 is the copy bit for bit; the forward against tests/match_refine_case.py within
+    tests/test_gpu_match_refine.py's 1e-6, d off against tests/match_flow_case.py by tests/test_gpu_match_flow.py's 4 x rule; the NaN
+    offset makes its own cell NaN (forward and gradient) and no other."""
+    import numpy as np
+    import match_flow_case as fc
+    import match_refine_case as mc
+    from cocosnet_amd import ops
+    from test_gpu_match_flow import _judge
+    from test_gpu_parity import rel
+    grid, kgrid, down, C = (3, 4), (2, 5), 2, 3
+    nq, nk = grid[0] * grid[1], kgrid[0] * kgrid[1]
+    g = torch.Generator().manual_seed(90)
+    for Be in (2, 1):
+        img = torch.rand(Be, C, kgrid[0] * down, kgrid[1] * down, generator=g) * 2 - 1
+        idx = torch.randint(0, nk, (2, nq), generator=g)
+        off = torch.zeros(2, nq, 2)
+        off[0, 1], off[0, 2], off[1, 3] = torch.tensor((0.5, -0.5)), torch.tensor((-0.5, 0.5)), torch.tensor((0.5, 0.5))
+        idx[0, 4], idx[0, 5], idx[0, 6], idx[0, 7] = 0, kgrid[1] - 1, 0, nk - 1              # left, right, top, bottom
+        off[0, 4], off[0, 5], off[0, 6], off[0, 7] = (torch.tensor(o) for o in ((-1.3, 0.3), (1.3, 0.3), (0.3, -1.3), (0.3, 1.3)))
+        idx[1, 0], idx[1, 1] = -1, nk                                                          # clamped matches
+        nan_cell = (1, 9)
+        zero = ops.gather_patches_subcell(img.to(DEV), idx.to(DEV), torch.zeros(2, nq, 2, device=DEV), grid, kgrid, down)
+        assert torch.equal(_bits(zero), _bits(_index_copy(img.to(DEV), idx.to(DEV), grid, kgrid, down)))
+        dout = torch.randn(2, C, grid[0] * down, grid[1] * down, generator=g)
+        with_nan = off.clone()
+        with_nan[nan_cell] = float("nan")
+        leaf = with_nan.to(DEV).requires_grad_(True)
+        out = ops.subcell_warp(img.to(DEV), idx.to(DEV), leaf, grid, kgrid, down)
+        out.backward(dout.to(DEV))
+        assert torch.equal(_bits(out), _bits(ops.gather_patches_subcell(img.to(DEV), idx.to(DEV), with_nan.to(DEV), grid, kgrid, down)))
+        # the NaN cell: its 2 x 2 pixels of every channel, its two gradients; then it is set aside (the arbiter is run without it)
+        y, x = divmod(nan_cell[1], grid[1])
+        cell = out[nan_cell[0], :, y * down:(y + 1) * down, x * down:(x + 1) * down]
+        assert bool(torch.isnan(cell).all()) and int(torch.isnan(out).sum()) == cell.numel()
+        assert bool(torch.isnan(leaf.grad[nan_cell]).all()) and int(torch.isnan(leaf.grad).sum()) == 2
+        got, dgot = out.detach().clone(), leaf.grad.clone()
+        got[nan_cell[0], :, y * down:(y + 1) * down, x * down:(x + 1) * down] = zero[nan_cell[0], :, y * down:(y + 1) * down, x * down:(x + 1) * down]
+        want = mc.gather_subcell(img.numpy(), idx.numpy(), off.numpy(), grid, kgrid, down)
+        err = rel(got, want)
+        print(f"[warp family] sub-cell forward Be={Be}: rel {err:.3e} (bound 1e-06)")
+        assert err <= 1e-6
+        dwant = fc.gather_bwd_off(img.numpy(), idx.numpy(), off.numpy(), dout.numpy(), grid, kgrid, down)
+        arm = fc.t_gather_bwd_off(img.to(DEV), idx.to(DEV), off.to(DEV), dout.to(DEV), grid, kgrid, down)
+        dgot[nan_cell] = torch.from_numpy(dwant[nan_cell]).float().to(DEV)
+        _judge(f"3x4 on 2x5 down=2 Be={Be}", "doff", dgot, arm, dwant)
+        for cell_i, axis in ((4, 0), (5, 0), (6, 1), (7, 1)):
+            assert float(leaf.grad[0, cell_i, axis]) == 0.0 and dwant[0, cell_i, axis] == 0.0

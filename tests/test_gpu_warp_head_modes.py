@@ -424,3 +424,63 @@ def test_peak_memory_of_a_celeba_edge_step_is_not_above_the_framework_route(monk
         peaks[modes] = torch.cuda.max_memory_allocated() - base
     print(f"K30_HEAD_PEAK celeba_edge B=16 64x64 framework route {peaks[False] / 2**20:.1f} MiB new route {peaks[True] / 2**20:.1f} MiB")
     assert peaks[True] <= peaks[False], peaks
+
+
+# ------------------------------------------------------------------------------------------------------ 9. one head op, one arm
+@pytest.mark.parametrize("d", [4, 2])      # the unrolled window sums and the generic loop
+def test_one_head_op_defaults_and_a_missing_mask_gradient(d, monkeypatch):
+    """ops.warp_head with default arguments (round 6's function, now the nearest mode of the one op): F.interpolate(nearest) and the
+    mask view bit for bit; a backward in which nothing used the mask equals one with an explicit zero gradient — d o, D and the
+    remembered max|d o| bit for bit — through autograd and at the entry point, where the absent gradient is a NULL pointer."""
+    monkeypatch.setattr(ops, "PRECISION", "f16x3")
+    B, Ci, Cs, h, w = 2, 3, 2, 3, 4
+    bits = lambda t: t.contiguous().view(torch.int32)
+    base = _rand(B, Ci + Cs, h * w, seed=40 + d)
+    y, m = ops.warp_head(base, Ci, h, w, d)
+    assert torch.equal(bits(y), bits(F.interpolate(base[:, :Ci].reshape(B, Ci, h, w), scale_factor=d, mode="nearest")))
+    assert m.data_ptr() == base[:, Ci:].data_ptr() and torch.equal(bits(m), bits(base[:, Ci:].reshape(B, Cs, h, w)))
+    g = _rand(*y.shape, seed=41)
+
+    def through_autograd(explicit_zero):
+        leaf = base.clone().requires_grad_(True)
+        y, m = ops.warp_head(_Tap.apply(leaf), Ci, h, w, d)
+        if explicit_zero:
+            torch.autograd.backward([y, m], [g, torch.zeros_like(m)])
+        else:
+            y.backward(g)
+        return leaf.grad, _Tap.seen["d"], _Tap.seen["amax"]
+
+    def at_the_entry_point(g_mask):
+        dout, drow, cell = torch.empty_like(base), torch.empty(B, h * w, device=DEV), torch.zeros(1, device=DEV)
+        ops._call("warp_head_bwd", "cocos_warp_head_bwd_ex", g.data_ptr(), ops._ptr(g_mask), 0, base.data_ptr(), dout.data_ptr(),
+                  drow.data_ptr(), cell.data_ptr(), B, Ci, Cs, h, w, d, ops._HEAD_MODES["nearest"], ops._stream())
+        return dout, drow, float(cell)
+
+    for absent, zero in ((through_autograd(False), through_autograd(True)),
+                         (at_the_entry_point(None), at_the_entry_point(torch.zeros(B, Cs, h, w, device=DEV)))):
+        assert torch.equal(bits(absent[0]), bits(zero[0])) and torch.equal(bits(absent[1]), bits(zero[1]))
+        assert absent[2] is not None and absent[2] == zero[2] == float(absent[0].abs().max())
+        assert not bool(absent[0][:, Ci:].any())
+
+
+@pytest.mark.parametrize("precision", ["fp32", "f16x3"])
+def test_modes_off_still_selects_the_nearest_head_bit_for_bit(precision, monkeypatch):
+    """The direct-mask flag set (round 6's): with ops.WARP_HEAD_MODES off the restricted condition still selects the head, through the
+    one op — every output and the theta / phi gradients equal those with the switch on, bit for bit."""
+    monkeypatch.setattr(ops, "PRECISION", precision)
+    monkeypatch.setattr(ops, "PROJ_PRECISION", precision)
+    monkeypatch.setitem(FLAG_SETS, "ade_direct", dict(warp_mask_losstype="direct", nc=7))
+    real, seen = ops._lib.call, {}
+    res = {}
+    for modes in (False, True):
+        seen[modes] = []
+        monkeypatch.setattr(ops._lib, "call", lambda n, *a, _m=modes: (seen[_m].append(n), real(n, *a))[1])
+        res[modes] = _hot_step("ade_direct", 1, modes, monkeypatch, B=1, fh=8, fw=16)
+    for modes in (False, True):
+        assert "cocos_warp_head_fwd_ex" in seen[modes] and "cocos_warp_head_bwd_ex" in seen[modes], (modes, seen[modes])
+    (o0, dt0, dp0), (o1, dt1, dp1) = res[False], res[True]
+    assert sorted(o0) == sorted(o1) and {"warp_out", "warp_mask"} <= set(o0) and "warp_out_bi" not in o0
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for k in o0:
+        assert torch.equal(bits(o0[k]), bits(o1[k])), k
+    assert torch.equal(bits(dt0), bits(dt1)) and torch.equal(bits(dp0), bits(dp1))

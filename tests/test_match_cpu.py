@@ -87,7 +87,7 @@ def test_header_table_and_library_carry_the_three_entry_points(hip_lib):
         assert _lib.PROTOTYPES.get(name, ("",))[0] == "int", f"{name} is not declared in cocos_hip.h"
         assert name in _lib.EXPORTED_SYMBOLS
         assert hasattr(hip_lib, name)
-    for unit in ("corr_topk_f16x3.hip", "row_topk_lse.hip", "gather_patches.hip"):      # K36a / K36b are the K = 1 instantiations
+    for unit in ("corr_topk_f16x3.hip", "row_topk_lse.hip", "gather_warp.hip"):      # K36a / K36b are the K = 1 instantiations
         assert unit in build.HIP_SOURCES
 
 

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 NEW_SYMBOLS = ("cocos_corr_topk_f16x3", "cocos_row_topk_lse", "cocos_gather_blend_patches")
-NEW_UNITS = ("corr_topk_f16x3.hip", "row_topk_lse.hip", "gather_blend_patches.hip")
+NEW_UNITS = ("corr_topk_f16x3.hip", "row_topk_lse.hip", "gather_warp.hip")
 
 
 def test_header_table_and_library_carry_the_three_entry_points(hip_lib):

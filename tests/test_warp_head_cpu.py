@@ -54,8 +54,8 @@ def test_argument_validation_of_the_new_entry_points_needs_no_gpu(hip_lib):
     assert bwd(one, None, None, one, one, one, one, 1, 40, 0, 4, 4, 4, 2, None) == -1 and b"down^2" in err()
     assert bwd(one, None, None, one, one, one, one, 1, 3, 0, 4, 6, 4, 1, None) == -2 and b"multiple of 4" in err()
     assert bwd(one, None, odd, one, one, one, one, 1, 3, 0, 4, 4, 4, 1, None) == -1 and b"aligned" in err()
-    # the round-6 entry point keeps refusing missing gradients
-    assert hip_lib.cocos_warp_head_bwd(None, one, one, one, one, one, 1, 3, 2, 4, 4, 4, None) == -1 and b"null" in err()
+    # the nearest mode with mask channels (round 6's shape): missing gradients are zeros, a missing o is refused
+    assert bwd(None, None, None, None, one, one, one, 1, 3, 2, 4, 4, 4, 0, None) == -1 and b"null" in err()
     # patch values: null, dims, divisibility
     assert val(None, None, one, 1, 3, 0, 8, 8, 4, None, None) == -1 and b"null" in err()
     assert val(one, None, None, 1, 3, 0, 8, 8, 4, None, None) == -1

@@ -27,7 +27,7 @@ sys.path.insert(0, REPO)
 
 B, CROP, NC, INV_T = 8, 256, 151, 100.0
 KERNELS = (("match_refine_bwd_f16x3.hip", ("match_refine_bwd_query_kernel", "match_refine_bwd_key_kernel")),
-           ("gather_patches.hip", ("gather_patches_subcell_bwd_off_kernel",)))
+           ("gather_warp.hip", ("gather_patches_subcell_bwd_off_kernel",)))
 
 
 def register_rows():
