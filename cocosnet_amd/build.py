@@ -76,6 +76,7 @@ HIP_SOURCES = [
     "corr_lse_bwd_f16x3.hip",
     "corr_topk_bias_f16x3.hip",
     "box3_sparse_warp.hip",
+    "box3_match_refine.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]
@@ -115,6 +116,7 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
     srcs = [os.path.join(CSRC_DIR, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC_DIR, "common.h"), os.path.join(CSRC_DIR, "box3_common.h"), os.path.join(CSRC_DIR, "proj_frag.h"),
                    os.path.join(CSRC_DIR, "topk_list.h"), os.path.join(CSRC_DIR, "sparse_row.h"), os.path.join(CSRC_DIR, "corr_topk_kernel.h"),
+                   os.path.join(CSRC_DIR, "box3_rows.h"),
                    os.path.join(REPO_DIR, "include", "cocos_hip.h")]
     stamp = LIB_PATH + ".sha256"      # next to the library: it travels with it (obj/ does not have to)
     want = _digest(deps)

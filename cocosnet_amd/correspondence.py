@@ -24,8 +24,8 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_box3_scope, _sparse_scope,
-                       _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_hot_path,
+from .hot_path import (HotPathConfig, _flow_box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_box3_scope, _sparse_scope,
+                       _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3, correspondence_hot_path,
                        correspondence_match, correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_sparse_box3,
                        correspondence_transport)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
@@ -496,6 +496,27 @@ class NoVGGCorrespondence(NetworkBase):
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         coor_out.update(correspondence_flow(theta_raw, phi_raw, ref_img, cfg, temperature, radius=radius,
                                             refine_temperature=refine_temperature))
+        return coor_out
+
+    def flow_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, radius=1, refine_temperature=None):
+        """flow_warp on the reference's default route, match_kernel 3 (K52, hot_path.correspondence_flow_box3): per content position
+        the best exemplar position is selected without gradient, as match() selects it, a softmax at `refine_temperature` (None:
+        `temperature`) over the box logits of the (2 radius + 1)^2 window around it gives a sub-cell offset, and ref_img is sampled
+        bilinearly at the refined position — with gradients to the whole network through theta and phi (none to ref_img) and nothing
+        HWxHW kept for the backward.  Returns flow_warp's dictionary: {warp_out [B,3,H,W], match_index [B,h,w] int64, match_offset
+        [B,2,h,w], match_xy_sub [B,2,h,w], match_window_prob [B,h,w]} (+ loss_novgg_featpair where project() makes it).  Under
+        torch.no_grad() this is the forward-only readout of the route.  Scope: match_kernel 3 with PONO_C on the plain flag set,
+        radius in 1..3; everything else raises ValueError before the network runs (no fall-back).  forward(), match(), flow_warp() and
+        sparse_warp_box3() are unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        # out-of-scope flags are refused before the network runs
+        _flow_box3_scope("flow_warp_box3", cfg, radius, refine_temperature, False, self.inter_channels)
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("flow_warp_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        coor_out = {}
+        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        coor_out.update(correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg, temperature, radius=radius,
+                                                 refine_temperature=refine_temperature))
         return coor_out
 
     def match_loss(self, ref_img, real_img, seg_map, ref_seg_map, target, temperature=0.01, *, weight=None, symmetric=True):

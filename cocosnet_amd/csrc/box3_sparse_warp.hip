@@ -19,25 +19,14 @@
 //   key gradient     one wave per exemplar position n, a GATHER over the inverse table of idx (K42's): per tap d the list of the key
 //                    q = n - d; from the d = 0 list alone dv^T[n], dnu_n, db_n.  A key every query names is a serial list of Nq
 //                    entries, walked for up to nine taps.
-#include "sparse_row.h"      // wave_sum, clamp_key
+#include "box3_rows.h"       // row4, in_grid, lane_fma4; wave_sum, clamp_key
 
 namespace cocos {
 
 constexpr int BS_WAVES = 4;              // rows (queries, content positions or keys) per workgroup, one per wave
 constexpr int BS_THREADS = BS_WAVES * kWave;
 constexpr int BS_MAXK = COCOS_MATCH_TOPK_MAX;
-constexpr int BS_C = 256;                // channels of theta / phi
-
-__device__ __forceinline__ f32x4 row4(const float* __restrict__ t, long long row, int lane) {
-    return *reinterpret_cast<const f32x4*>(t + row * BS_C + lane * 4);
-}
-
-__device__ __forceinline__ bool in_grid(int y, int x, int h, int w) { return (unsigned)y < (unsigned)h && (unsigned)x < (unsigned)w; }
-
-// acc + this lane's share of <q, kv>, in the order every R of this file is formed in
-__device__ __forceinline__ float lane_fma4(const f32x4& q, const f32x4& kv, float acc) {
-    return __builtin_fmaf(q[3], kv[3], __builtin_fmaf(q[2], kv[2], __builtin_fmaf(q[1], kv[1], __builtin_fmaf(q[0], kv[0], acc))));
-}
+constexpr int BS_C = BOX3_ROW_C;         // channels of theta / phi
 
 __global__ __launch_bounds__(BS_THREADS) void box3_sparse_fwd_kernel(const float* __restrict__ th_t, const float* __restrict__ ph_t,
                                                                      const float* __restrict__ mu, const float* __restrict__ a,

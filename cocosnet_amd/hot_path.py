@@ -630,7 +630,8 @@ _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused ma
           "sparse": " (the sparse warp runs on the fused match_kernel 1 route)",
           "nll": " (the loss runs on the fused match_kernel 1 route)",
           "transport": " (transport runs on the fused match_kernel 1 route)",
-          "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)"}
+          "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)",
+          "flow_box3": " (the box sub-cell flow runs on the match_kernel 3 route)"}
 
 
 def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool, kernel: int = 1):
@@ -1376,6 +1377,73 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
     xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
     return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
             "match_window_prob": torch.exp(lse_win.detach() - lse.reshape(B, N)).reshape(B, fh, fw)}
+
+
+# ---- K52: the trainable sub-cell correspondence on the match_kernel-3 route ----------------------------------------------------------
+def _flow_box3_scope(name: str, cfg: HotPathConfig, radius, refine_temperature, has_exemplar: bool = False, channels=None):
+    """ValueError for everything outside the scope of the match_kernel-3 sub-cell flow (K52: match_kernel 3, PONO_C, the plain flag
+    set, COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels, radius in 1..ops.MATCH_REFINE_MAX_RADIUS, a positive refinement
+    temperature); checked before any tensor is looked at"""
+    _route_scope(name, cfg, "flow_box3", plain_flags=True, match_fused=False, kernel=3)
+    if has_exemplar:
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the refinement differentiates phi)")
+    _route_channels(name, "flow_box3", channels)
+    top = ops.MATCH_REFINE_MAX_RADIUS
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
+        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
+    _refine_temperature_arg(name, refine_temperature)
+
+
+def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, temperature=0.01, *, radius=1, refine_temperature=None,
+                             exemplar=None):
+    """correspondence_flow on the reference's default route, match_kernel 3 (K52): per content position the best exemplar position is
+    SELECTED without gradient exactly as correspondence_match(theta_raw, phi_raw, cfg, temperature) selects it (that function is
+    called: K37 on the one x-box tensor T where ops.box3_fused_ok holds, the materialised chain elsewhere; T is gone when it
+    returns), a softmax at `refine_temperature` (None: `temperature`) over the box logits of the (2 radius + 1)^2 window of exemplar
+    positions around it gives a sub-cell offset — ops.box3_soft_match_offset, with gradients to theta_raw and phi_raw through the pair
+    logits and through the statistics of the unfolded vectors (K12, made here with autograd) — and the exemplar is sampled bilinearly
+    at the refined position — ops.subcell_warp, with a gradient to the offset.  Nothing HWxHW is kept for, or allocated in, the backward.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 (or ops.LazyProj1x1: the selection takes them as correspondence_match does, the
+    refinement projects them).  ref_img [B,3,H,W] gets no gradient (one that requires it raises ValueError).  Returns
+    correspondence_flow's dictionary: {warp_out [B,3,H,W], match_index [B,h,w] int64, match_offset [B,2,h,w] (x, y; in cells; with
+    gradient), match_xy_sub [B,2,h,w] = match_xy + match_offset (with gradient), match_window_prob [B,h,w] = exp(lse_win - the
+    selection's lse) (no gradient)}.
+
+    Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, plain flag set (no warp_patch / warp_bilinear / cycle terms),
+    no prepared exemplar, radius in 1..ops.MATCH_REFINE_MAX_RADIUS: everything else raises ValueError — there is no fall-back route.
+    CPU tensors raise CocosHipError.  Not built on this route: top-k centres, restrict, transport, search="patchmatch"."""
+    name = "correspondence_flow_box3"
+    _flow_box3_scope(name, cfg, radius, refine_temperature, exemplar is not None, theta_raw.shape[1])
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    down = cfg.down
+    _fused_width(name, theta_raw, phi_raw)
+    if ref_img.dim() != 4 or ref_img.shape[0] != B or tuple(ref_img.shape[2:]) != (gh * down, gw * down):
+        raise ValueError(f"{name}: ref_img {tuple(ref_img.shape)} is not a batch of {B} images of down={down} times the exemplar grid "
+                         f"{(gh, gw)}")
+    if ref_img.requires_grad:
+        raise ValueError(f"{name}: ref_img requires a gradient, and the gradient to the exemplar image is not built (pass ref_img.detach())")
+    if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    inv_rt = 1.0 / (temperature if refine_temperature is None else refine_temperature)
+    # lazy operands are projected first, with autograd (K0; the handle caches the projection, so this must not happen inside the
+    # selection's no_grad block); the selection still gets the operands as they came: its centres are correspondence_match's bit for bit
+    th, ph = _raw(theta_raw), _raw(phi_raw)
+    with torch.no_grad():
+        m = correspondence_match(theta_raw, phi_raw, cfg, temperature)      # selection: no gradient; its T is dropped inside
+        index, lse = m.index, m.lse.reshape(B, N)
+        del m
+    kc = float(C * 9)
+    mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
+    nu, b = _unfold3_stats(ph, kc)
+    idx = index.reshape(B, N)
+    off, lse_win = ops.box3_soft_match_offset(th, ph, mu, a, nu, b, idx, (fh, fw), (gh, gw), inv_rt, radius)
+    warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
+    offset = _rank_first(off, (B, fh, fw), 2)
+    xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
+    return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
+            "match_window_prob": torch.exp(lse_win.detach() - lse).reshape(B, fh, fw)}
 
 
 # ---- K49: trainable match readout — the correspondence negative log-likelihood in both softmax directions ---------------------------

@@ -3686,6 +3686,112 @@ def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_tempe
 
 
 # ------------------------------------------------------------------------------------------
+# K52  trainable sub-cell refinement on the match_kernel-3 route: K46's window soft-argmax on K51's box logit
+# ------------------------------------------------------------------------------------------
+class _Box3SoftMatchOffset(torch.autograd.Function):
+    """K52.  Saved for the backward: the position-major copies of theta and phi, idx [B,Nq], c [B,Nq,W] and the four statistics —
+    nothing with an Nq x Nk extent.  Every gradient comes from the same launch whichever others are asked for (the same bits); a
+    launch that serves no needed gradient is skipped."""
+
+    @staticmethod
+    def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, idx, inv_t: float, radius: int, fh: int, fw: int, gh: int, gw: int):
+        B, K = theta_raw.shape[:2]
+        Nq, Nk, slots = fh * fw, gh * gw, (2 * radius + 1) ** 2
+        th_t, ph_t = _transpose(theta_raw.reshape(B, K, Nq)), _transpose(phi_raw.reshape(B, K, Nk))
+        new = lambda *shape: torch.empty(shape, device=th_t.device, dtype=torch.float32)
+        off, lse_win, c = new(B, Nq, 2), new(B, Nq), new(B, Nq, slots)
+        _call("box3_match_refine_fwd", "cocos_box3_match_refine_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(), a.data_ptr(),
+              nu.data_ptr(), b.data_ptr(), idx.data_ptr(), off.data_ptr(), lse_win.data_ptr(), c.data_ptr(), B, K, fh, fw, gh, gw, radius,
+              float(inv_t), _stream())
+        ctx.save_for_backward(th_t, ph_t, idx, c, mu, a, nu, b)
+        ctx.cfg = (fh, fw, gh, gw, radius, float(inv_t), tuple(theta_raw.shape), tuple(phi_raw.shape))
+        ctx.mark_non_differentiable(lse_win)
+        return off, lse_win
+
+    @staticmethod
+    def backward(ctx, doff, _dlse):
+        th_t, ph_t, idx, c, mu, a, nu, b = ctx.saved_tensors
+        need_th, need_ph, need_mu, need_a, need_nu, need_b = ctx.needs_input_grad[:6]
+        fh, fw, gh, gw, radius, inv_t, th_shape, ph_shape = ctx.cfg
+        B, Nq, K = th_t.shape
+        Nk, slots = ph_t.shape[1], c.shape[2]
+        dth = dph = dmu = da = dnu = db = None
+        if not (need_th or need_ph or need_mu or need_a or need_nu or need_b):
+            return (None,) * 13
+        doff = _chk(doff, "box3_soft_match_offset: doff")
+        new = lambda *shape: torch.empty(shape, device=doff.device, dtype=torch.float32)
+        g = new(B, Nq, slots)
+        hb = new(B, Nq, slots) if need_b else None
+        dmu = new(B, Nq) if need_mu else None
+        da = new(B, Nq) if need_a else None
+        _call("box3_match_refine_bwd_pair", "cocos_box3_match_refine_bwd_pair", idx.data_ptr(), c.data_ptr(), a.data_ptr(), nu.data_ptr(),
+              b.data_ptr(), doff.data_ptr(), g.data_ptr(), _ptr(hb), _ptr(dmu), _ptr(da), B, K, fh, fw, gh, gw, radius, inv_t, _stream())
+        if need_th:
+            dth_t = new(B, Nq, K)
+            _call("box3_match_refine_bwd_theta", "cocos_box3_match_refine_bwd_theta", ph_t.data_ptr(), idx.data_ptr(), g.data_ptr(),
+                  dth_t.data_ptr(), B, K, fh, fw, gh, gw, radius, _stream())
+            dth = _transpose(dth_t).reshape(th_shape)
+            del dth_t
+        if need_ph or need_nu or need_b:      # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
+            entries, offsets = _inverse_index_table(idx.view(B, Nq, 1), Nk)
+            dph_t = new(B, Nk, K) if need_ph else None
+            dnu = new(B, Nk) if need_nu else None
+            db = new(B, Nk) if need_b else None
+            _call("box3_match_refine_bwd_key", "cocos_box3_match_refine_bwd_key", th_t.data_ptr(), g.data_ptr(), _ptr(hb), mu.data_ptr(),
+                  entries.data_ptr(), offsets.data_ptr(), _ptr(dph_t), _ptr(dnu), _ptr(db), B, K, fh, fw, gh, gw, radius, _stream())
+            if need_ph:
+                dph = _transpose(dph_t).reshape(ph_shape)
+                del dph_t
+        return (dth, dph, dmu, da, dnu, db) + (None,) * 7
+
+
+def box3_soft_match_offset(theta_raw, phi_raw, mu, a, nu, b, idx, grid, kgrid, inv_rt: float, radius: int):
+    """soft_match_offset on the match_kernel-3 logit (K52) -> (off [B,Nq,2] fp32, x first; lse_win [B,Nq]): per query p a softmax over
+    z[p,q] = inv_rt * a_p * b_q * (R[p,q] - 9*256 * mu_p * nu_q) — box3_sparse_softmax_warp's logit of one pair — of the keys q in the
+    (2 radius + 1)^2 window around idx[b,p] on the `kgrid` = (gh, gw) exemplar grid (positions outside the grid are left out), and its
+    expected offset (sum p dx, sum p dy) in cells, limited to [-radius, radius]; lse_win is the window's log-sum-exp (no gradient).
+    Differentiable in theta_raw, phi_raw, mu, a, nu and b (each gradient computed only when needed; idx is data; the backward treats
+    the limit as the identity).  theta_raw [B,256,fh,fw] or [B,256,fh*fw] on the `grid` = (fh, fw) content grid, phi_raw likewise on
+    `kgrid`, fp32, any grids >= 1, equal or not; (mu, a) [B,fh*fw] and (nu, b) [B,gh*gw] as unfold3_stats returns them for theta_raw
+    and phi_raw (made by it from tensors that require a gradient, they carry the statistics' share of the gradient back); idx [B,fh*fw]
+    (or [B,fh,fw]) int32 / int64, values outside [0, gh*gw) are clamped into it.  Nothing Nq x Nk is allocated, forward or backward;
+    the gradients are gathered in a fixed order (no atomics: bitwise reproducible; a centre all queries share is one serial list per
+    key around it and tap).  radius in 1..MATCH_REFINE_MAX_RADIUS, inv_rt > 0: ValueError before the library is called."""
+    name = "box3_soft_match_offset"
+    fh, fw = _grid_pair(name, "grid", grid)
+    gh, gw = _grid_pair(name, "kgrid", kgrid)
+    if not _is_int(radius) or not 1 <= radius <= MATCH_REFINE_MAX_RADIUS:
+        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{MATCH_REFINE_MAX_RADIUS}")
+    if not inv_rt > 0:
+        raise ValueError(f"{name}: inv_rt={inv_rt!r}: expected a positive number")
+    Nq, Nk = fh * fw, gh * gw
+    if theta_raw.dim() not in (3, 4) or phi_raw.dim() not in (3, 4):
+        raise ValueError(f"{name}: expected theta_raw [B,256,{fh},{fw}] and phi_raw [B,256,{gh},{gw}] (or flat positions); got "
+                         f"{tuple(theta_raw.shape)}, {tuple(phi_raw.shape)}")
+    B, K = theta_raw.shape[:2]
+    if (tuple(theta_raw.shape[2:]) not in ((fh, fw), (Nq,)) or tuple(phi_raw.shape[2:]) not in ((gh, gw), (Nk,))
+            or tuple(phi_raw.shape[:2]) != (B, K) or B < 1):
+        raise ValueError(f"{name}: shape mismatch theta_raw{tuple(theta_raw.shape)} phi_raw{tuple(phi_raw.shape)} on a {fh}x{fw} content "
+                         f"grid and a {gh}x{gw} exemplar grid")
+    if K != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
+    stats = ((mu, "mu", Nq), (a, "a", Nq), (nu, "nu", Nk), (b, "b", Nk))
+    for t, what, n in stats:
+        if tuple(t.shape) != (B, n):
+            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {(B, n)} (ops.unfold3_stats of "
+                             f"{'theta_raw' if what in ('mu', 'a') else 'phi_raw'})")
+    idx = _int_table(name, "idx", idx)
+    if idx.dim() < 1 or idx.shape[0] != B or idx.numel() != B * Nq:
+        raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
+    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + tuple((t, what) for t, what, _ in stats) + ((idx, "idx"),), False)
+    theta_raw, phi_raw = _chk(theta_raw, f"{name}: theta_raw"), _chk(phi_raw, f"{name}: phi_raw")
+    mu, a, nu, b = (_chk(t, f"{name}: {what}") for t, what, _ in stats)
+    with torch.no_grad():      # the kernels clamp as well: this is the table the key side inverts
+        idx = idx.reshape(B, Nq).clamp(0, Nk - 1).to(torch.int32).contiguous()
+    return _Box3SoftMatchOffset.apply(theta_raw, phi_raw, mu, a, nu, b, idx, float(inv_rt), radius, fh, fw, gh, gw)
+
+
+# ------------------------------------------------------------------------------------------
 # K7  softmax + warp from materialised key-major logits   (correspondence.py:307 + :318 ...)
 # ------------------------------------------------------------------------------------------
 class _LogitsSoftmaxWarp(torch.autograd.Function):

@@ -1521,6 +1521,49 @@ int cocos_match_refine_bwd_key_f16x3(const void* qh, const void* ql, const float
 int cocos_gather_patches_subcell_bwd_off(const float* img, const int* idx, const float* off, const float* dout, float* doff, int B, int C,
                                          int fh, int fw, int hk, int wk, int down, long long img_batch_stride, cocos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K52 Trainable sub-cell refinement on the match_kernel-3 route (box3_match_refine.hip): K44 / K46's window soft-argmax on K51's logit.
+ *     Grids, taps, R, the statistics, the 2-D in-grid rule and the fp32 position-major rows th_t [B,Nq,256], ph_t [B,Nk,256] as K51:
+ *         c[p,q] = R[p,q] - kc mu_p nu_q,   z[p,q] = inv_temperature a_p b_q c[p,q],   kc = 9 * 256.
+ *     idx [B,Nq] int32 is the centre key of every query, clamped into [0, Nk) first, at (yk, xk) of the gh x gw exemplar grid.  With
+ *     W1 = 2 radius + 1 the window has W = W1^2 slots, slot s = (dy + radius) W1 + (dx + radius), and holds the keys (yk + dy, xk + dx)
+ *     INSIDE the grid (a position outside is left out: neither clamped nor wrapped), visited dy ascending outside, dx ascending inside —
+ *     cocos_match_refine_f16x3's rules.  fp32 in a fixed order, contraction off, no atomics: bitwise reproducible.  A null pointer, a
+ *     non-positive size, radius outside 1..COCOS_MATCH_REFINE_MAX_RADIUS, a non-positive inv_temperature, misaligned rows:
+ *     COCOS_ERR_INVALID; K != 256, B Nq W or B Nk at or above 2^31: COCOS_ERR_UNSUPPORTED — all before any HIP call.
+ *   cocos_box3_match_refine_fwd: one wave per query.  m = max z over the window, lse_win = m + log sum exp(z - m), p = exp(z - lse_win),
+ *       off = (sum p dx, sum p dy) in visiting order, limited to [-radius, radius].  Writes off [B,Nq,2] (x first), lse_win [B,Nq] and
+ *       c [B,Nq,W], 0 in the slots outside the grid.  Non-finite scores are not sanitised.
+ *   cocos_box3_match_refine_bwd_pair: one wave per query.  Recomputes z from c and the statistics in the forward's arithmetic,
+ *       p = exp(z - m) / sum exp(z - m) (without the rounding of lse_win), o = (sum p dx, sum p dy) NOT limited (the limit is the
+ *       identity);  with doff [B,Nq,2] the incoming gradient of off:  dz_s = p_s ((dx_s - o_x) doff_x + (dy_s - o_y) doff_y), 0 for a
+ *       slot outside the grid.  Writes g [B,Nq,W] = dz inv_temperature a_p b_q (the coefficient on R) and, each unless null,
+ *       hb [B,Nq,W] = dz inv_temperature a_p c (the pair's share of db_q), dmu [B,Nq] = -kc sum_s g_s nu_q,
+ *       da [B,Nq] = sum_s dz_s inv_temperature b_q c_s — every slot of g and hb is written.
+ *   cocos_box3_match_refine_bwd_theta: one wave per content position m, a gather:
+ *       dth_t[m] = sum over d (raster order) with p = m - d in the content grid, over the slots s of p's window ascending, of
+ *                  g[p,s] [q_s + d in the exemplar grid] phi[q_s + d];  a position nobody reaches gets zeros, written here.
+ *   cocos_box3_match_refine_bwd_key: one wave per exemplar position n, a gather over the inverse table of the CLAMPED centre table
+ *       (entries [B Nq] / offsets [B Nk + 1] int32 as cocos_match_refine_bwd_key_f16x3 takes them):
+ *       dph_t[n] = sum over d (raster order) with q = n - d in the exemplar grid, over the window offsets e in visiting order with the
+ *                  centre q - e in the grid, over that centre's list in table order, of g[p, s(e)] [p + d in the content grid] theta[p + d];
+ *       and from d = 0 alone dnu [B,Nk] = -kc sum g[p, s(e)] mu_p, db [B,Nk] = sum hb[p, s(e)].  Each output may be null (not all
+ *       three), with the inputs only it reads: dph_t reads th_t, g; dnu reads g, mu; db reads hb.  A key in nobody's window gets zeros.
+ *       A centre all queries name is one serial list of Nq entries, walked for up to 9 W (tap, offset) pairs.  Positions and offsets
+ *       are clamped into the tables.
+ * ------------------------------------------------------------------------------------- */
+int cocos_box3_match_refine_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu, const float* b,
+                                const int* idx, float* off, float* lse_win, float* c, int B, int K, int fh, int fw, int gh, int gw,
+                                int radius, float inv_temperature, cocos_stream_t stream);
+int cocos_box3_match_refine_bwd_pair(const int* idx, const float* c, const float* a, const float* nu, const float* b, const float* doff,
+                                     float* g, float* hb /* nullable */, float* dmu /* nullable */, float* da /* nullable */, int B, int K,
+                                     int fh, int fw, int gh, int gw, int radius, float inv_temperature, cocos_stream_t stream);
+int cocos_box3_match_refine_bwd_theta(const float* ph_t, const int* idx, const float* g, float* dth_t, int B, int K, int fh, int fw, int gh,
+                                      int gw, int radius, cocos_stream_t stream);
+int cocos_box3_match_refine_bwd_key(const float* th_t, const float* g, const float* hb, const float* mu, const int* entries,
+                                    const int* offsets, float* dph_t /* nullable */, float* dnu /* nullable */, float* db /* nullable */,
+                                    int B, int K, int fh, int fw, int gh, int gw, int radius, cocos_stream_t stream);
+
 /* Debug: runs one v_mfma_f32_32x32x2_f32 with known operands and dumps the 64x16 accumulator
  * registers to out[64*16] so the host can verify the lane/register -> (row, col) map. */
 int cocos_debug_mfma_probe(float* out, cocos_stream_t stream);
