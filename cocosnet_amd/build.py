@@ -75,8 +75,7 @@ HIP_SOURCES = [
     "corr_match_mutual_f16x3.hip",
     "corr_lse_bwd_f16x3.hip",
     "corr_topk_bias_f16x3.hip",
-    "box3_sparse_warp.hip",
-    "box3_match_refine.hip",
+    "box3_pair.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

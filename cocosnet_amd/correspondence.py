@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _flow_box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_box3_scope, _sparse_scope,
+from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_scope,
                        _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3, correspondence_hot_path,
                        correspondence_match, correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_sparse_box3,
                        correspondence_transport)
@@ -471,7 +471,7 @@ class NoVGGCorrespondence(NetworkBase):
         project() makes it).  Scope: match_kernel 3 with PONO_C on the plain flag set; everything else raises ValueError before the
         network runs (no fall-back).  forward(), match() and sparse_warp() are unaffected."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-        _sparse_box3_scope("sparse_warp_box3", cfg, topk, False, self.inter_channels)      # refused before the network runs
+        _box3_scope("sparse_warp_box3", "sparse_box3", cfg, False, self.inter_channels, topk=topk)      # refused before the network runs
         if ref_img is None or ref_seg_map is None:
             raise ValueError("sparse_warp_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         coor_out = {}
@@ -510,7 +510,7 @@ class NoVGGCorrespondence(NetworkBase):
         sparse_warp_box3() are unaffected."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
         # out-of-scope flags are refused before the network runs
-        _flow_box3_scope("flow_warp_box3", cfg, radius, refine_temperature, False, self.inter_channels)
+        _box3_scope("flow_warp_box3", "flow_box3", cfg, False, self.inter_channels, radius=radius, refine_temperature=refine_temperature)
         if ref_img is None or ref_seg_map is None:
             raise ValueError("flow_warp_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         coor_out = {}

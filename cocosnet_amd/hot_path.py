@@ -1183,16 +1183,39 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
     return out
 
 
-# ---- K51: the trainable k-sparse warp on the match_kernel-3 route -------------------------------------------------------------------
-def _sparse_box3_scope(name: str, cfg: HotPathConfig, topk, has_exemplar: bool = False, channels=None):
-    """ValueError for everything outside the scope of the match_kernel-3 sparse warp (K51: match_kernel 3, PONO_C, the plain flag set,
-    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels); checked before any tensor is looked at -> k"""
-    k = _topk_arg(name, topk)
-    _route_scope(name, cfg, "sparse_box3", plain_flags=True, match_fused=False, kernel=3)
+# ---- K51 / K52: the trainable routes on match_kernel 3 (the k-sparse warp, the sub-cell flow) -----------------------------------------
+def _box3_scope(name: str, member: str, cfg: HotPathConfig, has_exemplar: bool = False, channels=None, *, topk=None, radius=None,
+                refine_temperature=None):
+    """ValueError for everything outside the scope of a trainable match_kernel-3 route (match_kernel 3, PONO_C, the plain flag set,
+    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels), before any tensor is looked at.  "sparse_box3" (K51): `topk` first
+    -> k.  "flow_box3" (K52): `radius` in 1..ops.MATCH_REFINE_MAX_RADIUS and a positive refinement temperature last."""
+    sparse = member == "sparse_box3"
+    k = _topk_arg(name, topk) if sparse else None
+    _route_scope(name, cfg, member, plain_flags=True, match_fused=False, kernel=3)
     if has_exemplar:
-        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the sparse warp differentiates phi)")
-    _route_channels(name, "sparse_box3", channels)
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the {'sparse warp' if sparse else 'refinement'} "
+                         "differentiates phi)")
+    _route_channels(name, member, channels)
+    if not sparse:
+        top = ops.MATCH_REFINE_MAX_RADIUS
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
+            raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
+        _refine_temperature_arg(name, refine_temperature)
     return k
+
+
+def _box3_select_and_stats(theta_raw, phi_raw, cfg: HotPathConfig, temperature, topk=1):
+    """The prologue of both routes -> (th, ph, mu, a, nu, b, readout).  Lazy operands are projected first, with autograd (K0; the
+    handle caches the projection, so this must not happen inside the selection's no_grad block); the selection still gets the
+    operands as they came: its candidates are correspondence_match's on the same arguments bit for bit.  The readout (a few [B,·,h,w]
+    tensors) lives across the two statistics launches, which run before the caller's warp_values: the same launches, reordered."""
+    th, ph = _raw(theta_raw), _raw(phi_raw)
+    with torch.no_grad():
+        m = correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk)      # selection: no gradient; its T is dropped inside
+    kc = float(th.shape[1] * 9)
+    mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
+    nu, b = _unfold3_stats(ph, kc)
+    return th, ph, mu, a, nu, b, m
 
 
 def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
@@ -1212,7 +1235,7 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     no prepared exemplar: everything else raises ValueError — there is no fall-back route.  CPU tensors raise CocosHipError.  Not built
     on this route: restrict, transport, search="patchmatch", refine."""
     name = "correspondence_sparse_box3"
-    k = _sparse_box3_scope(name, cfg, topk, exemplar is not None, theta_raw.shape[1])
+    k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     down = cfg.down
@@ -1224,19 +1247,12 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
-    # lazy operands are projected first, with autograd (K0; the handle caches the projection, so this must not happen inside the
-    # selection's no_grad block); the selection still gets the operands as they came, which is what makes its candidates those of
-    # correspondence_match on the same arguments bit for bit
-    th, ph = _raw(theta_raw), _raw(phi_raw)
+    *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature, k)
     with torch.no_grad():
-        m = correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=k)      # selection: no gradient; its T is dropped inside
         idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
         del m
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
-    kc = float(C * 9)
-    mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
-    nu, b = _unfold3_stats(ph, kc)
-    o, w = ops.box3_sparse_softmax_warp(th, ph, mu, a, nu, b, v, idx, 1.0 / temperature, return_weights=True)
+    o, w = ops.box3_sparse_softmax_warp(*operands, v, idx, 1.0 / temperature, return_weights=True)
     n_ref = ref_img.shape[1]
     y, o_mask = _split_channels(o, n_ref) if direct_mask else (o, None)
     out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
@@ -1327,6 +1343,18 @@ def _flow_scope(cfg: HotPathConfig, radius, refine_temperature):
     _refine_temperature_arg(name, refine_temperature)
 
 
+def _flow_result(ref_img, idx, off, lse_win, lse, grid, kgrid, down):
+    """correspondence_flow's dictionary (and correspondence_flow_box3's) from the selected centres idx [B,N] (int32 or int64), the refined
+    offset off [B,N,2] (with gradient), the window's log-sum-exp and the selection's lse [B,N]"""
+    (fh, fw), (gh, gw), B = grid, kgrid, idx.shape[0]
+    warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
+    index = idx.to(torch.int64).reshape(B, fh, fw)
+    offset = _rank_first(off, (B, fh, fw), 2)
+    xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
+    return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
+            "match_window_prob": torch.exp(lse_win.detach() - lse).reshape(B, fh, fw)}
+
+
 def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, temperature=0.01, *, radius=1, refine_temperature=None,
                         exemplar=None):
     """The trainable sub-cell correspondence (K46): per content position the best exemplar position is SELECTED without gradient (the
@@ -1371,29 +1399,10 @@ def correspondence_flow(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, tempera
         idx, _, lse = ops.corr_topk(qn, kn, inv_t, 1, planes)                  # selection: no gradient
         idx = idx.reshape(B, N)
     off, lse_win = ops.soft_match_offset(qn, kn, idx, (gh, gw), inv_rt, radius, planes)
-    warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
-    index = idx.to(torch.int64).reshape(B, fh, fw)
-    offset = _rank_first(off, (B, fh, fw), 2)
-    xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
-    return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
-            "match_window_prob": torch.exp(lse_win.detach() - lse.reshape(B, N)).reshape(B, fh, fw)}
+    return _flow_result(ref_img, idx, off, lse_win, lse.reshape(B, N), (fh, fw), (gh, gw), down)
 
 
 # ---- K52: the trainable sub-cell correspondence on the match_kernel-3 route ----------------------------------------------------------
-def _flow_box3_scope(name: str, cfg: HotPathConfig, radius, refine_temperature, has_exemplar: bool = False, channels=None):
-    """ValueError for everything outside the scope of the match_kernel-3 sub-cell flow (K52: match_kernel 3, PONO_C, the plain flag
-    set, COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels, radius in 1..ops.MATCH_REFINE_MAX_RADIUS, a positive refinement
-    temperature); checked before any tensor is looked at"""
-    _route_scope(name, cfg, "flow_box3", plain_flags=True, match_fused=False, kernel=3)
-    if has_exemplar:
-        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the refinement differentiates phi)")
-    _route_channels(name, "flow_box3", channels)
-    top = ops.MATCH_REFINE_MAX_RADIUS
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
-        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
-    _refine_temperature_arg(name, refine_temperature)
-
-
 def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, temperature=0.01, *, radius=1, refine_temperature=None,
                              exemplar=None):
     """correspondence_flow on the reference's default route, match_kernel 3 (K52): per content position the best exemplar position is
@@ -1414,7 +1423,7 @@ def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, te
     no prepared exemplar, radius in 1..ops.MATCH_REFINE_MAX_RADIUS: everything else raises ValueError — there is no fall-back route.
     CPU tensors raise CocosHipError.  Not built on this route: top-k centres, restrict, transport, search="patchmatch"."""
     name = "correspondence_flow_box3"
-    _flow_box3_scope(name, cfg, radius, refine_temperature, exemplar is not None, theta_raw.shape[1])
+    _box3_scope(name, "flow_box3", cfg, exemplar is not None, theta_raw.shape[1], radius=radius, refine_temperature=refine_temperature)
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     down = cfg.down
@@ -1427,23 +1436,11 @@ def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, te
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     inv_rt = 1.0 / (temperature if refine_temperature is None else refine_temperature)
-    # lazy operands are projected first, with autograd (K0; the handle caches the projection, so this must not happen inside the
-    # selection's no_grad block); the selection still gets the operands as they came: its centres are correspondence_match's bit for bit
-    th, ph = _raw(theta_raw), _raw(phi_raw)
-    with torch.no_grad():
-        m = correspondence_match(theta_raw, phi_raw, cfg, temperature)      # selection: no gradient; its T is dropped inside
-        index, lse = m.index, m.lse.reshape(B, N)
-        del m
-    kc = float(C * 9)
-    mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
-    nu, b = _unfold3_stats(ph, kc)
-    idx = index.reshape(B, N)
-    off, lse_win = ops.box3_soft_match_offset(th, ph, mu, a, nu, b, idx, (fh, fw), (gh, gw), inv_rt, radius)
-    warp = ops.subcell_warp(ref_img, idx, off, (fh, fw), (gh, gw), down)
-    offset = _rank_first(off, (B, fh, fw), 2)
-    xy = torch.stack((index % gw, torch.div(index, gw, rounding_mode="floor")), dim=1)
-    return {"warp_out": warp, "match_index": index, "match_offset": offset, "match_xy_sub": xy.float() + offset,
-            "match_window_prob": torch.exp(lse_win.detach() - lse).reshape(B, fh, fw)}
+    *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature)
+    idx, lse = m.index.reshape(B, N), m.lse.reshape(B, N)
+    del m
+    off, lse_win = ops.box3_soft_match_offset(*operands, idx, (fh, fw), (gh, gw), inv_rt, radius)
+    return _flow_result(ref_img, idx, off, lse_win, lse, (fh, fw), (gh, gw), down)
 
 
 # ---- K49: trainable match readout — the correspondence negative log-likelihood in both softmax directions ---------------------------

@@ -3580,12 +3580,65 @@ def unfold3_stats(x, k_unfolded: float, eps: float = NORM_EPS):
 
 
 # ------------------------------------------------------------------------------------------
-# K51  k-sparse correspondence warp with gradients on the match_kernel-3 route: K42's blend on the box logit of single pairs
+# K51 / K52  the pair kernels of the match_kernel-3 route (box3_pair.hip): a softmax over a few candidate keys per query on the box
+# logit of single pairs.  K51's candidates are the k keys of idx[b,p,:], K52's the window around idx[b,p]; what follows is shared.
 # ------------------------------------------------------------------------------------------
+def _box3_stats(name, B, Nq, Nk, mu, a, nu, b):
+    """ValueError unless (mu, a) are [B,Nq] and (nu, b) [B,Nk] -> ((tensor, what), ...) of the four"""
+    for t, what, n in ((mu, "mu", Nq), (a, "a", Nq), (nu, "nu", Nk), (b, "b", Nk)):
+        if tuple(t.shape) != (B, n):
+            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {(B, n)} (ops.unfold3_stats of "
+                             f"{'theta_raw' if what in ('mu', 'a') else 'phi_raw'})")
+    return (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")
+
+
+def _box3_pair_gate(name, heads, stats, idx, shape, Nk):
+    """_gate, then _chk of the float operands — `heads` = theta_raw, phi_raw (and v), then the statistics — and the clamp of the index
+    table into int32 `shape` (the kernels clamp as well: this is the table the key side inverts) -> (*heads, *stats, idx)"""
+    _gate(name, heads[:2] + stats + heads[2:] + ((idx, "idx"),), False)
+    floats = [_chk(t, f"{name}: {what}") for t, what in heads + stats]
+    with torch.no_grad():
+        return (*floats, idx.reshape(shape).clamp(0, Nk - 1).to(torch.int32).contiguous())
+
+
+def _box3_pair_backward(needs, th_t, ph_t, table, width, launch_pair, launch_theta, launch_key, Cv=0):
+    """The backward of both pair functions; needs = (theta, phi, mu, a, nu, b, v), `table` [B,Nq,k] what the key side inverts, `width`
+    the g / hb entries per query.  Every gradient comes from the same launch whichever others are asked for (the same bits); a launch
+    that serves no needed gradient is skipped -> (dth [B,K,Nq], dph [B,K,Nk], dmu, da, dnu, db, dv), None where not needed"""
+    need_th, need_ph, need_mu, need_a, need_nu, need_b, need_v = needs
+    B, Nq, K = th_t.shape
+    Nk = ph_t.shape[1]
+    new = lambda *shape: torch.empty(shape, device=th_t.device, dtype=torch.float32)
+    dth = dph = dmu = da = dnu = db = dv = g = hb = None
+    if need_th or need_ph or need_mu or need_a or need_nu or need_b:
+        g = new(B, Nq, width)
+        hb = new(B, Nq, width) if need_b else None
+        dmu = new(B, Nq) if need_mu else None
+        da = new(B, Nq) if need_a else None
+        launch_pair(g.data_ptr(), _ptr(hb), _ptr(dmu), _ptr(da))
+    if need_th:
+        dth_t = new(B, Nq, K)
+        launch_theta(g.data_ptr(), dth_t.data_ptr())
+        dth = _transpose(dth_t)
+        del dth_t
+    if need_ph or need_v or need_nu or need_b:
+        entries, offsets = _inverse_index_table(table, Nk)      # K42's table: one per backward, shared by the nine taps
+        dph_t = new(B, Nk, K) if need_ph else None
+        dv_t = new(B, Nk, Cv) if need_v else None
+        dnu = new(B, Nk) if need_nu else None
+        db = new(B, Nk) if need_b else None
+        launch_key(_ptr(g), _ptr(hb), entries.data_ptr(), offsets.data_ptr(), _ptr(dph_t), _ptr(dv_t), _ptr(dnu), _ptr(db))
+        if need_ph:
+            dph = _transpose(dph_t)
+            del dph_t
+        if need_v:
+            dv = _transpose(dv_t)
+    return dth, dph, dmu, da, dnu, db, dv
+
+
 class _Box3SparseSoftmaxWarp(torch.autograd.Function):
     """K51.  Saved for the backward: the position-major copies of theta and phi, v^T, idx, w, c [B,Nq,k] and the four statistics —
-    nothing with an Nq x Nk extent.  Every gradient comes from the same launch whichever others are asked for (the same bits);
-    a launch that serves no needed gradient is skipped."""
+    nothing with an Nq x Nk extent."""
 
     @staticmethod
     def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_t: float):
@@ -3606,42 +3659,18 @@ class _Box3SparseSoftmaxWarp(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dw):
         th_t, ph_t, vt, idx, w, c, mu, a, nu, b = ctx.saved_tensors
-        need_th, need_ph, need_mu, need_a, need_nu, need_b, need_v = ctx.needs_input_grad[:7]
         fh, fw, gh, gw, inv_t = ctx.cfg
-        B, Nq, K = th_t.shape
-        Nk, Cv, k = ph_t.shape[1], vt.shape[2], idx.shape[2]
+        B, _, K = th_t.shape
+        Cv, k = vt.shape[2], idx.shape[2]
         dout_t = _transpose(_chk(dout, "box3_sparse_softmax_warp: dout"))
-        new = lambda *shape: torch.empty(shape, device=dout.device, dtype=torch.float32)
-        dth = dph = dmu = da = dnu = db = dv = g = hb = None
-        if need_th or need_ph or need_mu or need_a or need_nu or need_b:
-            g = new(B, Nq, k)
-            hb = new(B, Nq, k) if need_b else None
-            dmu = new(B, Nq) if need_mu else None
-            da = new(B, Nq) if need_a else None
-            _call("box3_sparse_softmax_warp_bwd_pair", "cocos_box3_sparse_softmax_warp_bwd_pair", vt.data_ptr(), dout_t.data_ptr(),
-                  idx.data_ptr(), w.data_ptr(), c.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(), g.data_ptr(), _ptr(hb), _ptr(dmu),
-                  _ptr(da), B, K, fh, fw, gh, gw, Cv, k, inv_t, _stream())
-        if need_th:
-            dth_t = new(B, Nq, K)
-            _call("box3_sparse_softmax_warp_bwd_theta", "cocos_box3_sparse_softmax_warp_bwd_theta", ph_t.data_ptr(), idx.data_ptr(),
-                  g.data_ptr(), dth_t.data_ptr(), B, K, fh, fw, gh, gw, k, _stream())
-            dth = _transpose(dth_t).reshape(B, K, fh, fw)
-            del dth_t
-        if need_ph or need_v or need_nu or need_b:
-            entries, offsets = _inverse_index_table(idx, Nk)      # K42's table: one per backward, shared by the nine taps
-            dph_t = new(B, Nk, K) if need_ph else None
-            dv_t = new(B, Nk, Cv) if need_v else None
-            dnu = new(B, Nk) if need_nu else None
-            db = new(B, Nk) if need_b else None
-            _call("box3_sparse_softmax_warp_bwd_key", "cocos_box3_sparse_softmax_warp_bwd_key", th_t.data_ptr(), dout_t.data_ptr(), _ptr(g),
-                  _ptr(hb), w.data_ptr(), mu.data_ptr(), entries.data_ptr(), offsets.data_ptr(), _ptr(dph_t), _ptr(dv_t), _ptr(dnu),
-                  _ptr(db), B, K, fh, fw, gh, gw, Cv, k, _stream())
-            if need_ph:
-                dph = _transpose(dph_t).reshape(B, K, gh, gw)
-                del dph_t
-            if need_v:
-                dv = _transpose(dv_t)
-        return dth, dph, dmu, da, dnu, db, dv, None, None
+        name, dims = "box3_sparse_softmax_warp_bwd_", (B, K, fh, fw, gh, gw)
+        pair = lambda *out: _call(name + "pair", f"cocos_{name}pair", vt.data_ptr(), dout_t.data_ptr(), idx.data_ptr(), w.data_ptr(),
+                                  c.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(), *out, *dims, Cv, k, inv_t, _stream())
+        theta = lambda g, dth_t: _call(name + "theta", f"cocos_{name}theta", ph_t.data_ptr(), idx.data_ptr(), g, dth_t, *dims, k, _stream())
+        key = lambda g, hb, entries, offsets, *out: _call(name + "key", f"cocos_{name}key", th_t.data_ptr(), dout_t.data_ptr(), g, hb,
+                                                          w.data_ptr(), mu.data_ptr(), entries, offsets, *out, *dims, Cv, k, _stream())
+        dth, dph, *rest = _box3_pair_backward(ctx.needs_input_grad[:7], th_t, ph_t, idx, k, pair, theta, key, Cv)
+        return (None if dth is None else dth.reshape(B, K, fh, fw), None if dph is None else dph.reshape(B, K, gh, gw), *rest, None, None)
 
 
 def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_temperature: float, return_weights: bool = False):
@@ -3671,27 +3700,17 @@ def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_tempe
     if K != FUSED_K:
         raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
     _check_topk(name, int(idx.shape[2]), Nk)
-    stats = ((mu, "mu", Nq), (a, "a", Nq), (nu, "nu", Nk), (b, "b", Nk))
-    for t, what, n in stats:
-        if tuple(t.shape) != (B, n):
-            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {(B, n)} (ops.unfold3_stats of "
-                             f"{'theta_raw' if what in ('mu', 'a') else 'phi_raw'})")
-    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + tuple((t, what) for t, what, _ in stats) + ((v, "v"), (idx, "idx")), False)
-    theta_raw, phi_raw, v = (_chk(t, f"{name}: {what}") for t, what in ((theta_raw, "theta_raw"), (phi_raw, "phi_raw"), (v, "v")))
-    mu, a, nu, b = (_chk(t, f"{name}: {what}") for t, what, _ in stats)
-    with torch.no_grad():
-        idx = idx.clamp(0, Nk - 1).to(torch.int32).contiguous()
+    stats = _box3_stats(name, B, Nq, Nk, mu, a, nu, b)
+    theta_raw, phi_raw, v, mu, a, nu, b, idx = _box3_pair_gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw"), (v, "v")), stats, idx,
+                                                               idx.shape, Nk)
     out, w = _Box3SparseSoftmaxWarp.apply(theta_raw, phi_raw, mu, a, nu, b, v, idx, float(inv_temperature))
     return (out, w) if return_weights else out
 
 
-# ------------------------------------------------------------------------------------------
 # K52  trainable sub-cell refinement on the match_kernel-3 route: K46's window soft-argmax on K51's box logit
-# ------------------------------------------------------------------------------------------
 class _Box3SoftMatchOffset(torch.autograd.Function):
     """K52.  Saved for the backward: the position-major copies of theta and phi, idx [B,Nq], c [B,Nq,W] and the four statistics —
-    nothing with an Nq x Nk extent.  Every gradient comes from the same launch whichever others are asked for (the same bits); a
-    launch that serves no needed gradient is skipped."""
+    nothing with an Nq x Nk extent."""
 
     @staticmethod
     def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, idx, inv_t: float, radius: int, fh: int, fw: int, gh: int, gw: int):
@@ -3711,38 +3730,21 @@ class _Box3SoftMatchOffset(torch.autograd.Function):
     @staticmethod
     def backward(ctx, doff, _dlse):
         th_t, ph_t, idx, c, mu, a, nu, b = ctx.saved_tensors
-        need_th, need_ph, need_mu, need_a, need_nu, need_b = ctx.needs_input_grad[:6]
+        needs = ctx.needs_input_grad[:6]
         fh, fw, gh, gw, radius, inv_t, th_shape, ph_shape = ctx.cfg
         B, Nq, K = th_t.shape
-        Nk, slots = ph_t.shape[1], c.shape[2]
-        dth = dph = dmu = da = dnu = db = None
-        if not (need_th or need_ph or need_mu or need_a or need_nu or need_b):
+        if not any(needs):
             return (None,) * 13
         doff = _chk(doff, "box3_soft_match_offset: doff")
-        new = lambda *shape: torch.empty(shape, device=doff.device, dtype=torch.float32)
-        g = new(B, Nq, slots)
-        hb = new(B, Nq, slots) if need_b else None
-        dmu = new(B, Nq) if need_mu else None
-        da = new(B, Nq) if need_a else None
-        _call("box3_match_refine_bwd_pair", "cocos_box3_match_refine_bwd_pair", idx.data_ptr(), c.data_ptr(), a.data_ptr(), nu.data_ptr(),
-              b.data_ptr(), doff.data_ptr(), g.data_ptr(), _ptr(hb), _ptr(dmu), _ptr(da), B, K, fh, fw, gh, gw, radius, inv_t, _stream())
-        if need_th:
-            dth_t = new(B, Nq, K)
-            _call("box3_match_refine_bwd_theta", "cocos_box3_match_refine_bwd_theta", ph_t.data_ptr(), idx.data_ptr(), g.data_ptr(),
-                  dth_t.data_ptr(), B, K, fh, fw, gh, gw, radius, _stream())
-            dth = _transpose(dth_t).reshape(th_shape)
-            del dth_t
-        if need_ph or need_nu or need_b:      # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
-            entries, offsets = _inverse_index_table(idx.view(B, Nq, 1), Nk)
-            dph_t = new(B, Nk, K) if need_ph else None
-            dnu = new(B, Nk) if need_nu else None
-            db = new(B, Nk) if need_b else None
-            _call("box3_match_refine_bwd_key", "cocos_box3_match_refine_bwd_key", th_t.data_ptr(), g.data_ptr(), _ptr(hb), mu.data_ptr(),
-                  entries.data_ptr(), offsets.data_ptr(), _ptr(dph_t), _ptr(dnu), _ptr(db), B, K, fh, fw, gh, gw, radius, _stream())
-            if need_ph:
-                dph = _transpose(dph_t).reshape(ph_shape)
-                del dph_t
-        return (dth, dph, dmu, da, dnu, db) + (None,) * 7
+        name, dims = "box3_match_refine_bwd_", (B, K, fh, fw, gh, gw, radius)
+        pair = lambda *out: _call(name + "pair", f"cocos_{name}pair", idx.data_ptr(), c.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+                                  doff.data_ptr(), *out, *dims, inv_t, _stream())
+        theta = lambda g, dth_t: _call(name + "theta", f"cocos_{name}theta", ph_t.data_ptr(), idx.data_ptr(), g, dth_t, *dims, _stream())
+        key = lambda g, hb, entries, offsets, dph_t, _dv_t, dnu, db: _call(name + "key", f"cocos_{name}key", th_t.data_ptr(), g, hb,
+                                                                           mu.data_ptr(), entries, offsets, dph_t, dnu, db, *dims, _stream())
+        # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
+        dth, dph, *rest = _box3_pair_backward(needs + (False,), th_t, ph_t, idx.view(B, Nq, 1), c.shape[2], pair, theta, key)
+        return (None if dth is None else dth.reshape(th_shape), None if dph is None else dph.reshape(ph_shape), *rest[:4]) + (None,) * 7
 
 
 def box3_soft_match_offset(theta_raw, phi_raw, mu, a, nu, b, idx, grid, kgrid, inv_rt: float, radius: int):
@@ -3775,20 +3777,12 @@ def box3_soft_match_offset(theta_raw, phi_raw, mu, a, nu, b, idx, grid, kgrid, i
                          f"grid and a {gh}x{gw} exemplar grid")
     if K != FUSED_K:
         raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
-    stats = ((mu, "mu", Nq), (a, "a", Nq), (nu, "nu", Nk), (b, "b", Nk))
-    for t, what, n in stats:
-        if tuple(t.shape) != (B, n):
-            raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {(B, n)} (ops.unfold3_stats of "
-                             f"{'theta_raw' if what in ('mu', 'a') else 'phi_raw'})")
+    stats = _box3_stats(name, B, Nq, Nk, mu, a, nu, b)
     idx = _int_table(name, "idx", idx)
     if idx.dim() < 1 or idx.shape[0] != B or idx.numel() != B * Nq:
         raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
-    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + tuple((t, what) for t, what, _ in stats) + ((idx, "idx"),), False)
-    theta_raw, phi_raw = _chk(theta_raw, f"{name}: theta_raw"), _chk(phi_raw, f"{name}: phi_raw")
-    mu, a, nu, b = (_chk(t, f"{name}: {what}") for t, what, _ in stats)
-    with torch.no_grad():      # the kernels clamp as well: this is the table the key side inverts
-        idx = idx.reshape(B, Nq).clamp(0, Nk - 1).to(torch.int32).contiguous()
-    return _Box3SoftMatchOffset.apply(theta_raw, phi_raw, mu, a, nu, b, idx, float(inv_rt), radius, fh, fw, gh, gw)
+    operands = _box3_pair_gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")), stats, idx, (B, Nq), Nk)
+    return _Box3SoftMatchOffset.apply(*operands, float(inv_rt), radius, fh, fw, gh, gw)
 
 
 # ------------------------------------------------------------------------------------------

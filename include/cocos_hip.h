@@ -1383,7 +1383,7 @@ int cocos_sparse_softmax_warp_bwd_key_f16x3(const void* qh, const void* ql, cons
 int cocos_transpose_f32(const float* in, float* out, int B, int R, int C, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K51 k-sparse correspondence warp with gradients on the match_kernel-3 route (box3_sparse_warp.hip): K42's blend on the logit of the
+ * K51 k-sparse correspondence warp with gradients on the match_kernel-3 route (box3_pair.hip, the TopkSet candidate policy): K42's blend on the logit of the
  *     3x3-unfolded, centred, normalised vectors, taken for one pair.  Content grid fh x fw (Nq = fh fw, position p = py fw + px),
  *     exemplar grid gh x gw (Nk = gh gw), any sizes >= 1, equal or not; taps d in {-1,0,1}^2:
  *         R[p,q] = sum_d [p+d inside the content grid] [q+d inside the exemplar grid] <theta[:,p+d], phi[:,q+d]>
@@ -1522,7 +1522,7 @@ int cocos_gather_patches_subcell_bwd_off(const float* img, const int* idx, const
                                          int fh, int fw, int hk, int wk, int down, long long img_batch_stride, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K52 Trainable sub-cell refinement on the match_kernel-3 route (box3_match_refine.hip): K44 / K46's window soft-argmax on K51's logit.
+ * K52 Trainable sub-cell refinement on the match_kernel-3 route (box3_pair.hip, the WindowSet candidate policy): K44 / K46's window soft-argmax on K51's logit.
  *     Grids, taps, R, the statistics, the 2-D in-grid rule and the fp32 position-major rows th_t [B,Nq,256], ph_t [B,Nk,256] as K51:
  *         c[p,q] = R[p,q] - kc mu_p nu_q,   z[p,q] = inv_temperature a_p b_q c[p,q],   kc = 9 * 256.
  *     idx [B,Nq] int32 is the centre key of every query, clamped into [0, Nk) first, at (yk, xk) of the gh x gw exemplar grid.  With

@@ -23,8 +23,8 @@ def test_header_table_and_library_carry_the_entry_points(hip_lib):
         assert _lib.PROTOTYPES.get(name, ("",))[0] == "int", f"{name} is not declared in cocos_hip.h"
         assert name in _lib.EXPORTED_SYMBOLS
         assert hasattr(hip_lib, name)
-    assert "box3_sparse_warp.hip" in build.HIP_SOURCES
-    assert os.path.exists(os.path.join(build.CSRC_DIR, "box3_sparse_warp.hip"))
+    assert "box3_pair.hip" in build.HIP_SOURCES
+    assert os.path.exists(os.path.join(build.CSRC_DIR, "box3_pair.hip"))
 
 
 def test_argument_validation_needs_no_gpu(hip_lib):

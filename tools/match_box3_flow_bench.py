@@ -34,10 +34,11 @@ SHAPES = {"8x64": (8, 64), "1x128": (1, 128)}
 
 
 def register_rows():
-    usage = benchlib.resource_usage("box3_match_refine.hip")
+    usage = benchlib.resource_usage("box3_pair.hip", keep=("box3_refine_", "WindowSet"))      # this route's four of the unit's eight kernels
     if usage is None:
         return None
-    return [(re.search(r"\d+(box3_refine_[a-z_0-9]+_kernel)", u.name).group(1), u.vgprs, u.agprs, u.scratch, u.occupancy) for u in usage]
+    return [(re.search(r"\d+(box3_[a-z_0-9]+_kernel)", u.name).group(1) + ("<WindowSet>" if "WindowSet" in u.name else ""), u.vgprs, u.agprs,
+             u.scratch, u.occupancy) for u in usage]
 
 
 def bench_shape(B, H, args):
