@@ -68,10 +68,8 @@ HIP_SOURCES = [
     "gather_warp.hip",
     "corr_topk_f16x3.hip",
     "row_topk_lse.hip",
-    "sparse_warp_f16x3.hip",
+    "plane_pair.hip",
     "patchmatch_f16x3.hip",
-    "match_refine_f16x3.hip",
-    "match_refine_bwd_f16x3.hip",
     "corr_match_mutual_f16x3.hip",
     "corr_lse_bwd_f16x3.hip",
     "corr_topk_bias_f16x3.hip",
@@ -113,10 +111,10 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
     """Compile every HIP translation unit for gfx950 and link libcocos_hip.so. Returns its path."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = [os.path.join(CSRC_DIR, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC_DIR, "common.h"), os.path.join(CSRC_DIR, "box3_common.h"), os.path.join(CSRC_DIR, "proj_frag.h"),
-                   os.path.join(CSRC_DIR, "topk_list.h"), os.path.join(CSRC_DIR, "sparse_row.h"), os.path.join(CSRC_DIR, "corr_topk_kernel.h"),
-                   os.path.join(CSRC_DIR, "box3_rows.h"),
-                   os.path.join(REPO_DIR, "include", "cocos_hip.h")]
+    # every header under csrc/, found by listing it: one left off a hand-kept list would not enter the stamp, and editing it would
+    # leave a stale library in use
+    deps = srcs + sorted(os.path.join(CSRC_DIR, h) for h in os.listdir(CSRC_DIR) if h.endswith(".h")) + [
+        os.path.join(REPO_DIR, "include", "cocos_hip.h")]
     stamp = LIB_PATH + ".sha256"      # next to the library: it travels with it (obj/ does not have to)
     want = _digest(deps)
     if (not force and os.path.exists(LIB_PATH) and os.path.exists(stamp)

@@ -1524,6 +1524,34 @@ def _inverse_index_table(idx: torch.Tensor, Nk: int):
     return entries, offsets
 
 
+def _plane_pair_backward(needs, qh, Nk, table, width, launch_query, launch_key, Cv=0):
+    """The backward of K42 and K46 (plane_pair.hip); needs = (qn, kn, v), `table` [B,Nq,k] what the key side inverts, `width` the ds entries
+    per query.  Every gradient comes from the same launch whichever others are asked for (the same bits); a launch that serves no needed
+    gradient is skipped -> (dqn [B,K,Nq], dkn [B,K,Nk], dv [B,Cv,Nk]), None where not needed"""
+    need_q, need_k, need_v = needs
+    B, Nq, K = qh.shape
+    new = lambda *shape: torch.empty(shape, device=qh.device, dtype=torch.float32)
+    dqn = dkn = dv = ds = None
+    if need_q or need_k:
+        ds = new(B, Nq, width)
+        dq_t = new(B, Nq, K) if need_q else None
+        launch_query(ds.data_ptr(), _ptr(dq_t))
+        if need_q:
+            dqn = _transpose(dq_t)
+            del dq_t
+    if need_k or need_v:
+        entries, offsets = _inverse_index_table(table, Nk)
+        dk_t = new(B, Nk, K) if need_k else None
+        dv_t = new(B, Nk, Cv) if need_v else None
+        launch_key(_ptr(ds), entries.data_ptr(), offsets.data_ptr(), _ptr(dk_t), _ptr(dv_t))
+        if need_k:
+            dkn = _transpose(dk_t)
+            del dk_t
+        if need_v:
+            dv = _transpose(dv_t)
+    return dqn, dkn, dv
+
+
 class _SparseSoftmaxWarp(torch.autograd.Function):
     """K42.  qn / kn are only the autograd inputs (fp32 tensors or producer handles): the kernels read their position-major operand
     planes qh, ql, kh, kl.  Saved for the backward: the four planes, v^T, idx and w [B,Nq,k] — nothing with an Nq x Nk extent."""
@@ -1550,32 +1578,15 @@ class _SparseSoftmaxWarp(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dw):
         qh, ql, kh, kl, vt, idx, w = ctx.saved_tensors
-        need_q, need_k, need_v = ctx.needs_input_grad[:3]
         B, Nq, K = qh.shape
         Nk, Cv, k = kh.shape[1], vt.shape[2], idx.shape[2]
         dout_t = _transpose(_chk(dout, "sparse_softmax_warp: dout"))
-        dims = (B, K, Nq, Nk, Cv, k, ctx.inv_t, SPLIT_OPERAND_SCALE, _stream())
-        dqn = dkn = dv = ds = None
-        if need_q or need_k:
-            ds = torch.empty((B, Nq, k), device=dout.device, dtype=torch.float32)
-            dq_t = torch.empty((B, Nq, K), device=dout.device, dtype=torch.float32) if need_q else None
-            _call("sparse_softmax_warp_bwd_query", "cocos_sparse_softmax_warp_bwd_query_f16x3", kh.data_ptr(), kl.data_ptr(), vt.data_ptr(),
-                  dout_t.data_ptr(), idx.data_ptr(), w.data_ptr(), ds.data_ptr(), _ptr(dq_t), *dims)
-            if need_q:
-                dqn = _transpose(dq_t)
-                del dq_t
-        if need_k or need_v:
-            entries, offsets = _inverse_index_table(idx, Nk)
-            dk_t = torch.empty((B, Nk, K), device=dout.device, dtype=torch.float32) if need_k else None
-            dv_t = torch.empty((B, Nk, Cv), device=dout.device, dtype=torch.float32) if need_v else None
-            _call("sparse_softmax_warp_bwd_key", "cocos_sparse_softmax_warp_bwd_key_f16x3", qh.data_ptr(), ql.data_ptr(), dout_t.data_ptr(),
-                  _ptr(ds), w.data_ptr(), entries.data_ptr(), offsets.data_ptr(), _ptr(dk_t), _ptr(dv_t), *dims)
-            if need_k:
-                dkn = _transpose(dk_t)
-                del dk_t
-            if need_v:
-                dv = _transpose(dv_t)
-        return dqn, dkn, dv, None, None, None, None, None, None, None
+        name, dims = "sparse_softmax_warp_bwd_", (B, K, Nq, Nk, Cv, k, ctx.inv_t, SPLIT_OPERAND_SCALE, _stream())
+        query = lambda *out: _call(name + "query", f"cocos_{name}query_f16x3", kh.data_ptr(), kl.data_ptr(), vt.data_ptr(), dout_t.data_ptr(),
+                                   idx.data_ptr(), w.data_ptr(), *out, *dims)
+        key = lambda ds, entries, offsets, *out: _call(name + "key", f"cocos_{name}key_f16x3", qh.data_ptr(), ql.data_ptr(), dout_t.data_ptr(),
+                                                       ds, w.data_ptr(), entries, offsets, *out, *dims)
+        return _plane_pair_backward(ctx.needs_input_grad[:3], qh, Nk, idx, k, query, key, Cv) + (None,) * 7
 
 
 def sparse_softmax_warp(qn, kn, v, idx, inv_temperature: float, planes: OperandPlanes | None = None, return_weights: bool = False,
@@ -1826,27 +1837,16 @@ class _SoftMatchOffset(torch.autograd.Function):
     def backward(ctx, doff, _dlse):
         qh, ql, kh, kl, idx = ctx.saved_tensors
         inv_t, radius, hk, wk = ctx.cfg
-        need_q, need_k = ctx.needs_input_grad[:2]
-        dqn = dkn = None
-        if need_q or need_k:
-            B, Nq, K = qh.shape
-            Nk, slots = hk * wk, (2 * radius + 1) ** 2
-            doff = _chk(doff, "soft_match_offset: doff")
-            dims = (B, K, Nq, Nk, hk, wk, radius, inv_t, SPLIT_OPERAND_SCALE, _stream())
-            ds = torch.empty((B, Nq, slots), device=doff.device, dtype=torch.float32)
-            dq_t = torch.empty((B, Nq, K), device=doff.device, dtype=torch.float32) if need_q else None
-            _call("match_refine_bwd_query", "cocos_match_refine_bwd_query_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
-                  idx.data_ptr(), doff.data_ptr(), ds.data_ptr(), _ptr(dq_t), *dims)
-            if need_q:
-                dqn = _transpose(dq_t)
-                del dq_t
-            if need_k:      # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
-                entries, offsets = _inverse_index_table(idx.view(B, Nq, 1), Nk)
-                dk_t = torch.empty((B, Nk, K), device=doff.device, dtype=torch.float32)
-                _call("match_refine_bwd_key", "cocos_match_refine_bwd_key_f16x3", qh.data_ptr(), ql.data_ptr(), ds.data_ptr(),
-                      entries.data_ptr(), offsets.data_ptr(), dk_t.data_ptr(), *dims)
-                dkn = _transpose(dk_t)
-        return dqn, dkn, None, None, None, None, None, None, None, None, None
+        B, Nq, K = qh.shape
+        doff = _chk(doff, "soft_match_offset: doff")
+        name, dims = "match_refine_bwd_", (B, K, Nq, hk * wk, hk, wk, radius, inv_t, SPLIT_OPERAND_SCALE, _stream())
+        query = lambda *out: _call(name + "query", f"cocos_{name}query_f16x3", qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(),
+                                   idx.data_ptr(), doff.data_ptr(), *out, *dims)
+        key = lambda ds, entries, offsets, dk_t, _dv_t: _call(name + "key", f"cocos_{name}key_f16x3", qh.data_ptr(), ql.data_ptr(), ds, entries,
+                                                              offsets, dk_t, *dims)
+        # the key side gathers over the inverse table of the (clamped) centres: K42's, with k = 1
+        needs = ctx.needs_input_grad[:2] + (False,)
+        return _plane_pair_backward(needs, qh, hk * wk, idx.view(B, Nq, 1), (2 * radius + 1) ** 2, query, key)[:2] + (None,) * 9
 
 
 def soft_match_offset(qn, kn, idx, kgrid, inv_t: float, radius: int, planes: OperandPlanes | None = None):

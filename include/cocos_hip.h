@@ -1338,7 +1338,7 @@ int cocos_pair_logits_bwd_query_f16x3(const void* kh, const void* kl, const int*
                                       int Nq, int Nk, float inv_temperature, float operand_scale, int accumulate, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K42 k-sparse correspondence warp with gradients (sparse_warp_f16x3.hip): attention over the k keys per query that the top-k match
+ * K42 k-sparse correspondence warp with gradients (plane_pair.hip): attention over the k keys per query that the top-k match
  *     readout selected (selection itself carries no gradient),
  *         s[b,i,r] = inv_temperature <qn[b,:,i], kn[b,:,j_r]>,  j_r = idx[b,i,r],  w = softmax over r of s,
  *         out[b,:,i] = sum_r w[b,i,r] v[b,:,j_r]
@@ -1455,7 +1455,7 @@ int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const void* kh, 
                                 int radius0, int seed, int iteration, float inv_temperature, float operand_scale, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K44 Sub-cell match refinement (match_refine_f16x3.hip, gather_warp.hip): a soft-argmax over the window of keys around a hard
+ * K44 Sub-cell match refinement (plane_pair.hip, gather_warp.hip): a soft-argmax over the window of keys around a hard
  *     match, and the full-resolution warp sampled at the refined position.
  *   cocos_match_refine_f16x3: qh, ql [B,Nq,256], kh, kl [B,Nk,256] operand planes and score arithmetic as K42 / K43 (the logit
  *     cocos_sparse_softmax_warp_fwd_f16x3 forms for the same pair, bit for bit); idx [B,Nq] int32 the centre key of every query,
@@ -1484,7 +1484,7 @@ int cocos_gather_patches_subcell(const float* img, const int* idx, const float* 
                                  int wk, int down, long long img_batch_stride, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * K46 Gradients of the sub-cell refinement (match_refine_bwd_f16x3.hip, gather_warp.hip): K44's offset becomes trainable — the
+ * K46 Gradients of the sub-cell refinement (plane_pair.hip, gather_warp.hip): K44's offset becomes trainable — the
  *     backward of cocos_match_refine_f16x3 to the two operands and of cocos_gather_patches_subcell to the offset.
  *     Common to the two match kernels: planes, idx, grids, radius and scales as cocos_match_refine_f16x3; W = (2 radius + 1)^2 window
  *     slots per query, slot s = (dy + radius) (2 radius + 1) + (dx + radius); ds [B,Nq,W] fp32; dq_t [B,Nq,256], dk_t [B,Nk,256]

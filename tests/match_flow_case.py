@@ -1,4 +1,4 @@
-"""An fp64 numpy restatement of K46's three backward formulas for the tests (cocosnet_amd/csrc/match_refine_bwd_f16x3.hip and
+"""An fp64 numpy restatement of K46's three backward formulas for the tests (cocosnet_amd/csrc/plane_pair.hip and
 gather_patches_subcell_bwd_off_kernel of gather_warp.hip), built on tests/match_refine_case.py's forward restatement, and the same
 formulas in torch ops of any dtype and device: the fp32 arm the GPU tests measure the kernels' error against, and the fp64 function
 torch.autograd differentiates to check the restatement itself.

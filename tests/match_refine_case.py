@@ -1,4 +1,4 @@
-"""A numpy fp64 restatement of K44 for the tests (cocosnet_amd/csrc/match_refine_f16x3.hip and gather_patches_subcell_kernel of
+"""A numpy fp64 restatement of K44 for the tests (cocosnet_amd/csrc/plane_pair.hip and gather_patches_subcell_kernel of
 gather_warp.hip): which keys are in a query's window, the window softmax and its expected offset, and the bilinear gather at the
 sub-cell position.
 

@@ -23,7 +23,7 @@ def test_header_table_and_library_carry_the_entry_points(hip_lib):
     for name in (QUERY, KEY, GATHER):
         assert _lib.PROTOTYPES.get(name, ("",))[0] == "int", f"{name} is not declared in cocos_hip.h"
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(hip_lib, name)
-    assert "match_refine_bwd_f16x3.hip" in build.HIP_SOURCES
+    assert "plane_pair.hip" in build.HIP_SOURCES
     assert list(_lib._SIGNATURES[QUERY][1]) == [_P] * 8 + [_I] * 7 + [_F] * 2 + [_P]
     assert list(_lib._SIGNATURES[KEY][1]) == [_P] * 6 + [_I] * 7 + [_F] * 2 + [_P]
     assert list(_lib._SIGNATURES[GATHER][1]) == [_P] * 5 + [_I] * 7 + [_LL, _P]

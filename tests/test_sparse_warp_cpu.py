@@ -16,7 +16,7 @@ def test_header_table_and_library_carry_the_entry_points(hip_lib):
         assert _lib.PROTOTYPES.get(name, ("",))[0] == "int", f"{name} is not declared in cocos_hip.h"
         assert name in _lib.EXPORTED_SYMBOLS
         assert hasattr(hip_lib, name)
-    assert "sparse_warp_f16x3.hip" in build.HIP_SOURCES
+    assert "plane_pair.hip" in build.HIP_SOURCES
 
 
 def test_argument_validation_needs_no_gpu(hip_lib):

@@ -26,7 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 B, CROP, NC, INV_T = 8, 256, 151, 100.0
-KERNELS = (("match_refine_bwd_f16x3.hip", ("match_refine_bwd_query_kernel", "match_refine_bwd_key_kernel")),
+KERNELS = (("plane_pair.hip", ("match_refine_bwd_query_kernel", "match_refine_bwd_key_kernel")),
            ("gather_warp.hip", ("gather_patches_subcell_bwd_off_kernel",)))
 
 

@@ -30,7 +30,7 @@ def register_rows():
     """[(kernel, VGPRs, SGPRs, scratch bytes / lane, waves / SIMD)] of the two new kernels from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
     rows = []
-    for unit, want in (("match_refine_f16x3.hip", "match_refine_kernel"), ("gather_warp.hip", "gather_patches_subcell_kernel")):
+    for unit, want in (("plane_pair.hip", "match_refine_kernel"), ("gather_warp.hip", "gather_patches_subcell_kernel")):
         usage = benchlib.resource_usage(unit, keep=(want,))
         if usage is None:
             return None

@@ -31,9 +31,9 @@ KS = (1, 2, 4, 8)
 
 
 def register_rows():
-    """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of sparse_warp_f16x3.hip from hipcc's kernel-resource-usage remarks;
+    """[(kernel, VGPRs, AGPRs, scratch bytes / lane, waves / SIMD)] of plane_pair.hip from hipcc's kernel-resource-usage remarks;
     None without hipcc"""
-    usage = benchlib.resource_usage("sparse_warp_f16x3.hip")
+    usage = benchlib.resource_usage("plane_pair.hip")
     if usage is None:
         return None
     return [(re.search(r"\d+([a-z_0-9]+_kernel)", u.name).group(1), u.vgprs, u.agprs, u.scratch, u.occupancy) for u in usage]
