@@ -74,6 +74,7 @@ HIP_SOURCES = [
     "corr_lse_bwd_f16x3.hip",
     "corr_topk_bias_f16x3.hip",
     "box3_pair.hip",
+    "box3_lse_bwd_f16x3.hip",
 ]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
              "-Wall", "-Wno-unused-function"]

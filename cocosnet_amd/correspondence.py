@@ -24,9 +24,10 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope, _sparse_scope,
-                       _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3, correspondence_hot_path,
-                       correspondence_match, correspondence_mutual, correspondence_nll, correspondence_sparse, correspondence_sparse_box3,
+from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_box3_scope, _nll_scope, _refine_scope, _restrict_scope,
+                       _sparse_scope, _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
+                       correspondence_hot_path, correspondence_match, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
+                       correspondence_sparse, correspondence_sparse_box3,
                        correspondence_transport)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
@@ -541,6 +542,28 @@ class NoVGGCorrespondence(NetworkBase):
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         coor_out.update(correspondence_nll(theta_raw, phi_raw, target, cfg, temperature, weight=weight, symmetric=symmetric))
+        return coor_out
+
+    def match_loss_box3(self, ref_img, real_img, seg_map, ref_seg_map, target, temperature=0.01, *, weight=None, symmetric=True):
+        """match_loss on the reference's default route, match_kernel 3 (K53, hot_path.correspondence_nll_box3): the same targets, the
+        same dictionary — match_nll, back_nll [B,h,w] (0 where unsupervised), match_lse, back_lse (match()'s, bit for bit),
+        match_target_prob (detached), loss_match, + loss_novgg_featpair where project() makes it — on the box logits of the 3x3-unfolded
+        vectors.  loss_match.backward() reaches the whole network through theta and phi.  The x-box tensor T is kept for the backward
+        and its gradient is allocated there: two HWxHW tensors, the dense match_kernel-3 step's budget.  match_nll is not clamped: on a
+        one-hot row it can come out slightly negative (the target logit is fp32, the lse split-precision).  With no supervised cell
+        the loss is 0 with zero gradients.  Scope: match_kernel 3 with PONO_C on the plain flag set, COCOS_PRECISION=f16x3, equal 64-
+        or 128-wide grids, no prepared exemplar; everything else raises ValueError before the network runs (no fall-back).
+        match_loss(), match(), forward(), sparse_warp_box3() and flow_warp_box3() are unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _nll_box3_scope(cfg, symmetric, False, self.inter_channels)      # out-of-scope flags are refused before the network runs
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("match_loss_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"match_loss_box3: target must be an int32 or int64 tensor, got "
+                            f"{target.dtype if torch.is_tensor(target) else type(target).__name__}")
+        coor_out = {}
+        theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
+        coor_out.update(correspondence_nll_box3(theta_raw, phi_raw, target, cfg, temperature, weight=weight, symmetric=symmetric))
         return coor_out
 
 

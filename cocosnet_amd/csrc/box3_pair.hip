@@ -194,6 +194,59 @@ __global__ __launch_bounds__(BOX3_THREADS) void box3_sparse_bwd_pair_kernel(cons
     }
 }
 
+// ---- K53: the logit head — TopkSet at k = 1 with the pair's logit itself as the output instead of a blend --------------------------
+//   z[b,p] = inv_t a_p b_j (R[p,j] - kc mu_p nu_j),  j = idx[b,p];  a NEGATIVE idx (an unsupervised cell) gives z = 0 and c = 0, and the
+//   pair backward gives it g = hb = dmu = da = 0.  c is kept: the backward's state.  The gathers are K51's (TopkSet{idx, 1}, the
+//   inverse table of the clamped idx): a negative entry rides along as key 0 with a zero coefficient.
+__global__ __launch_bounds__(BOX3_THREADS) void box3_pair_logit_fwd_kernel(const float* __restrict__ th_t, const float* __restrict__ ph_t,
+                                                                           const float* __restrict__ mu, const float* __restrict__ a,
+                                                                           const float* __restrict__ nu, const float* __restrict__ b,
+                                                                           const int* __restrict__ idx, float* __restrict__ z_out,
+                                                                           float* __restrict__ c_out, long long rows, int fh, int fw, int gh,
+                                                                           int gw, float inv_t, float kc) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & (kWave - 1);
+    const long long row = wave_row();                                                 // b * Nq + p
+    if (row >= rows) return;                                                          // (whole waves; the kernel has no barrier)
+    const int Nq = fh * fw, Nk = gh * gw;
+    const long long bq = row / Nq;
+    const int p = (int)(row - bq * Nq), py = p / fw, px = p - py * fw;
+    const int t = __builtin_amdgcn_readfirstlane(idx[row]);
+    float c = 0.f, z = 0.f;
+    if (t >= 0) {
+        const int j = clamp_key(t, Nk), ky = j / gw, kx = j - ky * gw;
+        const long long key = bq * Nk + j;
+        const QueryTaps taps = load_query_taps(th_t, row, py, px, fh, fw, lane);
+        c = pair_R(taps, ph_t, key, ky, kx, gh, gw, lane) - (kc * mu[row]) * nu[key];
+        z = (inv_t * a[row]) * b[key] * c;
+    }
+    if (lane == 0) {
+        z_out[row] = z;
+        c_out[row] = c;
+    }
+}
+
+// one THREAD per query: g = dz inv_t a_p b_j, hb = dz inv_t a_p c, dmu_p = -kc g nu_j, da_p = dz inv_t b_j c (pair_grad).  hb_out,
+// dmu_out, da_out may be null.
+__global__ __launch_bounds__(BOX3_THREADS) void box3_pair_logit_bwd_pair_kernel(const int* __restrict__ idx, const float* __restrict__ c,
+                                                                                const float* __restrict__ a, const float* __restrict__ nu,
+                                                                                const float* __restrict__ b, const float* __restrict__ dz,
+                                                                                float* __restrict__ g_out, float* __restrict__ hb_out,
+                                                                                float* __restrict__ dmu_out, float* __restrict__ da_out,
+                                                                                long long rows, int Nq, int Nk, float inv_t, float kc) {
+#pragma clang fp contract(off)
+    const long long row = (long long)blockIdx.x * BOX3_THREADS + threadIdx.x;
+    if (row >= rows) return;
+    const int t = idx[row];
+    const long long key = (row / Nq) * Nk + clamp_key(t, Nk);
+    const float c_r = c[row];
+    const PairGrad pg = pair_grad(t >= 0 ? dz[row] * inv_t : 0.f, a[row], b[key], c_r);
+    g_out[row] = pg.g;
+    if (hb_out) hb_out[row] = pg.hb;
+    if (dmu_out) dmu_out[row] = -kc * (pg.g * nu[key]);
+    if (da_out) da_out[row] = pg.ab * c_r;
+}
+
 // ---- K52: forward and pair backward -------------------------------------------------------------------------------------------------
 //   m = max z;  lse_win = m + log sum exp(z - m);  p = exp(z - lse_win);  off = (sum p dx, sum p dy) in visiting order, limited to
 //   [-r, r];  c is kept per slot (0 outside the grid): the backward's state
@@ -569,6 +622,36 @@ extern "C" int cocos_box3_sparse_softmax_warp_bwd_key(const float* th_t, const f
     const long long keys = (long long)B * gh * gw;
     hipLaunchKernelGGL(box3_sparse_bwd_key_kernel, dim3(box3_pair_blocks(keys)), dim3(BOX3_THREADS), 0, as_stream(stream), th_t, dout_t, g,
                        hb, w, mu, entries, offsets, dph_t, dv_t, dnu, db, keys, B * fh * fw * k, fh, fw, gh, gw, Cv, k, (float)(9 * BOX3_ROW_C));
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
+
+extern "C" int cocos_box3_pair_logit_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu, const float* b,
+                                         const int* idx, float* z, float* c, int B, int K, int fh, int fw, int gh, int gw,
+                                         float inv_temperature, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "box3_pair_logit_fwd";
+    COCOS_REQUIRE(th_t && ph_t && mu && a && nu && b && idx && z && c, COCOS_ERR_INVALID, "%s: null pointer", name);
+    if (const int rc = box3_pair_check(name, TopkSet{idx, 1}, B, K, fh, fw, gh, gw, 1, inv_temperature)) return rc;
+    for (const void* p : {th_t, ph_t}) COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: the theta / phi rows must be 16-byte aligned", name);
+    const long long rows = (long long)B * fh * fw;
+    hipLaunchKernelGGL(box3_pair_logit_fwd_kernel, dim3(box3_pair_blocks(rows)), dim3(BOX3_THREADS), 0, as_stream(stream), th_t, ph_t, mu, a,
+                       nu, b, idx, z, c, rows, fh, fw, gh, gw, inv_temperature, (float)(9 * BOX3_ROW_C));
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
+
+extern "C" int cocos_box3_pair_logit_bwd_pair(const int* idx, const float* c, const float* a, const float* nu, const float* b, const float* dz,
+                                              float* g, float* hb, float* dmu, float* da, int B, int K, int fh, int fw, int gh, int gw,
+                                              float inv_temperature, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "box3_pair_logit_bwd_pair";
+    COCOS_REQUIRE(idx && c && a && nu && b && dz && g, COCOS_ERR_INVALID, "%s: null pointer", name);
+    if (const int rc = box3_pair_check(name, TopkSet{idx, 1}, B, K, fh, fw, gh, gw, 1, inv_temperature)) return rc;
+    const long long rows = (long long)B * fh * fw;
+    hipLaunchKernelGGL(box3_pair_logit_bwd_pair_kernel, dim3((unsigned)((rows + BOX3_THREADS - 1) / BOX3_THREADS)), dim3(BOX3_THREADS), 0,
+                       as_stream(stream), idx, c, a, nu, b, dz, g, hb, dmu, da, rows, fh * fw, gh * gw, inv_temperature,
+                       (float)(9 * BOX3_ROW_C));
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }

@@ -192,7 +192,7 @@ class _BoxedCorr:
     actually used, T = xbox(C_raw) from the correlation GEMM's epilogue; every softmax + warp pass then reads T three
     blocks at a time (K19).  Nothing box-filtered and no logits matrix reaches HBM."""
 
-    def __init__(self, theta_raw, phi_raw, inv_t, prepared_k=None):
+    def __init__(self, theta_raw, phi_raw, inv_t, prepared_k=None, share_sink=None):
         _, C, self.fh, self.fw = theta_raw.shape
         self.kc = float(C * 9)
         self._cache = {}
@@ -231,7 +231,8 @@ class _BoxedCorr:
         self.th, self.ph, self.inv_t = theta_raw, phi_raw, inv_t
         # round 4: ONE T for both orientations (xbox(C)^T = xbox(C^T): the column pass reads it transposed) and one gradient
         # buffer for all passes over it — no second correlation GEMM, one box adjoint and one pair of GEMMs in the backward
-        self._sink = ops.Box3GradSink() if ops.BOX3_SHARE_T else None
+        # (`share_sink`: None = the ops.BOX3_SHARE_T switch; True: always, for a caller whose passes are made to share one G — K53)
+        self._sink = ops.Box3GradSink() if (ops.BOX3_SHARE_T if share_sink is None else share_sink) else None
 
     def _get(self, name, fn):
         if name not in self._cache:
@@ -264,6 +265,17 @@ class _BoxedCorr:
         if k == 1:
             return ops.box3_match(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows)
         return ops.box3_topk(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
+
+    def stats(self):
+        """((mu, a), (nu, b)) of theta and phi, with autograd where the operands carry it"""
+        return self._get("q", lambda: _unfold3_stats(self.th, self.kc)), self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
+
+    def lse(self, rows: bool):
+        """match(rows)'s lse [B,N] bit for bit, WITH a gradient (K53, ops.box3_lse): the passes over the one T share its gradient sink"""
+        q, kk = self.stats()
+        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+        q, kk = (q, kk) if rows else (kk, q)
+        return ops.box3_lse(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows, sink=self._sink)
 
 
 def _box_sum3(x):
@@ -631,7 +643,8 @@ _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused ma
           "nll": " (the loss runs on the fused match_kernel 1 route)",
           "transport": " (transport runs on the fused match_kernel 1 route)",
           "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)",
-          "flow_box3": " (the box sub-cell flow runs on the match_kernel 3 route)"}
+          "flow_box3": " (the box sub-cell flow runs on the match_kernel 3 route)",
+          "nll_box3": " (the box match loss runs on the match_kernel 3 route)"}
 
 
 def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool, kernel: int = 1):
@@ -1453,10 +1466,9 @@ def _nll_scope(cfg: HotPathConfig, symmetric=True):
     _route_scope(name, cfg, "nll", plain_flags=True, match_fused=False)
 
 
-def _nll_targets(target, weight, B, fh, fw, Nk):
+def _nll_targets(target, weight, B, fh, fw, Nk, name="match_loss"):
     """target [B,h,w] int32 / int64 with values below Nk (negative: unsupervised), weight [B,h,w] fp32 >= 0 or None — TypeError /
-    ValueError in messages that name match_loss"""
-    name = "match_loss"
+    ValueError in messages that name match_loss (`name`: match_loss_box3's)"""
     if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"{name}: target must be an int32 or int64 tensor, got {target.dtype if torch.is_tensor(target) else type(target).__name__}")
     if tuple(target.shape) != (B, fh, fw):
@@ -1516,6 +1528,76 @@ def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperatu
     qn, kn = _operand_planes(theta_raw, phi_raw, planes, detach=False, want_chan=keep)
     tgt = target.reshape(B, N)
     row_nll, col_nll, row_lse, col_lse = ops.corr_pair_nll(qn, kn, tgt, 1.0 / temperature, planes, return_lse=True, check_target=False)
+    return {"match_nll": row_nll.reshape(B, fh, fw), "back_nll": col_nll.reshape(B, fh, fw), "match_lse": row_lse.reshape(B, fh, fw),
+            "back_lse": col_lse.reshape(B, gh, gw), "match_target_prob": torch.exp(-row_nll.detach()).reshape(B, fh, fw),
+            "loss_match": nll_reduce(row_nll, col_nll, tgt, weight, symmetric)}
+
+
+# ---- K53: the supervised match loss on the match_kernel-3 route ----------------------------------------------------------------------
+def _nll_box3_scope(cfg: HotPathConfig, symmetric=True, has_exemplar: bool = False, channels=None):
+    """ValueError for everything outside correspondence_nll_box3's scope (match_kernel 3, PONO_C, the plain flag set,
+    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels), in messages that name match_loss_box3; checked before any tensor is
+    looked at"""
+    name = "match_loss_box3"
+    if not isinstance(symmetric, bool):
+        raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
+    _route_scope(name, cfg, "nll_box3", plain_flags=True, match_fused=False, kernel=3)
+    if has_exemplar:
+        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the loss differentiates phi)")
+    _route_channels(name, "nll_box3", channels)
+
+
+def correspondence_nll_box3(theta_raw, phi_raw, target, cfg: HotPathConfig, temperature=0.01, *, weight=None, symmetric=True, exemplar=None):
+    """correspondence_nll on the reference's default route, match_kernel 3 (K53): with z[p,q] the box logit of the 3x3-unfolded,
+    centred, normalised vectors over the temperature, match_nll = lse_q z[p,.] - z[p,t_p] and back_nll = lse_p z[.,t_p] - z[p,t_p].
+    The two log-sum-exp vectors are read from the one x-box tensor T exactly as correspondence_match reads them (ops.box3_lse: K37's
+    launch; the column direction reads T transposed), the target logit comes from the pair unit on fp32 rows (ops.box3_pair_logits),
+    and the column lse is gathered at the target in a fixed order (ops.box3_gather_keys).  In the backward both lse passes write into
+    ONE gradient of T (cocos_box3_lse_bwd_f16x3 under the Box3GradSink), so one box adjoint and one pair of GEMMs serve them.
+
+    Memory: T is saved for the backward and its gradient G is allocated there — two HWxHW fp32 tensors, the dense match_kernel-3
+    step's budget (unlike correspondence_nll, whose route keeps nothing HWxHW).  Precision: the target logit is formed in fp32 rows,
+    the lse from the f16x3 T, so on a one-hot row match_nll can come out slightly NEGATIVE; it is not clamped.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1, equal grids; target [B,h,w] int32 / int64: flat exemplar position
+    per content cell, negative = unsupervised; weight [B,h,w] fp32 >= 0 or None.  Returns correspondence_nll's dictionary.  With
+    symmetric=False the column direction is out of the loss: back_lse / back_nll are still reported, detached, at the cost of one
+    more forward-only readout launch over T (K37, transposed) — no second lse backward, no accumulate pass.
+
+    Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, the plain flag set, no prepared exemplar, equal 64- or
+    128-wide grids that ops.box3_fused_ok takes: everything else raises ValueError in a message that names match_loss_box3 — there is
+    no fall-back to the materialised chain.  CPU tensors raise CocosHipError."""
+    name = "match_loss_box3"
+    _nll_box3_scope(cfg, symmetric, exemplar is not None)      # before any tensor is looked at
+    _route_channels(name, "nll_box3", theta_raw.shape[1])
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    _fused_width(name, theta_raw, phi_raw)
+    _nll_targets(target, weight, B, fh, fw, Nk, name)
+    if not (_hip_fp32(theta_raw) and _hip_fp32(phi_raw) and target.is_cuda and (weight is None or weight.is_cuda)):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP tensors (fp32 features); the correspondence hot path has no CPU fallback")
+    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw):
+        raise ValueError(f"{name}: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid (equal 64- or "
+                         "128-wide grids, positions a multiple of 256)")
+    inv_t = 1.0 / temperature
+    th, ph = _raw(theta_raw), _raw(phi_raw)      # the fp32 projections the pair unit reads (K0 with autograd; cached by the handle)
+    # T and the statistics as correspondence_match makes them (the lse vectors are its readout's bit for bit), with autograd
+    lazy = isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED
+    boxed = _BoxedCorr(theta_raw if lazy else th, phi_raw if lazy else ph, inv_t, share_sink=True)      # the lse passes share one G
+    (mu, a), (nu, b) = boxed.stats()
+    tgt = target.reshape(B, N)
+    row_lse = boxed.lse(True)
+    col_lse = boxed.lse(False) if symmetric else None
+    z_t = ops.box3_pair_logits(th, ph, mu, a, nu, b, tgt, inv_t)
+    sup = tgt >= 0
+    zero = torch.zeros((), device=z_t.device, dtype=z_t.dtype)
+    row_nll = torch.where(sup, row_lse - z_t, zero)
+    if symmetric:
+        col_nll = torch.where(sup, ops.box3_gather_keys(col_lse, tgt) - z_t, zero)
+    else:
+        with torch.no_grad():
+            col_lse = boxed.match(False)[2]
+            col_nll = torch.where(sup, torch.gather(col_lse, 1, tgt.clamp_min(0).long()) - z_t.detach(), zero)
     return {"match_nll": row_nll.reshape(B, fh, fw), "back_nll": col_nll.reshape(B, fh, fw), "match_lse": row_lse.reshape(B, fh, fw),
             "back_lse": col_lse.reshape(B, gh, gw), "match_target_prob": torch.exp(-row_nll.detach()).reshape(B, fh, fw),
             "loss_match": nll_reduce(row_nll, col_nll, tgt, weight, symmetric)}

@@ -3535,6 +3535,88 @@ def box3_topk(t, mu, a, nu, b, h, w, k_unfolded, scale, k: int, transposed: bool
     return idx, val, lse
 
 
+class _Box3Lse(torch.autograd.Function):
+    """K53.  Forward: box3_match's launch, its lse.  Backward: cocos_box3_lse_bwd_f16x3 writes G = g_lse softmax(z) scale a_p b_q
+    in _Box3SoftmaxWarp's convention and under its Box3GradSink protocol, so T's node runs one K20 and one pair of GEMMs for every
+    pass over T.  Saved: T, the statistics, lse."""
+
+    @staticmethod
+    def forward(ctx, t, mu, a, nu, b, h: int, w: int, kc: float, scale: float, transposed: bool = False, sink=None):
+        ctx.transposed, ctx.sink = bool(transposed), sink
+        B, N = mu.shape
+        idx = torch.empty((B, N), device=t.device, dtype=torch.int32)
+        mx = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        _call("box3_match", "cocos_box3_match_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+              idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(kc), float(scale),
+              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+        ctx.save_for_backward(t, mu, a, nu, b, lse)
+        ctx.cfg = (int(h), int(w), float(kc), float(scale))
+        return lse
+
+    @staticmethod
+    def backward(ctx, g_lse):
+        t, mu, a, nu, b, lse = ctx.saved_tensors
+        h, w, kc, scale = ctx.cfg
+        g_lse = _chk(g_lse, "box3_lse: g_lse")
+        B, N = mu.shape
+        f32 = dict(device=t.device, dtype=torch.float32)
+        sink, flags = ctx.sink, (_C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
+        if not ctx.needs_input_grad[0]:
+            sink = None          # nobody differentiates T through this pass: its G is scratch and must not become — or be added
+                                 # into — the shared buffer (as _Box3SoftmaxWarp)
+        if sink is not None and sink.buf is not None:      # another pass over this T has written its G: add ours to it
+            g, g_ret = sink.buf, None
+            gmax = sink.gmax = _zero_cell(t.device)        # ... and max|G| becomes that of the sum (a fresh cell)
+            flags |= _C["COCOS_BOX3_G_ACCUMULATE"]
+        else:
+            g = g_ret = torch.empty(B * N * N, **f32)
+            gmax = _zero_cell(t.device)
+            if sink is not None:
+                sink.buf, sink.gmax = g, gmax
+                # the buffer belongs to THIS backward (see _Box3SoftmaxWarp): a later backward over a retained graph starts a new G
+                torch.autograd.Variable._execution_engine.queue_callback(sink.reset)
+        dmu, da, dnu, db = (torch.empty((B, N), **f32) for _ in range(4))
+        colpart = torch.empty(_lib.load().cocos_box3_lse_bwd_colpart_bytes(B, N, N) // 4, **f32)
+        _call("box3_lse_bwd", "cocos_box3_lse_bwd_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+              lse.data_ptr(), g_lse.data_ptr(), g.data_ptr(), dmu.data_ptr(), da.data_ptr(), dnu.data_ptr(), db.data_ptr(),
+              colpart.data_ptr(), gmax.data_ptr(), B, N, N, h, w, kc, scale, flags, _stream())
+        if flags & _C["COCOS_BOX3_G_ACCUMULATE"]:
+            # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand
+            torch.autograd.graph.increment_version(g)
+        _remember_amax(g, gmax)      # (an accumulating pass replaces the cell remembered for the shared buffer)
+        if sink is not None and t.numel() * 4 >= BOX3_ALIAS_T_BYTES:
+            sink.t_dead = t          # (only when T's node will take the storage over)
+        if not ctx.needs_input_grad[0]:
+            g_ret = None
+        return g_ret, dmu, da, dnu, db, None, None, None, None, None, None
+
+
+def box3_lse(t, mu, a, nu, b, h, w, k_unfolded, scale, transposed: bool = False, sink: Box3GradSink | None = None):
+    """lse [B,N] = log sum_q exp z[p,q] of box3_match's logits z[p,q] = scale * a_p b_q (ybox(T)[p,q] - k mu_p nu_q), with T from
+    box3_corr_xbox — box3_match's launch and its third output bit for bit — WITH a gradient (K53): the backward writes
+    g_lse[p] softmax(z)[p,q] scale a_p b_q into T's gradient buffer (cocos_box3_lse_bwd_f16x3) and returns the statistics' gradients.
+    `transposed`, `sink` as for box3_softmax_warp: a row pass and a transposed pass over one T that share a Box3GradSink end in one
+    box adjoint and one pair of GEMMs.  T is saved for the backward and G is allocated in it: two HWxHW tensors, the dense route's
+    budget.  CPU tensors raise CocosHipError, the fp32 flavour too; shapes outside cocos_box3_fused_supported raise ValueError."""
+    name = "box3_lse"
+    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
+        if not torch.is_tensor(x) or x.dtype != torch.float32:
+            raise TypeError(f"{name}: {what} must be a float32 tensor")
+    if mu.dim() != 2:
+        raise ValueError(f"{name}: mu is [B,N]")
+    B, N = mu.shape
+    if not (_is_int(h) and _is_int(w)) or N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
+        raise ValueError(f"{name}: shape mismatch")
+    if not scale > 0:
+        raise ValueError(f"{name}: scale={scale!r}: expected a positive number")
+    _gate(name, ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")), True)
+    if not _lib.load().cocos_box3_fused_supported(N, N, 1, h, w):
+        raise ValueError(f"{name}: the fused box route does not take a {h}x{w} grid (64- or 128-wide, positions a multiple of 256)")
+    return _Box3Lse.apply(t.contiguous(), mu.contiguous(), a.contiguous(), nu.contiguous(), b.contiguous(), h, w, float(k_unfolded),
+                          float(scale), transposed, sink)
+
+
 # ------------------------------------------------------------------------------------------
 # K12 statistics of the 3x3-unfolded vectors without unfolding   (correspondence.py:276-280, match_kernel 3)
 # ------------------------------------------------------------------------------------------
@@ -3783,6 +3865,117 @@ def box3_soft_match_offset(theta_raw, phi_raw, mu, a, nu, b, idx, grid, kgrid, i
         raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
     operands = _box3_pair_gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")), stats, idx, (B, Nq), Nk)
     return _Box3SoftMatchOffset.apply(*operands, float(inv_rt), radius, fh, fw, gh, gw)
+
+
+# K53  the pair unit at one candidate per query with the logit itself as the output: the target logit of the match loss
+class _Box3PairLogits(torch.autograd.Function):
+    """Saved for the backward: the position-major copies of theta and phi, idx [B,Nq], c [B,Nq] and the four statistics — nothing
+    with an Nq x Nk extent."""
+
+    @staticmethod
+    def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, idx, inv_t: float):
+        B, K, fh, fw = theta_raw.shape
+        gh, gw = phi_raw.shape[2:]
+        Nq, Nk = fh * fw, gh * gw
+        th_t, ph_t = _transpose(theta_raw.reshape(B, K, Nq)), _transpose(phi_raw.reshape(B, K, Nk))
+        z, c = (torch.empty((B, Nq), device=th_t.device, dtype=torch.float32) for _ in range(2))
+        _call("box3_pair_logit_fwd", "cocos_box3_pair_logit_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(), a.data_ptr(),
+              nu.data_ptr(), b.data_ptr(), idx.data_ptr(), z.data_ptr(), c.data_ptr(), B, K, fh, fw, gh, gw, float(inv_t), _stream())
+        ctx.save_for_backward(th_t, ph_t, idx, c, mu, a, nu, b)
+        ctx.cfg = (fh, fw, gh, gw, float(inv_t))
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        th_t, ph_t, idx, c, mu, a, nu, b = ctx.saved_tensors
+        needs = ctx.needs_input_grad[:6]
+        fh, fw, gh, gw, inv_t = ctx.cfg
+        B, Nq, K = th_t.shape
+        Nk = ph_t.shape[1]
+        if not any(needs):
+            return (None,) * 8
+        dz = _chk(dz, "box3_pair_logits: dz")
+        dims = (B, K, fh, fw, gh, gw)
+        with torch.no_grad():
+            table = idx.clamp(0, Nk - 1)      # what the gathers see: a negative (unsupervised) entry rides along with g = 0
+        sparse = "box3_sparse_softmax_warp_bwd_"
+        pair = lambda *out: _call("box3_pair_logit_bwd_pair", "cocos_box3_pair_logit_bwd_pair", idx.data_ptr(), c.data_ptr(), a.data_ptr(),
+                                  nu.data_ptr(), b.data_ptr(), dz.data_ptr(), *out, *dims, inv_t, _stream())
+        theta = lambda g, dth_t: _call(sparse + "theta", f"cocos_{sparse}theta", ph_t.data_ptr(), table.data_ptr(), g, dth_t, *dims, 1,
+                                       _stream())
+        key = lambda g, hb, entries, offsets, dph_t, _dv_t, dnu, db: _call(sparse + "key", f"cocos_{sparse}key", th_t.data_ptr(), 0, g, hb, 0,
+                                                                           mu.data_ptr(), entries, offsets, dph_t, 0, dnu, db, *dims, 1, 1,
+                                                                           _stream())
+        dth, dph, *rest = _box3_pair_backward(needs + (False,), th_t, ph_t, table.view(B, Nq, 1), 1, pair, theta, key)
+        return (None if dth is None else dth.reshape(B, K, fh, fw), None if dph is None else dph.reshape(B, K, gh, gw), *rest[:4], None, None)
+
+
+def box3_pair_logits(theta_raw, phi_raw, mu, a, nu, b, idx, inv_temperature: float):
+    """z [B,fh*fw] fp32: z[b,p] = inv_temperature * a_p * b_j * (R[p,j] - 9*256 * mu_p * nu_j) for j = idx[b,p] —
+    box3_sparse_softmax_warp's logit of one pair per query, itself the output (K53: the target logit of the match loss), with gradients
+    for theta_raw, phi_raw, mu, a, nu and b (each computed only when needed; idx is data).  A NEGATIVE idx gives 0 with zero
+    gradients; values at or above gh*gw are clamped into the grid.  theta_raw [B,256,fh,fw], phi_raw [B,256,gh,gw] fp32, any grids;
+    (mu, a) [B,fh*fw], (nu, b) [B,gh*gw] as unfold3_stats returns them; idx [B,fh*fw] (or [B,fh,fw]) int32 / int64.  Nothing Nq x Nk
+    is allocated; the gradients are gathered in a fixed order over the inverse table of idx (no atomics: bitwise reproducible)."""
+    name = "box3_pair_logits"
+    idx = _int_table(name, "idx", idx)
+    if theta_raw.dim() != 4 or phi_raw.dim() != 4:
+        raise ValueError(f"{name}: expected theta_raw [B,256,fh,fw] and phi_raw [B,256,gh,gw]; got {tuple(theta_raw.shape)}, "
+                         f"{tuple(phi_raw.shape)}")
+    B, K, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    Nq, Nk = fh * fw, gh * gw
+    if phi_raw.shape[:2] != (B, K) or B < 1 or Nq < 1 or Nk < 1:
+        raise ValueError(f"{name}: shape mismatch theta_raw{tuple(theta_raw.shape)} phi_raw{tuple(phi_raw.shape)}")
+    if K != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
+    if not inv_temperature > 0:
+        raise ValueError(f"{name}: inv_temperature={inv_temperature!r}: expected a positive number")
+    stats = _box3_stats(name, B, Nq, Nk, mu, a, nu, b)
+    if idx.dim() < 1 or idx.shape[0] != B or idx.numel() != B * Nq:
+        raise ValueError(f"{name}: idx is {tuple(idx.shape)}, expected {B} x {Nq} entries")
+    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + stats + ((idx, "idx"),), False)
+    floats = [_chk(t, f"{name}: {what}") for t, what in ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + stats]
+    return _Box3PairLogits.apply(*floats, idx.reshape(B, Nq), float(inv_temperature))
+
+
+class _GatherKeys(torch.autograd.Function):
+    """x[b, idx[b,p]] with a backward that is a GATHER in a fixed order: the key kernel of the pair unit at one channel — its dv output
+    sums w over the inverse table's list of every key, with w the upstream gradient and dout = 1 (exact products)."""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        ctx.save_for_backward(idx)
+        ctx.nk = x.shape[1]
+        return torch.where(idx >= 0, torch.gather(x, 1, idx.clamp_min(0).long()), torch.zeros((), device=x.device, dtype=x.dtype))
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        B, Nq = idx.shape
+        Nk = ctx.nk
+        dy = _chk(dy, "box3_gather_keys: dy")
+        w = torch.where(idx >= 0, dy, torch.zeros((), device=dy.device, dtype=dy.dtype)).contiguous()
+        ones = torch.ones((B, Nq), device=dy.device, dtype=torch.float32)
+        entries, offsets = _inverse_index_table(idx.clamp(0, Nk - 1).view(B, Nq, 1), Nk)
+        dx = torch.empty((B, Nk), device=dy.device, dtype=torch.float32)
+        name = "box3_sparse_softmax_warp_bwd_key"
+        _call(name, f"cocos_{name}", 0, ones.data_ptr(), 0, 0, w.data_ptr(), 0, entries.data_ptr(), offsets.data_ptr(), 0, dx.data_ptr(), 0, 0,
+              B, FUSED_K, 1, Nq, 1, Nk, 1, 1, _stream())
+        return dx, None
+
+
+def box3_gather_keys(x, idx):
+    """y [B,Nq] = x[b, idx[b,p]] for x [B,Nk] fp32 on the GPU and idx [B,Nq] int32 / int64 below Nk (a negative entry gives 0 and no
+    gradient).  The gradient of x is gathered over the inverse table of idx in table order — no index_add_, no atomics: bitwise
+    reproducible (K53: the column lse at the target)."""
+    name = "box3_gather_keys"
+    idx = _int_table(name, "idx", idx)
+    if x.dim() != 2 or idx.dim() != 2 or idx.shape[0] != x.shape[0]:
+        raise ValueError(f"{name}: expected x [B,Nk] and idx [B,Nq]; got {tuple(x.shape)}, {tuple(idx.shape)}")
+    _gate(name, ((x, "x"), (idx, "idx")), False)
+    x = _chk(x, f"{name}: x")
+    return _GatherKeys.apply(x, idx)
 
 
 # ------------------------------------------------------------------------------------------

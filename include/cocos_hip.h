@@ -1087,6 +1087,26 @@ int cocos_box3_softmax_warp_bwd_f16x3(const float* t_blocked, const float* mu_q,
 int cocos_box3_adjoint_planes_f16x3(const float* g_blocked, const float* gmax_dev, void* dc_hi, void* dc_lo,
                                     float* scale_out_dev, int B, int Nq, int Nk, int grid_h, int grid_w,
                                     cocos_stream_t stream);
+/* K53 — the adjoint of cocos_box3_match_f16x3's log-sum-exp (box3_lse_bwd_f16x3.hip): with lse [B,Nq] that kernel's third output on
+ *     the same arguments and g_lse [B,Nq] the upstream gradient on it (any magnitude; null = all zero),
+ *         w[p,q] = g_lse[p] exp(z[p,q] - lse[p])        (z formed from T as cocos_box3_match_f16x3 forms it, bit for bit; the
+ *                                                        difference is rounded once and clamped at 0 from above: |w| <= |g_lse|)
+ *     and the outputs are those of cocos_box3_softmax_warp_bwd_f16x3 with w in the place of its L, in the same convention:
+ *         g_blocked = w scale a_p b_q = dloss / d ybox(T)[p,q], fp32, unscaled, tile-blocked like the STORED T (so that
+ *                     cocos_box3_adjoint_planes_f16x3 and the two cocos_hgemm_f16x3 launches follow unchanged),
+ *         dmu, da [B,Nq] (row sums), dnu, db [B,Nk] (column sums: per-workgroup partials in `colpart`, folded in workgroup order by a
+ *         second launch), *gmax_dev = max|g_blocked| (written, not accumulated: the cell need not be zeroed).
+ *     colpart: cocos_box3_lse_bwd_colpart_bytes(B, Nq, Nk) bytes (the column partials and one maximum per wave), 16-byte aligned.
+ *     flags: COCOS_BOX3_T_TRANSPOSED (the column direction on the row pass's T; g_blocked in the layout of the stored T) and
+ *     COCOS_BOX3_G_ACCUMULATE (g_blocked holds another pass's G: this one is added, *gmax_dev receives max|sum|), as for
+ *     cocos_box3_softmax_warp_bwd_f16x3; any other bit is COCOS_ERR_INVALID.  Supported: exactly
+ *     cocos_box3_fused_supported(Nq, Nk, 1, grid_h, grid_w), else COCOS_ERR_UNSUPPORTED with nothing launched.  T, G, nu, b, colpart
+ *     16-byte aligned.  No atomics, every sum in a fixed order: bitwise reproducible. */
+size_t cocos_box3_lse_bwd_colpart_bytes(int B, int Nq, int Nk);
+int cocos_box3_lse_bwd_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                             const float* lse, const float* g_lse /* nullable */, float* g_blocked, float* dmu, float* da, float* dnu,
+                             float* db, void* colpart, float* gmax_dev, int B, int Nq, int Nk, int grid_h, int grid_w,
+                             float k_unfolded, float scale, int flags, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * K12 statistics of the zero-padded 3x3-unfolded, centred feature vectors without unfolding (match_kernel 3 with
@@ -1426,6 +1446,21 @@ int cocos_box3_sparse_softmax_warp_bwd_key(const float* th_t, const float* dout_
                                            const float* mu, const int* entries, const int* offsets, float* dph_t /* nullable */,
                                            float* dv_t /* nullable */, float* dnu /* nullable */, float* db /* nullable */, int B, int K,
                                            int fh, int fw, int gh, int gw, int Cv, int k, cocos_stream_t stream);
+/* K53 — the logit head of the same pair unit (TopkSet at k = 1): the pair's logit itself, for the supervised match loss.
+ *   cocos_box3_pair_logit_fwd: one wave per query; idx [B,Nq] int32; z[b,p] = inv_temperature a_p b_j (R[p,j] - kc mu_p nu_j) and
+ *       c[b,p] = R[p,j] - kc mu_p nu_j for j = idx[b,p] (values at or above Nk are clamped into the grid); a NEGATIVE idx gives
+ *       z = c = 0 (an unsupervised cell).  z, c [B,Nq] fp32.
+ *   cocos_box3_pair_logit_bwd_pair: one thread per query; from dz [B,Nq] writes g [B,Nq] = dz inv_temperature a_p b_j and, each
+ *       unless null, hb = dz inv_temperature a_p c, dmu = -kc g nu_j, da = dz inv_temperature b_j c; all 0 where idx is negative.
+ *       g / hb then go through cocos_box3_sparse_softmax_warp_bwd_theta and _bwd_key at k = 1 (the inverse table of the idx clamped
+ *       into [0, Nk): a negative entry rides along with a zero coefficient).
+ *   Refusals as the K51 entry points at k = 1. */
+int cocos_box3_pair_logit_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu, const float* b,
+                              const int* idx, float* z, float* c, int B, int K, int fh, int fw, int gh, int gw, float inv_temperature,
+                              cocos_stream_t stream);
+int cocos_box3_pair_logit_bwd_pair(const int* idx, const float* c, const float* a, const float* nu, const float* b, const float* dz,
+                                   float* g, float* hb /* nullable */, float* dmu /* nullable */, float* da /* nullable */, int B, int K,
+                                   int fh, int fw, int gh, int gw, float inv_temperature, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * K43 PatchMatch candidate search for the k-sparse warp (patchmatch_f16x3.hip): ONE Jacobi iteration per call — a second selector
