@@ -25,10 +25,10 @@ from torch.nn import init
 
 from . import inference, ops
 from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_box3_scope, _nll_scope, _refine_scope, _restrict_scope,
-                       _sparse_scope, _sparse_search, _topk_arg, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
+                       _sparse_scope, _sparse_search, _topk_arg, _transport_box3_scope, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
                        correspondence_hot_path, correspondence_match, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
                        correspondence_sparse, correspondence_sparse_box3,
-                       correspondence_transport)
+                       correspondence_transport, correspondence_transport_box3)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
 
 _EPS = __import__("sys").float_info.epsilon
@@ -463,21 +463,52 @@ class NoVGGCorrespondence(NetworkBase):
                                               search_opts=search_opts, **kw))
         return coor_out
 
-    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4):
+    def transport_match_box3(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, iters=5, tau=1.0, topk=1, hard_warp=False):
+        """transport_match on the reference's default route, match_kernel 3 (K54, hot_path.correspondence_transport_box3): the Sinkhorn
+        iteration runs on the one x-box tensor T of the box logits — one correlation GEMM, 2 iters + 1 streaming reads of T — and every
+        content position reads the row of z + g.  One projection of the network, under torch.no_grad(); one HWxHW tensor alive at a
+        time, none after return.  Returns transport_match's keys: match_index [B,h,w] int64 ([B,k,h,w] with topk = k > 1), match_xy,
+        match_prob, match_lse, potential_q, potential_k, match_mass, key_mass, and with `hard_warp` warp_hard (topk > 1: also
+        warp_topk).  Scope: match_kernel 3 with PONO_C on the plain flag set, COCOS_PRECISION=f16x3, no prepared exemplar; everything
+        else raises a ValueError naming box transport before the network runs.  transport_match() is unaffected."""
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        k, iters, tau = _transport_box3_scope("transport_match_box3", cfg, iters, tau, topk, False, self.inter_channels)
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("transport_match_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        with torch.no_grad():
+            theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
+            res = correspondence_transport_box3(theta_raw, phi_raw, cfg, temperature, iters=iters, tau=tau, topk=k)
+            m = res.pop("readout")
+            out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse, **res}
+            if hard_warp and k == 1:
+                fh, fw = m.index.shape[1:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+            elif hard_warp:
+                fh, fw = m.index.shape[2:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)
+                out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, torch.softmax(m.logit, dim=1), fh, fw, self.opt.down)
+        return out
+
+    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, transport=None):
         """sparse_warp on the reference's default route, match_kernel 3 (K51, hot_path.correspondence_sparse_box3): per content position
         the `topk` best exemplar positions are selected without gradient, as match(topk=topk) selects them, and a softmax over those k
         box logits alone blends the pooled exemplar (and, under --warp_mask_losstype direct, the exemplar's labels), with gradients to
         the whole network through theta and phi and nothing HWxHW kept for the backward.  Returns sparse_warp's dictionary: {warp_out
         [B,3,H,W], warp_mask [B,nc,h,w] (direct), match_index [B,k,h,w] int64, match_weight [B,k,h,w]} (+ loss_novgg_featpair where
         project() makes it).  Scope: match_kernel 3 with PONO_C on the plain flag set; everything else raises ValueError before the
-        network runs (no fall-back).  forward(), match() and sparse_warp() are unaffected."""
+        network runs (no fall-back).  forward(), match() and sparse_warp() are unaffected.  `transport` (K54; None changes nothing):
+        dict(iters=, tau=) — the candidates are the top-k of the box transport plan's rows and the blend is the biased softmax over
+        them, with the Sinkhorn potentials detached; the result gains potential_k and match_mass."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
         _box3_scope("sparse_warp_box3", "sparse_box3", cfg, False, self.inter_channels, topk=topk)      # refused before the network runs
+        if transport is not None:
+            _transport_dict("sparse_warp_box3", transport)
         if ref_img is None or ref_seg_map is None:
             raise ValueError("sparse_warp_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
-        coor_out.update(correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk))
+        kw = {} if transport is None else {"transport": transport}
+        coor_out.update(correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, **kw))
         return coor_out
 
     def flow_warp(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, radius=1, refine_temperature=None):

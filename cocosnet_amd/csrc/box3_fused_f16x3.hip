@@ -100,31 +100,46 @@ __device__ __forceinline__ void bx_fetch(BxTile& tl, const BxGeom& gm, int t, in
 // every tile then reads its 2 x 16 values per lane as broadcast 16-byte LDS reads.  (Round-3 ablation: fetching them from
 // global memory per tile — 8 buffer loads whose 32 lanes share an address — cost 0.06 ms of the 0.46 ms backward.)
 // (`cap` = floats per array of the LDS buffer, `n` <= cap = keys staged)
+// NPL = 3 (K54, the BIAS readout): a third plane [b | kn | bias] takes the caller's additive per-key term as it is; every other kernel
+// is NPL = 2 and neither sees the plane nor pays for it.
+// (the two-plane callers use the overloads without a bias below; an NPL = 3 call has no default for the pointer: leaving it out does
+//  not compile)
+template <int NPL>
 __device__ __forceinline__ void bx_stage_stats(float* kstat, const float* __restrict__ b_k, const float* __restrict__ nu_k,
-                                               int cap, int n, float kc, int tid) {
+                                               int cap, int n, float kc, int tid, const float* __restrict__ k_bias) {
     for (int i = tid; i < n; i += 256) {
         const float bq = b_k[i];
         kstat[i] = bq;
         kstat[cap + i] = kc * nu_k[i] * bq;
+        if constexpr (NPL == 3) kstat[2 * cap + i] = k_bias[i];
     }
 }
+__device__ __forceinline__ void bx_stage_stats(float* kstat, const float* __restrict__ b_k, const float* __restrict__ nu_k,
+                                               int cap, int n, float kc, int tid) {
+    bx_stage_stats<2>(kstat, b_k, nu_k, cap, n, kc, tid, nullptr);
+}
 // chunked flavour: behind the barrier that ended tile t - 1; stages the chunk AFTER the one tile t opens
+template <bool CHUNKED, int NPL>
+__device__ __forceinline__ void bx_stage_next_chunk(float* kstat, const float* __restrict__ b_k, const float* __restrict__ nu_k,
+                                                    int t, int ntiles, float kc, int tid, const float* __restrict__ k_bias) {
+    if (CHUNKED && (t & (BX_TCH - 1)) == 0 && t + BX_TCH < ntiles) {
+        const int c1 = t / BX_TCH + 1;
+        bx_stage_stats<NPL>(kstat + (c1 & 1) * NPL * BX_KCH, b_k + c1 * BX_KCH, nu_k + c1 * BX_KCH, BX_KCH,
+                            min(BX_KCH, ntiles * 32 - c1 * BX_KCH), kc, tid, NPL == 3 ? k_bias + c1 * BX_KCH : nullptr);
+    }
+}
 template <bool CHUNKED>
 __device__ __forceinline__ void bx_stage_next_chunk(float* kstat, const float* __restrict__ b_k, const float* __restrict__ nu_k,
                                                     int t, int ntiles, float kc, int tid) {
-    if (CHUNKED && (t & (BX_TCH - 1)) == 0 && t + BX_TCH < ntiles) {
-        const int c1 = t / BX_TCH + 1;
-        bx_stage_stats(kstat + (c1 & 1) * 2 * BX_KCH, b_k + c1 * BX_KCH, nu_k + c1 * BX_KCH, BX_KCH,
-                       min(BX_KCH, ntiles * 32 - c1 * BX_KCH), kc, tid);
-    }
+    bx_stage_next_chunk<CHUNKED, 2>(kstat, b_k, nu_k, t, ntiles, kc, tid, nullptr);
 }
 
 // tt[r] = b_q * (T_sum) - mu_p * kc * nu_q * b_q  (the logit without its per-query factor scale * a_p); also returns
 // b_q and kn_q per register for the backward.
-template <bool CHUNKED>
+template <bool CHUNKED, int NPL = 2>
 __device__ __forceinline__ void bx_logits(const BxTile& tl, const BxGeom& gm, int t, int h, float mu_p, float (&tt)[16],
                                           float (&bq)[16], float (&kn)[16], int lane_c) {
-    const float* ks = gm.kstat + (CHUNKED ? ((t / BX_TCH) & 1) * 2 * BX_KCH + (t & (BX_TCH - 1)) * 32 : t * 32);
+    const float* ks = gm.kstat + (CHUNKED ? ((t / BX_TCH) & 1) * NPL * BX_KCH + (t & (BX_TCH - 1)) * 32 : t * 32);
     float ts[16];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -143,6 +158,21 @@ __device__ __forceinline__ void bx_logits(const BxTile& tl, const BxGeom& gm, in
             kn[r] = k4[e];
             tt[r] = __builtin_fmaf(bq[r], ts[r], -(mu_p * kn[r]));
         }
+    }
+}
+
+// K54: tt[r] += bias[key of r] * inv_an — the third plane of the staged statistics in bx_logits' pattern (four broadcast 16-byte LDS
+// reads per lane and tile), one fma per element.  Register r of the tile is the PROBLEM's key 32t + 8g + 4h + e also when T is read
+// transposed (bx_logits has been through bx_transpose32 by then).
+template <bool CHUNKED>
+__device__ __forceinline__ void bx_add_bias(const BxGeom& gm, int t, int h, float inv_an, float (&tt)[16]) {
+    constexpr int NPL = 3;      // the BIAS layout: [b | kn | bias], the bias in plane NPL - 1
+    const float* ks = gm.kstat + (NPL - 1) * gm.nk + (CHUNKED ? ((t / BX_TCH) & 1) * NPL * BX_KCH + (t & (BX_TCH - 1)) * 32 : t * 32);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 k4 = *reinterpret_cast<const f32x4*>(ks + 8 * g + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tt[4 * g + e] = __builtin_fmaf(k4[e], inv_an, tt[4 * g + e]);
     }
 }
 
@@ -398,13 +428,25 @@ __device__ __forceinline__ float bx_match_sum2(float l, float e, float ol, float
     return x + y;
 }
 
-template <int K, bool CHUNKED>
+// K54, BIAS: the readout of z'[p,q] = z[p,q] + k_bias[b,q] (one half-step of a log-domain Sinkhorn iteration with the other side's
+// potential as the bias; a key mask is the bias 0 / -inf).  The state lives in the tt domain (z = tt * a_n, a_n the QUERY's factor), and a
+// per-key term does not commute with that factor: it enters as tt += bias / a_n, one fma per element with 1 / a_n formed once per
+// lane, right behind bx_logits — before the tile maximum, the list and the sum, all of which are the statements below unchanged.  A
+// bias of zeros leaves every register as it was: the three outputs are the unbiased instantiation's bit for bit.  -inf excludes a key
+// (fma(-inf, positive, finite) = -inf: it never passes a strict compare and adds 2^-inf = 0); a row with every key excluded keeps
+// m = -inf, r = 0, l = 0 and comes out with val = -inf, lse = log2(0) = -inf and the index 0.  Two selects, BIAS only, keep the
+// rescales of a side that has seen nothing away from 0 * 2^(0 - r) = 0 * inf when the first finite maximum lies below -128 in log2
+// units (a strongly negative potential; without a bias the logits are bounded by scale): they pick the same bits wherever the
+// unguarded product was finite.  The bias is the third plane of the staged statistics (NPL = 3); +inf and NaN are not sanitised.
+template <int K, bool CHUNKED, bool BIAS = false>
 __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const float* __restrict__ T, const float* __restrict__ mu_q, const float* __restrict__ a_q,
     const float* __restrict__ nu_k, const float* __restrict__ b_k, int* __restrict__ idx_out, float* __restrict__ max_out,
-    float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags, int k_out) {
+    float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags, int k_out,
+    const float* __restrict__ k_bias) {
+    constexpr int NPL = BIAS ? 3 : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char bx_smem[];
-    float* const kstat = reinterpret_cast<float*>(bx_smem);      // [b | kn][Nk] (x 2 buffers when chunked), then the XT images
+    float* const kstat = reinterpret_cast<float*>(bx_smem);      // [b | kn (| bias)][Nk] (x 2 buffers when chunked), then the XT images
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform for the compiler too: see the forward)
@@ -415,7 +457,8 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const int i_lane = q0 + wave * 32 + c;
     const float* const bk_b = b_k + (size_t)b * Nk;
     const float* const nu_b = nu_k + (size_t)b * Nk;
-    bx_stage_stats(kstat, bk_b, nu_b, CHUNKED ? BX_KCH : Nk, CHUNKED ? BX_KCH : Nk, kc, tid);
+    const float* const bias_b = BIAS ? k_bias + (size_t)b * Nk : nullptr;
+    bx_stage_stats<NPL>(kstat, bk_b, nu_b, CHUNKED ? BX_KCH : Nk, CHUNKED ? BX_KCH : Nk, kc, tid, bias_b);
 
     BxGeom gm;
     gm.t_rs = make_rsrc(T + (size_t)b * Nk * Nq, (size_t)Nk * Nq * 4);
@@ -428,11 +471,12 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     gm.himg = himg;
     gm.nqblk = Nq >> 5;
     gm.lane_off = (unsigned)lane * 16u;
-    gm.xt = (flags & BX_FLAG_TRANSPOSED) ? kstat + (CHUNKED ? 4 * BX_KCH : 2 * Nk) + wave * BX_XT_FLOATS : nullptr;
+    gm.xt = (flags & BX_FLAG_TRANSPOSED) ? kstat + (CHUNKED ? 2 * NPL * BX_KCH : NPL * Nk) + wave * BX_XT_FLOATS : nullptr;
 
     const float mu_p = mu_q[(size_t)b * Nq + i_lane];
     const float a_n = a_q[(size_t)b * Nq + i_lane] * scale;      // natural-domain factor: z = tt * a_n
     const float a2 = a_n * kLog2e;
+    [[maybe_unused]] const float inv_an = BIAS ? 1.0f / a_n : 0.f;      // the bias in the tt domain: bias / a_n
 
     float m_run = -INFINITY, r_run = 0.f, l_run = 0.f;      // r_run = m_run * a2 (0 while nothing was seen)
     int i_run = 0;                // K == 1
@@ -447,9 +491,10 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
 
     auto do_tile = [&](int t, BxTile& tl) __attribute__((always_inline)) {
         if (CHUNKED && t > 0 && (t & (BX_TCH - 1)) == 0) __syncthreads();      // a chunk opens: see above
-        bx_stage_next_chunk<CHUNKED>(kstat, bk_b, nu_b, t, ntiles, kc, tid);
+        bx_stage_next_chunk<CHUNKED, NPL>(kstat, bk_b, nu_b, t, ntiles, kc, tid, bias_b);
         float tt[16], bq[16], kn[16];
-        bx_logits<CHUNKED>(tl, gm, t, h, mu_p, tt, bq, kn, c);
+        bx_logits<CHUNKED, NPL>(tl, gm, t, h, mu_p, tt, bq, kn, c);
+        if constexpr (BIAS) bx_add_bias<CHUNKED>(gm, t, h, inv_an, tt);
         bx_fetch(tl, gm, t + 2, ntiles);
         float tmax = tt[0];
 #pragma unroll
@@ -469,7 +514,8 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
                 i_run = t * 32 + 8 * (at >> 2) + 4 * h + (at & 3);      // register r = 4g + e of lane (h, c) is key 32t + 8g + 4h + e
             }
             const float r_new = bx_match_ref(tmax, a2);
-            l_run *= fast_exp2(r_run - r_new);                      // (the first move: l_run is 0)
+            if constexpr (BIAS) l_run = m_run == -INFINITY ? 0.f : l_run * fast_exp2(r_run - r_new);
+            else l_run *= fast_exp2(r_run - r_new);                 // (the first move: l_run is 0)
             m_run = tmax;
             r_run = r_new;
         }
@@ -493,7 +539,12 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
         const int oi = __shfl_xor(i_run, 32, 64);
         const bool take_o = om > m_run || (om == m_run && oi < i_run);
         const float ref = om > m_run ? orr : r_run;               // (equal maxima have equal references: a2 is the query's)
-        l_run = bx_match_sum2(l_run, fast_exp2(r_run - ref), ol, fast_exp2(orr - ref));      // (a side that saw nothing has l = 0, r = 0)
+        float e_own = fast_exp2(r_run - ref), e_oth = fast_exp2(orr - ref);
+        if constexpr (BIAS) {      // a side that saw nothing but excluded keys: its l = 0 must not meet 2^(0 - ref) = inf
+            e_own = m_run == -INFINITY ? 0.f : e_own;
+            e_oth = om == -INFINITY ? 0.f : e_oth;
+        }
+        l_run = bx_match_sum2(l_run, e_own, ol, e_oth);      // (a side that saw nothing has l = 0, r = 0)
         i_run = take_o ? oi : i_run;
         m_run = fmaxf(m_run, om);
         r_run = ref;
@@ -1141,17 +1192,20 @@ static int check_box3_readout(const char* name, const float* t_blocked, const fl
     return COCOS_OK;
 }
 
-template <int K>
+// BIAS (K54): three staged planes instead of two — 12 Nk bytes up to 4096 keys, 48 KB for the ring — plus the 18 KB of images when
+// transposed: 66 KB at most, two workgroups per CU.
+template <int K, bool BIAS = false>
 static int launch_box3_readout(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
                                int* idx_out, float* val_out, float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w,
-                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream) {
+                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream, const float* k_bias = nullptr) {
     const bool chunked = Nk > 2 * BX_KCH;
-    const size_t smem = (size_t)(chunked ? 4 * BX_KCH : 2 * Nk) * sizeof(float) +
+    constexpr int NPL = BIAS ? 3 : 2;
+    const size_t smem = (size_t)(chunked ? 2 * NPL * BX_KCH : NPL * Nk) * sizeof(float) +
                         ((flags & BX_FLAG_TRANSPOSED) ? (size_t)4 * BX_XT_FLOATS * sizeof(float) : 0);
-    auto kern = chunked ? box3_topk_kernel<K, true> : box3_topk_kernel<K, false>;
+    auto kern = chunked ? box3_topk_kernel<K, true, BIAS> : box3_topk_kernel<K, false, BIAS>;
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(kern, dim3(B * (Nq / 128)), dim3(256), smem, as_stream(stream), t_blocked, mu_q, a_q, nu_k, b_k, idx_out,
-                       val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags, k);
+                       val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags, k, k_bias);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }
@@ -1220,6 +1274,25 @@ extern "C" int cocos_box3_topk_f16x3(const float* t_blocked, const float* mu_q, 
     if (k == 2) return launch_box3_readout<2>(COCOS_ARGS);
     if (k <= 4) return launch_box3_readout<4>(COCOS_ARGS);
     return launch_box3_readout<8>(COCOS_ARGS);
+#undef COCOS_ARGS
+}
+
+extern "C" int cocos_box3_topk_bias_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
+                                          const float* b_k, const float* k_bias, int* idx_out, float* val_out, float* lse_out, int B,
+                                          int Nq, int Nk, int grid_h, int grid_w, float k_unfolded, float scale, int k, int flags,
+                                          cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "box3_topk_bias_f16x3";
+    COCOS_REQUIRE(k_bias, COCOS_ERR_INVALID, "%s: null pointer (k_bias)", name);
+    if (const int rc = check_box3_readout(name, t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h, grid_w, scale,
+                                          k, flags))
+        return rc;
+    COCOS_REQUIRE(aligned16(k_bias), COCOS_ERR_INVALID, "%s: k_bias must be 16-byte aligned", name);
+#define COCOS_ARGS t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, k, flags, stream, k_bias
+    if (k == 1) return launch_box3_readout<1, true>(COCOS_ARGS);
+    if (k == 2) return launch_box3_readout<2, true>(COCOS_ARGS);
+    if (k <= 4) return launch_box3_readout<4, true>(COCOS_ARGS);
+    return launch_box3_readout<8, true>(COCOS_ARGS);
 #undef COCOS_ARGS
 }
 

@@ -87,13 +87,18 @@ struct WindowSet {
 
 // ---- K51: forward and pair backward -------------------------------------------------------------------------------------------------
 //   w = softmax over r of z[p, j_r],   out^T[p] = sum_r w_r v^T[j_r];   c_r is kept: the backward's state
+// BIAS (K54): w = softmax over r of z[p, j_r] + k_bias[b, j_r] — a flag on this one body, not a second unit; the bias is a constant of the
+// softmax, so c, the saved w and the three backward entries serve both flavours.  A bias of zeros adds 0 to a rounded product: the bits
+// of the unbiased forward.
+template <bool BIAS>
 __global__ __launch_bounds__(BOX3_THREADS) void box3_sparse_fwd_kernel(const float* __restrict__ th_t, const float* __restrict__ ph_t,
                                                                        const float* __restrict__ mu, const float* __restrict__ a,
                                                                        const float* __restrict__ nu, const float* __restrict__ b,
                                                                        const float* __restrict__ vt, const int* __restrict__ idx,
                                                                        float* __restrict__ out_t, float* __restrict__ w_out,
                                                                        float* __restrict__ c_out, long long rows, int fh, int fw, int gh,
-                                                                       int gw, int Cv, int k, float inv_t, float kc) {
+                                                                       int gw, int Cv, int k, float inv_t, float kc,
+                                                                       const float* __restrict__ k_bias) {
     const int lane = threadIdx.x & (kWave - 1);
     const long long row = (long long)blockIdx.x * BOX3_WAVES + (threadIdx.x >> 6);    // b * Nq + p
     if (row >= rows) return;                                                          // (whole waves; the kernel has no barrier)
@@ -116,6 +121,7 @@ __global__ __launch_bounds__(BOX3_THREADS) void box3_sparse_fwd_kernel(const flo
             const float c = pair_R(taps, ph_t, key[r], qy, qx, gh, gw, lane) - kmu * nu[key[r]];
             if (lane == r) c_out[row * k + r] = c;
             s[r] = za * b[key[r]] * c;
+            if constexpr (BIAS) s[r] = s[r] + k_bias[key[r]];
             m = fmaxf(m, s[r]);
         }
     }
@@ -585,8 +591,24 @@ extern "C" int cocos_box3_sparse_softmax_warp_fwd(const float* th_t, const float
     if (const int rc = box3_pair_check(name, TopkSet{idx, k}, B, K, fh, fw, gh, gw, Cv, inv_temperature)) return rc;
     for (const void* p : {th_t, ph_t}) COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: the theta / phi rows must be 16-byte aligned", name);
     const long long rows = (long long)B * fh * fw;
-    hipLaunchKernelGGL(box3_sparse_fwd_kernel, dim3(box3_pair_blocks(rows)), dim3(BOX3_THREADS), 0, as_stream(stream), th_t, ph_t, mu, a, nu,
-                       b, v_t, idx, out_t, w, c, rows, fh, fw, gh, gw, Cv, k, inv_temperature, (float)(9 * BOX3_ROW_C));
+    hipLaunchKernelGGL(box3_sparse_fwd_kernel<false>, dim3(box3_pair_blocks(rows)), dim3(BOX3_THREADS), 0, as_stream(stream), th_t, ph_t, mu, a,
+                       nu, b, v_t, idx, out_t, w, c, rows, fh, fw, gh, gw, Cv, k, inv_temperature, (float)(9 * BOX3_ROW_C), nullptr);
+    COCOS_HIP_CHECK(hipGetLastError());
+    return COCOS_OK;
+}
+
+extern "C" int cocos_box3_sparse_softmax_warp_bias_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu,
+                                                       const float* b, const float* v_t, const int* idx, const float* k_bias, float* out_t,
+                                                       float* w, float* c, int B, int K, int fh, int fw, int gh, int gw, int Cv, int k,
+                                                       float inv_temperature, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "box3_sparse_softmax_warp_bias_fwd";
+    COCOS_REQUIRE(th_t && ph_t && mu && a && nu && b && v_t && idx && k_bias && out_t && w && c, COCOS_ERR_INVALID, "%s: null pointer", name);
+    if (const int rc = box3_pair_check(name, TopkSet{idx, k}, B, K, fh, fw, gh, gw, Cv, inv_temperature)) return rc;
+    for (const void* p : {th_t, ph_t}) COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: the theta / phi rows must be 16-byte aligned", name);
+    const long long rows = (long long)B * fh * fw;
+    hipLaunchKernelGGL(box3_sparse_fwd_kernel<true>, dim3(box3_pair_blocks(rows)), dim3(BOX3_THREADS), 0, as_stream(stream), th_t, ph_t, mu, a,
+                       nu, b, v_t, idx, out_t, w, c, rows, fh, fw, gh, gw, Cv, k, inv_temperature, (float)(9 * BOX3_ROW_C), k_bias);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }

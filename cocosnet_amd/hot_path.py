@@ -266,6 +266,24 @@ class _BoxedCorr:
             return ops.box3_match(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows)
         return ops.box3_topk(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
 
+    def match_biased(self, rows: bool, bias, k: int = 1):
+        """match(rows, k) over z + bias[key] (K54, ops.box3_topk_biased) -> (idx [B,N,k], val, lse), on the same T and the same cached
+        statistics; `bias` [B,N] fp32 belongs to the keys of the direction read (phi's positions for rows, theta's otherwise)"""
+        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
+        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
+        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        return ops.box3_topk_biased(t, *q, *kk, bias, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
+
+    def sinkhorn(self, iters: int, tau: float = 1.0, readout: bool = False):
+        """(f, g, row_lse) [B,N] of ops.box3_sinkhorn on the row pass's T and the cached statistics (K54): 2 iters + 1 launches, no
+        second correlation GEMM.  `readout`: (f, g, idx [B,N,1], val [B,N,1], row_lse) — the last launch is the k = 1 readout of z + g"""
+        iters, tau = ops._sinkhorn_args("box3_sinkhorn", iters, tau)
+        (mu, a), (nu, b) = self.stats()
+        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+        out = ops._box3_sinkhorn_readout(t, mu, a, nu, b, self.fh, self.fw, self.kc, self.inv_t, iters, tau)
+        return out if readout else (out[0], out[1], out[4])
+
     def stats(self):
         """((mu, a), (nu, b)) of theta and phi, with autograd where the operands carry it"""
         return self._get("q", lambda: _unfold3_stats(self.th, self.kc)), self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
@@ -644,7 +662,8 @@ _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused ma
           "transport": " (transport runs on the fused match_kernel 1 route)",
           "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)",
           "flow_box3": " (the box sub-cell flow runs on the match_kernel 3 route)",
-          "nll_box3": " (the box match loss runs on the match_kernel 3 route)"}
+          "nll_box3": " (the box match loss runs on the match_kernel 3 route)",
+          "transport_box3": " (box transport runs on the match_kernel 3 route)"}
 
 
 def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool, kernel: int = 1):
@@ -1232,7 +1251,7 @@ def _box3_select_and_stats(theta_raw, phi_raw, cfg: HotPathConfig, temperature, 
 
 
 def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                               exemplar=None):
+                               exemplar=None, transport=None):
     """correspondence_sparse on the reference's default route, match_kernel 3 (K51): per content position the `topk` best exemplar
     positions are SELECTED without gradient exactly as correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk) selects
     them (that function is called: K41 on the one x-box tensor T where ops.box3_fused_ok and ops.box3_topk_ok(topk) hold, the
@@ -1246,9 +1265,17 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
 
     Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, plain flag set (no warp_patch / warp_bilinear / cycle terms),
     no prepared exemplar: everything else raises ValueError — there is no fall-back route.  CPU tensors raise CocosHipError.  Not built
-    on this route: restrict, transport, search="patchmatch", refine."""
+    on this route: restrict, search="patchmatch", refine.
+
+    `transport` (K54; None is the route as it was, launch for launch): dict(iters=, tau=) — the candidates are
+    correspondence_transport_box3's top-k of z + g and the blend is the softmax over the k pair logits plus g (ops.box3_sparse_softmax_warp
+    with k_bias = g).  The potentials are detached: gradients reach theta_raw, phi_raw and the values through the k pair logits and the
+    K12 statistics only.  It needs the grids the fused box route takes and a topk that ops.box3_topk_ok serves (ValueError); the result
+    gains potential_k [B,h,w] and match_mass [B,h,w]."""
     name = "correspondence_sparse_box3"
     k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)
+    if transport is not None:
+        iters, tau = _transport_dict(name, transport)
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     down = cfg.down
@@ -1260,12 +1287,23 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
-    *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature, k)
+    extra, g = {}, None
+    if transport is None:
+        *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature, k)
+        with torch.no_grad():
+            idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
+            del m
+    else:
+        _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+        th, ph = _raw(theta_raw), _raw(phi_raw)      # projected with autograd first, as _box3_select_and_stats does
+        f, g, idx, _, row_lse, _ = _transport_box3_select(theta_raw, phi_raw, 1.0 / temperature, iters, tau, k, key_mass=False)
+        extra = {"potential_k": g.reshape(B, gh, gw), "match_mass": torch.exp(f + row_lse + math.log(N)).reshape(B, fh, fw)}
+        idx = idx.to(torch.int64).contiguous()
+        kc = float(C * 9)
+        operands = [th, ph, *_unfold3_stats(th, kc), *_unfold3_stats(ph, kc)]
     with torch.no_grad():
-        idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
-        del m
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
-    o, w = ops.box3_sparse_softmax_warp(*operands, v, idx, 1.0 / temperature, return_weights=True)
+    o, w = ops.box3_sparse_softmax_warp(*operands, v, idx, 1.0 / temperature, return_weights=True, k_bias=g)
     n_ref = ref_img.shape[1]
     y, o_mask = _split_channels(o, n_ref) if direct_mask else (o, None)
     out = {"warp_out": ops.upsample_nearest(y.reshape(B, n_ref, fh, fw), down)}
@@ -1273,20 +1311,103 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
         out["warp_mask"] = o_mask.reshape(B, -1, fh, fw)
     out["match_index"] = _rank_first(idx, (B, fh, fw), k)
     out["match_weight"] = _rank_first(w, (B, fh, fw), k)
+    out.update(extra)
     return out
 
 
+# ---- K54: transport on the match_kernel-3 route — Sinkhorn from one T -------------------------------------------------------------
+def _transport_box3_scope(name: str, cfg: HotPathConfig, iters, tau, topk, has_exemplar: bool = False, channels=None):
+    """ValueError for everything outside box transport's scope, before any tensor is looked at, in §3.33's order: the arguments (topk,
+    iters, tau), then the flag set (match_kernel 3, PONO_C, the plain flags, COCOS_PRECISION=f16x3, ops.MATCH_FUSED), a prepared
+    exemplar, the channels; every route message ends in _ROUTE["transport_box3"] -> (k, iters, tau)"""
+    k = _topk_arg(name, topk)
+    iters, tau = ops._sinkhorn_args(f"{name}: transport", iters, tau)
+    _route_scope(f"{name}: transport", cfg, "transport_box3", plain_flags=True, match_fused=True, kernel=3)
+    if has_exemplar:
+        raise ValueError(f"{name}: transport with a prepared exemplar is out of scope (not built){_ROUTE['transport_box3']}")
+    _route_channels(f"{name}: transport", "transport_box3", channels)
+    return k, iters, tau
+
+
+def _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k):
+    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw) or not ops.box3_topk_ok(k):
+        raise ValueError(f"{name}: transport: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid at "
+                         f"topk={k} (equal 64- or 128-wide grids, positions a multiple of 256), and there is no materialised fall-back"
+                         f"{_ROUTE['transport_box3']}")
+
+
+def _transport_box3_select(theta_raw, phi_raw, inv_t, iters, tau, k, key_mass: bool):
+    """One _BoxedCorr as correspondence_match's fused match_kernel-3 branch makes it (lazy projections through K25 where allowed), one
+    x-box GEMM, 2 iters + 1 biased launches, one top-k launch when k > 1, one column launch when `key_mass` -> (f, g, idx [B,N,k],
+    z [B,N,k], lse [B,N] of z + g, col_lse or None), all without gradient; T is dropped on return"""
+    with torch.no_grad():
+        if isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:
+            boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
+        else:
+            boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
+        f, g, idx, z, lse = boxed.sinkhorn(iters, tau, readout=True)
+        if k > 1:
+            idx, z, lse = boxed.match_biased(True, g, k)      # (lse is the last launch's bit for bit)
+        col_lse = boxed.match_biased(False, f, 1)[2] if key_mass else None
+        del boxed
+        return f, g, idx, z, lse, col_lse
+
+
+def correspondence_transport_box3(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, iters=5, tau=1.0, topk=1):
+    """correspondence_transport on the reference's default route, match_kernel 3 (K54): the match readout of the entropic transport
+    plan over the box logits z — the rows of softmax_q(z[p,q] + g_q) with g the exemplar-side potential of `iters` log-domain Sinkhorn
+    iterations under uniform marginals (ops.box3_sinkhorn; tau = 1 balanced, tau < 1 KL-relaxed).  Forward only.  One x-box GEMM, then
+    2 iters + 1 biased launches over the one T (the last is the topk = 1 readout), one top-k launch when topk > 1, one column launch
+    for key_mass; only one HWxHW tensor is ever alive and it is dropped on return.
+
+    theta_raw, phi_raw: [B,256,h,w] CUDA fp32 or ops.LazyProj1x1.  Returns correspondence_transport's dictionary: `readout` (a
+    MatchReadout, or a TopkMatchReadout for topk > 1, over z + g), potential_q (f) and potential_k (g) [B,h,w], match_mass [B,h,w] =
+    exp(f + lse) N, key_mass [B,h,w] = exp(g + log sum_p exp(z + f)) N (1 under tau = 1).
+
+    Scope: match_kernel 3, PONO_C, the plain flag set, COCOS_PRECISION=f16x3, ops.MATCH_FUSED, 256 channels, no prepared exemplar —
+    anything else raises a ValueError naming box transport before any tensor is looked at; then equal grids that ops.box3_fused_ok
+    takes and a topk that ops.box3_topk_ok serves (ValueError: there is no materialised fall-back).  CPU tensors raise CocosHipError."""
+    name = "correspondence_transport_box3"
+    k, iters, tau = _transport_box3_scope(name, cfg, iters, tau, topk, False, theta_raw.shape[1])
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    _fused_width(name, theta_raw, phi_raw)
+    if k > Nk:
+        raise ValueError(f"{name}: topk={k} exceeds the {Nk} exemplar positions")
+    if not _hip_fp32(theta_raw):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+    f, g, idx, z, lse, col_lse = _transport_box3_select(theta_raw, phi_raw, 1.0 / temperature, iters, tau, k, key_mass=True)
+    with torch.no_grad():
+        shape = (B, fh, fw)
+        if k == 1:
+            m = _readout(idx[..., 0], z[..., 0], lse, shape, (gh, gw))
+        else:
+            val = _rank_first(z, shape, k)
+            m = TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.reshape(shape).unsqueeze(1)),
+                                 logit=val, lse=lse.reshape(shape), grid=(gh, gw))
+        return {"readout": m, "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
+                "match_mass": torch.exp(f + lse + math.log(N)).reshape(shape),
+                "key_mass": torch.exp(g + col_lse + math.log(Nk)).reshape(B, gh, gw)}
+
+
 # ---- K50: transport match — entropic optimal transport over the correlation instead of the row softmax ---------------------------
+def _transport_dict(name: str, transport):
+    """ValueError unless `transport` is a dict with exactly the keys iters (integer in 1..ops.SINKHORN_MAX_ITERS) and tau (0 < tau <= 1)
+    -> (iters, tau); the check both transport routes make of the argument"""
+    if not isinstance(transport, dict) or set(transport) != {"iters", "tau"}:
+        what = sorted(transport) if isinstance(transport, dict) else type(transport).__name__
+        raise ValueError(f"{name}: transport={what}: expected None or dict(iters=, tau=)")
+    return ops._sinkhorn_args(f"{name}: transport", transport["iters"], transport["tau"])
+
+
 def _transport_scope(name: str, cfg: HotPathConfig, transport, has_exemplar: bool, search="dense", restrict=None, channels=None):
     """ValueError for a `transport` that is neither None nor a dict with exactly the keys iters (integer in 1..ops.SINKHORN_MAX_ITERS)
     and tau (0 < tau <= 1), and — with one — for everything outside its scope (K50: sparse_warp's route, no prepared exemplar, the
     dense selector, no restriction); checked before any tensor is looked at.  Every message names `transport`."""
     if transport is None:
         return
-    if not isinstance(transport, dict) or set(transport) != {"iters", "tau"}:
-        what = sorted(transport) if isinstance(transport, dict) else type(transport).__name__
-        raise ValueError(f"{name}: transport={what}: expected None or dict(iters=, tau=)")
-    ops._sinkhorn_args(f"{name}: transport", transport["iters"], transport["tau"])
+    _transport_dict(name, transport)
     _route_scope(f"{name}: transport", cfg, "transport", plain_flags=True, match_fused=False)
     if has_exemplar:
         raise ValueError(f"{name}: transport with a prepared exemplar is out of scope (not built)")

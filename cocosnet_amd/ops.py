@@ -3535,6 +3535,96 @@ def box3_topk(t, mu, a, nu, b, h, w, k_unfolded, scale, k: int, transposed: bool
     return idx, val, lse
 
 
+# K54  transport on the match_kernel-3 route: the biased readout of T and the Sinkhorn iteration on top of it
+def _box3_topk_bias_launch(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k: int, transposed: bool, name: str = "box3_topk_biased"):
+    """One launch of cocos_box3_topk_bias_f16x3 on contiguous fp32 device tensors (already checked) -> (idx [B,N,k], val, lse)"""
+    B, N = mu.shape
+    idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
+    val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
+    lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
+    _call(name, "cocos_box3_topk_bias_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(), k_bias.data_ptr(),
+          idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale), k,
+          _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+    return idx, val, lse
+
+
+def _box3_readout_tensors(name, t, mu, a, nu, b):
+    """TypeError unless the five operands are tensors, ValueError unless mu is [B,N]: the first refusal of both K54 ops"""
+    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
+        if not torch.is_tensor(x):
+            raise TypeError(f"{name}: {what}: expected a tensor, got {type(x).__name__}")
+    if mu.dim() != 2:
+        raise ValueError(f"{name}: mu is [B,N]")
+
+
+def _box3_readout_args(name, t, mu, a, nu, b, h, w):
+    """The refusals box3_topk_biased and box3_sinkhorn share, after their own argument errors: device, then shapes -> the five tensors
+    detached, contiguous fp32"""
+    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
+        if not x.is_cuda:
+            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    t, mu, a, nu, b = (_chk(x.detach(), f"{name}: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
+    B, N = mu.shape
+    if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
+        raise ValueError(f"{name}: shape mismatch")
+    return t, mu, a, nu, b
+
+
+def box3_topk_biased(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k: int, transposed: bool = False):
+    """box3_topk over z'[p,q] = z[p,q] + k_bias[b,q] (K54; forward only: the inputs are detached and no autograd node is made) ->
+    (idx int32 [B,N,k], val [B,N,k] = z', lse [B,N] = log sum_q exp z'[p,q]).  k_bias [B,N] float32: finite values of any sign, or -inf
+    to exclude a key (a row with every key excluded has lse = val = -inf and indices in range; no NaN from finite or -inf input).  The
+    bias is added inside the scan of T, before the candidate list and the sum; a bias of zeros gives box3_topk's outputs bit for bit.
+    `transposed` as for box3_match: the bias then belongs to T's queries, the keys of the transposed problem.  Refusals in this order:
+    a bias of another dtype (TypeError), of another shape or one that requires a gradient, a bad k (ValueError); tensors off the
+    device; the shapes box3_topk refuses."""
+    name = "box3_topk_biased"
+    _box3_readout_tensors(name, t, mu, a, nu, b)
+    B, N = mu.shape
+    k_bias = _bias_table(name, k_bias, (B, N))
+    k = _check_topk(name, k, N)
+    if not box3_topk_ok(k):      # (cocos_box3_topk_max_k owns the limit of both entries: every BIAS instantiation ships)
+        raise ValueError(f"{name}: k={k}: no instantiation serves it (box3_topk_ok)")
+    if not k_bias.is_cuda:
+        raise _lib.CocosHipError(f"{name}: k_bias: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+    with torch.no_grad():
+        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
+        return _box3_topk_bias_launch(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k, transposed)
+
+
+def box3_sinkhorn(t, mu, a, nu, b, h, w, k_unfolded, scale, iters: int, tau: float = 1.0):
+    """corr_sinkhorn's iteration on the match_kernel-3 logits z[p,q] of box3_match, from ONE T = box3_corr_xbox (K54; forward only,
+    under torch.no_grad()) -> (f [B,N], g [B,N], row_lse [B,N]).  Uniform marginals 1 / N; with g = 0, `iters` times
+        f_p = tau (-log N - log sum_q exp(z[p,q] + g_q)),   g_q = tau (-log N - log sum_p exp(z[p,q] + f_p))
+    and row_lse_p = log sum_q exp(z[p,q] + g_q) against the final g.  Every half-step is one K = 1 launch of the biased readout over the
+    same T: the row half-step reads it as stored with g as the key bias, the column half-step reads it transposed with (mu, a) and
+    (nu, b) exchanged and f as the key bias; the affine update runs in torch on [B,N] vectors.  2 iters + 1 launches, no second
+    correlation GEMM and nothing N x N besides T.  iters an integer in 1..SINKHORN_MAX_ITERS, 0 < tau <= 1 (ValueError); then the
+    refusals of box3_match."""
+    name = "box3_sinkhorn"
+    f, g, _, _, row_lse = _box3_sinkhorn_readout(t, mu, a, nu, b, h, w, k_unfolded, scale, iters, tau)
+    return f, g, row_lse
+
+
+def _box3_sinkhorn_readout(t, mu, a, nu, b, h, w, k_unfolded, scale, iters, tau):
+    """box3_sinkhorn with all three outputs of its last launch -> (f, g, idx [B,N,1], val [B,N,1], row_lse): the k = 1 readout of
+    z + g is that launch, so a caller that wants the best match per row pays nothing for it"""
+    name = "box3_sinkhorn"
+    iters, tau = _sinkhorn_args(name, iters, tau)
+    _box3_readout_tensors(name, t, mu, a, nu, b)
+    with torch.no_grad():
+        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
+        B, N = mu.shape
+        log_m = -math.log(N)
+        rows = lambda g: _box3_topk_bias_launch(t, mu, a, nu, b, g, h, w, k_unfolded, scale, 1, False, name)
+        cols = lambda f: _box3_topk_bias_launch(t, nu, b, mu, a, f, h, w, k_unfolded, scale, 1, True, name)[2]
+        g = torch.zeros((B, N), device=t.device, dtype=torch.float32)
+        for _ in range(iters):
+            f = tau * (log_m - rows(g)[2])
+            g = tau * (log_m - cols(f))
+        return (f, g, *rows(g))
+
+
 class _Box3Lse(torch.autograd.Function):
     """K53.  Forward: box3_match's launch, its lse.  Backward: cocos_box3_lse_bwd_f16x3 writes G = g_lse softmax(z) scale a_p b_q
     in _Box3SoftmaxWarp's convention and under its Box3GradSink protocol, so T's node runs one K20 and one pair of GEMMs for every
@@ -3723,16 +3813,21 @@ class _Box3SparseSoftmaxWarp(torch.autograd.Function):
     nothing with an Nq x Nk extent."""
 
     @staticmethod
-    def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_t: float):
+    def forward(ctx, theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_t: float, k_bias=None):
         B, K, fh, fw = theta_raw.shape
         gh, gw = phi_raw.shape[2:]
         Nq, Nk, Cv, k = fh * fw, gh * gw, v.shape[1], idx.shape[2]
         th_t, ph_t, vt = _transpose(theta_raw.reshape(B, K, Nq)), _transpose(phi_raw.reshape(B, K, Nk)), _transpose(v)
         out_t = torch.empty((B, Nq, Cv), device=v.device, dtype=torch.float32)
         w, c = (torch.empty((B, Nq, k), device=v.device, dtype=torch.float32) for _ in range(2))
-        _call("box3_sparse_softmax_warp_fwd", "cocos_box3_sparse_softmax_warp_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(),
-              a.data_ptr(), nu.data_ptr(), b.data_ptr(), vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), c.data_ptr(), B, K,
-              fh, fw, gh, gw, Cv, k, float(inv_t), _stream())
+        if k_bias is None:
+            _call("box3_sparse_softmax_warp_fwd", "cocos_box3_sparse_softmax_warp_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(),
+                  a.data_ptr(), nu.data_ptr(), b.data_ptr(), vt.data_ptr(), idx.data_ptr(), out_t.data_ptr(), w.data_ptr(), c.data_ptr(), B, K,
+                  fh, fw, gh, gw, Cv, k, float(inv_t), _stream())
+        else:       # K54: w = softmax(pair logit + k_bias[key]); the bias is a constant — the backward below consumes the saved w
+            _call("box3_sparse_softmax_warp_fwd", "cocos_box3_sparse_softmax_warp_bias_fwd", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(),
+                  a.data_ptr(), nu.data_ptr(), b.data_ptr(), vt.data_ptr(), idx.data_ptr(), k_bias.data_ptr(), out_t.data_ptr(), w.data_ptr(),
+                  c.data_ptr(), B, K, fh, fw, gh, gw, Cv, k, float(inv_t), _stream())
         ctx.save_for_backward(th_t, ph_t, vt, idx, w, c, mu, a, nu, b)
         ctx.cfg = (fh, fw, gh, gw, float(inv_t))
         ctx.mark_non_differentiable(w)
@@ -3752,10 +3847,10 @@ class _Box3SparseSoftmaxWarp(torch.autograd.Function):
         key = lambda g, hb, entries, offsets, *out: _call(name + "key", f"cocos_{name}key", th_t.data_ptr(), dout_t.data_ptr(), g, hb,
                                                           w.data_ptr(), mu.data_ptr(), entries, offsets, *out, *dims, Cv, k, _stream())
         dth, dph, *rest = _box3_pair_backward(ctx.needs_input_grad[:7], th_t, ph_t, idx, k, pair, theta, key, Cv)
-        return (None if dth is None else dth.reshape(B, K, fh, fw), None if dph is None else dph.reshape(B, K, gh, gw), *rest, None, None)
+        return (None if dth is None else dth.reshape(B, K, fh, fw), None if dph is None else dph.reshape(B, K, gh, gw), *rest, None, None, None)
 
 
-def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_temperature: float, return_weights: bool = False):
+def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_temperature: float, return_weights: bool = False, k_bias=None):
     """out [B,Cv,fh*fw] = sum_r w[b,p,r] * v[b,:,idx[b,p,r]] with w = softmax over r of the match_kernel-3 logit of the pair
     (p, idx[b,p,r]): z[p,q] = inv_temperature * a_p * b_q * (R[p,q] - 9*256 * mu_p * nu_q), R the sum over the nine taps d of
     <theta_raw[:,p+d], phi_raw[:,q+d]> where both p+d and q+d lie inside their grids (box3_logits' value — F.unfold(3, padding=1),
@@ -3765,7 +3860,10 @@ def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_tempe
     and phi_raw (made by it from tensors that require a gradient, they carry the statistics' share of the gradient back); v
     [B,Cv,gh*gw] fp32; idx [B,fh*fw,k] int32 / int64 with 1 <= k <= MATCH_TOPK_MAX, k <= gh*gw — any values: repeats inside a row are
     legal, values outside [0, gh*gw) are clamped into it.  Nothing Nq x Nk is allocated, forward or backward; the gradients are
-    gathered in a fixed order (no atomics: bitwise reproducible).  `return_weights`: also return w [B,fh*fw,k] (no gradient)."""
+    gathered in a fixed order (no atomics: bitwise reproducible).  `return_weights`: also return w [B,fh*fw,k] (no gradient).
+    `k_bias` (K54; None is the call as it was, launch for launch): float32 [B,gh*gw] added to each of the k pair logits before their
+    softmax — a constant (a Sinkhorn potential): one that requires a gradient raises ValueError, another dtype TypeError; the
+    gradients are those of the biased softmax through the k pair logits, the statistics and v."""
     name = "box3_sparse_softmax_warp"
     if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"{name}: idx must be an int32 or int64 tensor, got {idx.dtype if torch.is_tensor(idx) else type(idx).__name__}")
@@ -3783,9 +3881,16 @@ def box3_sparse_softmax_warp(theta_raw, phi_raw, mu, a, nu, b, v, idx, inv_tempe
         raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
     _check_topk(name, int(idx.shape[2]), Nk)
     stats = _box3_stats(name, B, Nq, Nk, mu, a, nu, b)
+    if k_bias is not None:
+        k_bias = _bias_table(name, k_bias, (B, Nk))
+        if k_bias.device != v.device:
+            raise _lib.CocosHipError(f"{name}: k_bias: expected a tensor on v's device; the correspondence hot path has no CPU fallback")
     theta_raw, phi_raw, v, mu, a, nu, b, idx = _box3_pair_gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw"), (v, "v")), stats, idx,
                                                                idx.shape, Nk)
-    out, w = _Box3SparseSoftmaxWarp.apply(theta_raw, phi_raw, mu, a, nu, b, v, idx, float(inv_temperature))
+    if k_bias is None:
+        out, w = _Box3SparseSoftmaxWarp.apply(theta_raw, phi_raw, mu, a, nu, b, v, idx, float(inv_temperature))
+    else:
+        out, w = _Box3SparseSoftmaxWarp.apply(theta_raw, phi_raw, mu, a, nu, b, v, idx, float(inv_temperature), k_bias)
     return (out, w) if return_weights else out
 
 

@@ -1074,6 +1074,21 @@ int cocos_box3_topk_max_k(void);
 int cocos_box3_topk_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
                           int* idx, float* val, float* lse, int B, int Nq, int Nk, int grid_h, int grid_w, float k_unfolded,
                           float scale, int k, int flags, cocos_stream_t stream);
+/* K54 — the biased readout of these logits (the BIAS instantiations of the same kernel template): cocos_box3_topk_f16x3 over
+ *         z'[p,q] = z[p,q] + k_bias[b,q]
+ *     k_bias fp32 [B,Nk], 16-byte aligned (it is staged into LDS beside the key statistics).  val holds z' (natural units), lse = log
+ *     sum_q exp z'[p,q], idx / val the k best z' in K41's order.  The kernel's state lives in the tt domain (z = tt * a_n with a_n =
+ *     scale * a_p the query's factor): the bias enters as tt += k_bias / a_n, one fma per element before the tile maximum, the list and
+ *     the sum, so a bias of zeros gives cocos_box3_topk_f16x3's three outputs bit for bit.  A finite bias of any sign is legal; -inf
+ *     excludes the key; a row with every key excluded has lse = -inf, val = -inf and indices in [0, Nk); finite or -inf input never
+ *     produces a NaN.  +inf and NaN are not sanitised; idx stays in [0, Nk).  One launch at k = 1 is one half-step of a log-domain
+ *     Sinkhorn iteration over ONE T: f_p = tau (log mu_p - lse_p) with the other side's potential g as the bias; the column half-step is
+ *     the same entry with COCOS_BOX3_T_TRANSPOSED, (mu, a) and (nu, b) exchanged and f as the bias.
+ *     Arguments, supported shapes, flags, k and error codes of cocos_box3_topk_f16x3; a null k_bias or one that is not 16-byte aligned
+ *     is COCOS_ERR_INVALID; all checked before any HIP call. */
+int cocos_box3_topk_bias_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                               const float* k_bias, int* idx, float* val, float* lse, int B, int Nq, int Nk, int grid_h, int grid_w,
+                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream);
 size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk);
 int cocos_box3_softmax_warp_bwd_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
                                       const float* b_k, const void* vph, const void* vpl, const void* gph, const void* gpl,
@@ -1436,6 +1451,13 @@ int cocos_transpose_f32(const float* in, float* out, int B, int R, int C, cocos_
 int cocos_box3_sparse_softmax_warp_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu,
                                        const float* b, const float* v_t, const int* idx, float* out_t, float* w, float* c, int B, int K,
                                        int fh, int fw, int gh, int gw, int Cv, int k, float inv_temperature, cocos_stream_t stream);
+/* K54: cocos_box3_sparse_softmax_warp_fwd with w = softmax over r of z[p, j_r] + k_bias[b, j_r]; k_bias fp32 [B,Nk] (finite, or -inf on
+ *     keys no row names alone), a constant of the softmax: c, w and the three backward entries are the unbiased ones.  A bias of zeros
+ *     gives the unbiased forward's out_t, w and c bit for bit.  A null k_bias is COCOS_ERR_INVALID; otherwise its refusals. */
+int cocos_box3_sparse_softmax_warp_bias_fwd(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu,
+                                            const float* b, const float* v_t, const int* idx, const float* k_bias, float* out_t, float* w,
+                                            float* c, int B, int K, int fh, int fw, int gh, int gw, int Cv, int k, float inv_temperature,
+                                            cocos_stream_t stream);
 int cocos_box3_sparse_softmax_warp_bwd_pair(const float* v_t, const float* dout_t, const int* idx, const float* w, const float* c,
                                             const float* a, const float* nu, const float* b, float* g, float* hb /* nullable */,
                                             float* dmu /* nullable */, float* da /* nullable */, int B, int K, int fh, int fw, int gh,

@@ -39,7 +39,9 @@ def register_rows():
         return None
     rows = []
     for u in usage:
-        k, chunked = re.search(r"kernelILi(\d+)ELb([01])E", u.name).groups()
+        k, chunked, bias = re.search(r"kernelILi(\d+)ELb([01])ELb([01])E", u.name).groups()
+        if bias == "1":       # K54's instantiations: tools/match_box3_transport_bench.py
+            continue
         rows.append((int(k), int(chunked), u.vgprs, u.agprs, u.sgprs, u.scratch, u.occupancy))
     return sorted(rows)
 
