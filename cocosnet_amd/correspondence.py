@@ -25,8 +25,8 @@ from torch.nn import init
 
 from . import inference, ops
 from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_box3_scope, _nll_scope, _refine_scope, _restrict_scope,
-                       _sparse_scope, _sparse_search, _topk_arg, _transport_box3_scope, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
-                       correspondence_hot_path, correspondence_match, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
+                       _restrict_box3_scope, _sparse_scope, _sparse_search, _topk_arg, _transport_box3_scope, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
+                       correspondence_hot_path, correspondence_match, correspondence_match_box3, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
                        correspondence_sparse, correspondence_sparse_box3,
                        correspondence_transport, correspondence_transport_box3)
 from .producers import AdaptiveFeatureGenerator, ResidualBlock
@@ -489,7 +489,48 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, torch.softmax(m.logit, dim=1), fh, fw, self.opt.down)
         return out
 
-    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, transport=None):
+    def match_box3(self, ref_img, seg_map, ref_seg_map, temperature=0.01, *, direction="rows", hard_warp=False, topk=1, blend="topk",
+                   restrict="label"):
+        """match(restrict=) on the reference's default route, match_kernel 3 (K55, hot_path.correspondence_match_box3): every
+        position's candidates are picked only among the positions of the other side that carry its class — `restrict` = "label": the
+        majority class of each feature cell of seg_map / ref_seg_map; a pair (q_labels [B,h,w], k_labels [B,h,w]) of int32 / int64
+        tensors, content side first: any labels (a negative content label: unrestricted) — with the mask inside the scan of the one
+        x-box tensor T: one correlation GEMM, one launch, nothing HWxHW after return.  One projection of the network, under
+        torch.no_grad().  Returns match()'s keys plus match_restricted [B,h,w] bool (a position whose label has fewer than topk
+        positions on the other side falls back to the unrestricted scan): match_index [B,h,w] int64 ([B,k,h,w] with topk = k > 1),
+        match_xy, match_prob and match_lse over the ALLOWED positions, and with `hard_warp` warp_hard (topk > 1: also warp_topk,
+        weighted by `blend`) from the restricted indices.  `restrict` = None is match() on the same arguments.  Scope: match_kernel 3
+        with PONO_C, COCOS_PRECISION=f16x3, ops.MATCH_FUSED, no prepared exemplar; everything else raises a ValueError naming restrict
+        before the network runs.  match() is unaffected."""
+        if restrict is None:
+            return self.match(ref_img, seg_map, ref_seg_map, temperature, direction=direction, hard_warp=hard_warp, topk=topk, blend=blend)
+        if direction not in ("rows", "cols"):
+            raise ValueError(f"match_box3: direction {direction!r}: expected 'rows' or 'cols'")
+        k = _topk_arg("match_box3", topk)
+        if blend not in ("topk", "full"):
+            raise ValueError(f"match_box3: blend {blend!r}: expected 'topk' or 'full'")
+        if hard_warp and direction == "cols":
+            raise ValueError("match_box3: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
+        cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _restrict_box3_scope("match_box3", cfg, restrict, None, self.inter_channels, plain_flags=False)
+        if ref_img is None or ref_seg_map is None:
+            raise ValueError("match_box3: restrict: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
+        with torch.no_grad():
+            theta_raw, phi_raw = self.project(ref_img, None, seg_map, ref_seg_map, None, lazy=True)
+            m = correspondence_match_box3(theta_raw, phi_raw, cfg, temperature, direction=direction, topk=k, restrict=restrict,
+                                          seg_map=seg_map, ref_seg_map=ref_seg_map)
+            out = {"match_index": m.index, "match_xy": m.xy(), "match_prob": m.prob, "match_lse": m.lse, "match_restricted": m.restricted}
+            if hard_warp and k == 1:
+                fh, fw = m.index.shape[1:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index, fh, fw, self.opt.down)
+            elif hard_warp:
+                fh, fw = m.index.shape[2:]
+                out["warp_hard"] = ops.gather_patches(ref_img, m.index[:, 0], fh, fw, self.opt.down)
+                weights = torch.softmax(m.logit, dim=1) if blend == "topk" else m.prob
+                out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
+        return out
+
+    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, transport=None, restrict=None):
         """sparse_warp on the reference's default route, match_kernel 3 (K51, hot_path.correspondence_sparse_box3): per content position
         the `topk` best exemplar positions are selected without gradient, as match(topk=topk) selects them, and a softmax over those k
         box logits alone blends the pooled exemplar (and, under --warp_mask_losstype direct, the exemplar's labels), with gradients to
@@ -498,8 +539,13 @@ class NoVGGCorrespondence(NetworkBase):
         project() makes it).  Scope: match_kernel 3 with PONO_C on the plain flag set; everything else raises ValueError before the
         network runs (no fall-back).  forward(), match() and sparse_warp() are unaffected.  `transport` (K54; None changes nothing):
         dict(iters=, tau=) — the candidates are the top-k of the box transport plan's rows and the blend is the biased softmax over
-        them, with the Sinkhorn potentials detached; the result gains potential_k and match_mass."""
+        them, with the Sinkhorn potentials detached; the result gains potential_k and match_mass.  `restrict` (K55; None changes nothing):
+        "label" or a pair of integer label tensors as for match_box3 — the candidates are the restricted top-k; the result gains
+        match_restricted; restrict together with transport raises ValueError."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        if restrict is not None:      # (first: every scope message of a restricted call names restrict)
+            _topk_arg("sparse_warp_box3", topk)
+            _restrict_box3_scope("sparse_warp_box3", cfg, restrict, transport, self.inter_channels)
         _box3_scope("sparse_warp_box3", "sparse_box3", cfg, False, self.inter_channels, topk=topk)      # refused before the network runs
         if transport is not None:
             _transport_dict("sparse_warp_box3", transport)
@@ -508,6 +554,8 @@ class NoVGGCorrespondence(NetworkBase):
         coor_out = {}
         theta_raw, phi_raw = self.project(ref_img, real_img, seg_map, ref_seg_map, coor_out, lazy=True)
         kw = {} if transport is None else {"transport": transport}
+        if restrict is not None:
+            kw["restrict"] = restrict
         coor_out.update(correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, **kw))
         return coor_out
 

@@ -176,6 +176,24 @@ __device__ __forceinline__ void bx_add_bias(const BxGeom& gm, int t, int h, floa
     }
 }
 
+// K55: tt[r] = -inf where the key of register r carries another label than the lane's query — the third plane of the staged statistics
+// holds the key labels' INTEGER bits (the staging copies 32-bit words; no float instruction ever sees them), read in bx_add_bias'
+// pattern and compared as integers.  q_lab < 0 allows every key (K47's rule: allowed = q_label < 0 || q_label == k_label).  As in
+// bx_add_bias, register r is the PROBLEM's key 32t + 8g + 4h + e also when T is read transposed.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <bool CHUNKED>
+__device__ __forceinline__ void bx_mask_labels(const BxGeom& gm, int t, int h, int q_lab, float (&tt)[16]) {
+    constexpr int NPL = 3;      // the LABELS layout: [b | kn | label bits], the labels in plane NPL - 1
+    const float* ks = gm.kstat + (NPL - 1) * gm.nk + (CHUNKED ? ((t / BX_TCH) & 1) * NPL * BX_KCH + (t & (BX_TCH - 1)) * 32 : t * 32);
+    const bool any = q_lab < 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const i32x4 l4 = *reinterpret_cast<const i32x4*>(ks + 8 * g + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tt[4 * g + e] = (any || l4[e] == q_lab) ? tt[4 * g + e] : -INFINITY;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // K19 forward
 // ---------------------------------------------------------------------------------------------------------
@@ -438,13 +456,22 @@ __device__ __forceinline__ float bx_match_sum2(float l, float e, float ol, float
 // rescales of a side that has seen nothing away from 0 * 2^(0 - r) = 0 * inf when the first finite maximum lies below -128 in log2
 // units (a strongly negative potential; without a bias the logits are bounded by scale): they pick the same bits wherever the
 // unguarded product was finite.  The bias is the third plane of the staged statistics (NPL = 3); +inf and NaN are not sanitised.
-template <int K, bool CHUNKED, bool BIAS = false>
+// K55, LABELS: the readout over the allowed pairs only, allowed(p, q) = q_label[p] < 0 || q_label[p] == k_label[q].  The key labels
+// ride where the bias rides (NPL = 3; `k_bias` is then their bits, and LABELS with BIAS is not built), the query's label sits in one
+// register loaded before the tile loop, and a disallowed element becomes -inf right behind bx_logits (bx_mask_labels) — the same
+// value an excluded key has under BIAS, so everything below is shared.  A masked row CAN start low without any bias (a row whose
+// first tiles are all foreign sees its first allowed logit with no larger one before it: at scale = 100 a cosine near -1 is
+// r = -144 in log2 units), so LABELS takes BIAS's three guards.  With every query label negative no select fires and the three
+// outputs are the unlabelled instantiation's bit for bit.
+template <int K, bool CHUNKED, bool BIAS = false, bool LABELS = false>
 __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const float* __restrict__ T, const float* __restrict__ mu_q, const float* __restrict__ a_q,
     const float* __restrict__ nu_k, const float* __restrict__ b_k, int* __restrict__ idx_out, float* __restrict__ max_out,
     float* __restrict__ lse_out, int B, int Nq, int Nk, int himg, int wimg, float kc, float scale, int flags, int k_out,
-    const float* __restrict__ k_bias) {
-    constexpr int NPL = BIAS ? 3 : 2;
+    const float* __restrict__ k_bias, const int* __restrict__ q_label) {
+    static_assert(!(BIAS && LABELS), "restriction together with a bias is not built (no NPL = 4)");
+    constexpr int NPL = (BIAS || LABELS) ? 3 : 2;
+    constexpr bool GUARD = BIAS || LABELS;      // a side can hold m = -inf, l = 0 when its first finite maximum arrives
     extern __shared__ __attribute__((aligned(16))) unsigned char bx_smem[];
     float* const kstat = reinterpret_cast<float*>(bx_smem);      // [b | kn (| bias)][Nk] (x 2 buffers when chunked), then the XT images
 
@@ -457,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const int i_lane = q0 + wave * 32 + c;
     const float* const bk_b = b_k + (size_t)b * Nk;
     const float* const nu_b = nu_k + (size_t)b * Nk;
-    const float* const bias_b = BIAS ? k_bias + (size_t)b * Nk : nullptr;
+    const float* const bias_b = NPL == 3 ? k_bias + (size_t)b * Nk : nullptr;      // (LABELS: the key labels' bits)
     bx_stage_stats<NPL>(kstat, bk_b, nu_b, CHUNKED ? BX_KCH : Nk, CHUNKED ? BX_KCH : Nk, kc, tid, bias_b);
 
     BxGeom gm;
@@ -477,6 +504,8 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
     const float a_n = a_q[(size_t)b * Nq + i_lane] * scale;      // natural-domain factor: z = tt * a_n
     const float a2 = a_n * kLog2e;
     [[maybe_unused]] const float inv_an = BIAS ? 1.0f / a_n : 0.f;      // the bias in the tt domain: bias / a_n
+    [[maybe_unused]] int q_lab = -1;
+    if constexpr (LABELS) q_lab = q_label[(size_t)b * Nq + i_lane];
 
     float m_run = -INFINITY, r_run = 0.f, l_run = 0.f;      // r_run = m_run * a2 (0 while nothing was seen)
     int i_run = 0;                // K == 1
@@ -495,6 +524,7 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
         float tt[16], bq[16], kn[16];
         bx_logits<CHUNKED, NPL>(tl, gm, t, h, mu_p, tt, bq, kn, c);
         if constexpr (BIAS) bx_add_bias<CHUNKED>(gm, t, h, inv_an, tt);
+        if constexpr (LABELS) bx_mask_labels<CHUNKED>(gm, t, h, q_lab, tt);
         bx_fetch(tl, gm, t + 2, ntiles);
         float tmax = tt[0];
 #pragma unroll
@@ -514,7 +544,7 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
                 i_run = t * 32 + 8 * (at >> 2) + 4 * h + (at & 3);      // register r = 4g + e of lane (h, c) is key 32t + 8g + 4h + e
             }
             const float r_new = bx_match_ref(tmax, a2);
-            if constexpr (BIAS) l_run = m_run == -INFINITY ? 0.f : l_run * fast_exp2(r_run - r_new);
+            if constexpr (GUARD) l_run = m_run == -INFINITY ? 0.f : l_run * fast_exp2(r_run - r_new);
             else l_run *= fast_exp2(r_run - r_new);                 // (the first move: l_run is 0)
             m_run = tmax;
             r_run = r_new;
@@ -540,7 +570,7 @@ __global__ __launch_bounds__(256, 2) void box3_topk_kernel(
         const bool take_o = om > m_run || (om == m_run && oi < i_run);
         const float ref = om > m_run ? orr : r_run;               // (equal maxima have equal references: a2 is the query's)
         float e_own = fast_exp2(r_run - ref), e_oth = fast_exp2(orr - ref);
-        if constexpr (BIAS) {      // a side that saw nothing but excluded keys: its l = 0 must not meet 2^(0 - ref) = inf
+        if constexpr (GUARD) {      // a side that saw nothing but excluded keys: its l = 0 must not meet 2^(0 - ref) = inf
             e_own = m_run == -INFINITY ? 0.f : e_own;
             e_oth = om == -INFINITY ? 0.f : e_oth;
         }
@@ -1193,19 +1223,20 @@ static int check_box3_readout(const char* name, const float* t_blocked, const fl
 }
 
 // BIAS (K54): three staged planes instead of two — 12 Nk bytes up to 4096 keys, 48 KB for the ring — plus the 18 KB of images when
-// transposed: 66 KB at most, two workgroups per CU.
-template <int K, bool BIAS = false>
+// transposed: 66 KB at most, two workgroups per CU.  LABELS (K55): the same three planes, the third holding the key labels' bits.
+template <int K, bool BIAS = false, bool LABELS = false>
 static int launch_box3_readout(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
                                int* idx_out, float* val_out, float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w,
-                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream, const float* k_bias = nullptr) {
+                               float k_unfolded, float scale, int k, int flags, cocos_stream_t stream, const float* k_bias = nullptr,
+                               const int* q_label = nullptr) {
     const bool chunked = Nk > 2 * BX_KCH;
-    constexpr int NPL = BIAS ? 3 : 2;
+    constexpr int NPL = (BIAS || LABELS) ? 3 : 2;
     const size_t smem = (size_t)(chunked ? 2 * NPL * BX_KCH : NPL * Nk) * sizeof(float) +
                         ((flags & BX_FLAG_TRANSPOSED) ? (size_t)4 * BX_XT_FLOATS * sizeof(float) : 0);
-    auto kern = chunked ? box3_topk_kernel<K, true, BIAS> : box3_topk_kernel<K, false, BIAS>;
+    auto kern = chunked ? box3_topk_kernel<K, true, BIAS, LABELS> : box3_topk_kernel<K, false, BIAS, LABELS>;
     COCOS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(kern, dim3(B * (Nq / 128)), dim3(256), smem, as_stream(stream), t_blocked, mu_q, a_q, nu_k, b_k, idx_out,
-                       val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags, k, k_bias);
+                       val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, flags, k, k_bias, q_label);
     COCOS_HIP_CHECK(hipGetLastError());
     return COCOS_OK;
 }
@@ -1293,6 +1324,28 @@ extern "C" int cocos_box3_topk_bias_f16x3(const float* t_blocked, const float* m
     if (k == 2) return launch_box3_readout<2, true>(COCOS_ARGS);
     if (k <= 4) return launch_box3_readout<4, true>(COCOS_ARGS);
     return launch_box3_readout<8, true>(COCOS_ARGS);
+#undef COCOS_ARGS
+}
+
+extern "C" int cocos_box3_topk_labels_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
+                                            const float* b_k, const int* q_label, const int* k_label, int* idx_out, float* val_out,
+                                            float* lse_out, int B, int Nq, int Nk, int grid_h, int grid_w, float k_unfolded, float scale,
+                                            int k, int flags, cocos_stream_t stream) {
+    using namespace cocos;
+    const char* name = "box3_topk_labels_f16x3";
+    COCOS_REQUIRE(q_label && k_label, COCOS_ERR_INVALID, "%s: null pointer (q_label / k_label)", name);
+    COCOS_REQUIRE(((reinterpret_cast<uintptr_t>(q_label) | reinterpret_cast<uintptr_t>(k_label)) & 3u) == 0, COCOS_ERR_INVALID,
+                  "%s: q_label / k_label must be 4-byte aligned", name);
+    if (const int rc = check_box3_readout(name, t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h, grid_w, scale,
+                                          k, flags))
+        return rc;
+    // the key labels travel as the third staged plane: 32-bit words copied global -> LDS, compared as integers in the kernel
+    const float* k_plane = reinterpret_cast<const float*>(k_label);
+#define COCOS_ARGS t_blocked, mu_q, a_q, nu_k, b_k, idx_out, val_out, lse_out, B, Nq, Nk, grid_h, grid_w, k_unfolded, scale, k, flags, stream, k_plane, q_label
+    if (k == 1) return launch_box3_readout<1, false, true>(COCOS_ARGS);
+    if (k == 2) return launch_box3_readout<2, false, true>(COCOS_ARGS);
+    if (k <= 4) return launch_box3_readout<4, false, true>(COCOS_ARGS);
+    return launch_box3_readout<8, false, true>(COCOS_ARGS);
 #undef COCOS_ARGS
 }
 

@@ -275,6 +275,16 @@ class _BoxedCorr:
         q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
         return ops.box3_topk_biased(t, *q, *kk, bias, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
 
+    def match_labelled(self, rows: bool, q_label, k_label, k: int = 1):
+        """match(rows, k) over the keys each query's label allows (K55, ops.box3_topk_labelled) -> (idx [B,N,k], val, lse), on the same
+        T and the same cached statistics; q_label [B,N] belongs to the positions that ask in the direction read (theta's for rows,
+        phi's otherwise), k_label to the other side: the caller passes them in that order, statistics and T's orientation follow"""
+        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
+        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
+        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        return ops.box3_topk_labelled(t, *q, *kk, q_label, k_label, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
+
     def sinkhorn(self, iters: int, tau: float = 1.0, readout: bool = False):
         """(f, g, row_lse) [B,N] of ops.box3_sinkhorn on the row pass's T and the cached statistics (K54): 2 iters + 1 launches, no
         second correlation GEMM.  `readout`: (f, g, idx [B,N,1], val [B,N,1], row_lse) — the last launch is the k = 1 readout of z + g"""
@@ -663,7 +673,8 @@ _ROUTE = {"refine": ": the sub-cell refinement (refine > 0) runs on the fused ma
           "sparse_box3": " (the box sparse warp runs on the match_kernel 3 route)",
           "flow_box3": " (the box sub-cell flow runs on the match_kernel 3 route)",
           "nll_box3": " (the box match loss runs on the match_kernel 3 route)",
-          "transport_box3": " (box transport runs on the match_kernel 3 route)"}
+          "transport_box3": " (box transport runs on the match_kernel 3 route)",
+          "restrict_box3": " (the box restrict runs on the match_kernel 3 route)"}
 
 
 def _route_scope(name: str, cfg: HotPathConfig, member: str, *, plain_flags: bool, match_fused: bool, kernel: int = 1):
@@ -1251,7 +1262,7 @@ def _box3_select_and_stats(theta_raw, phi_raw, cfg: HotPathConfig, temperature, 
 
 
 def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                               exemplar=None, transport=None):
+                               exemplar=None, transport=None, restrict=None):
     """correspondence_sparse on the reference's default route, match_kernel 3 (K51): per content position the `topk` best exemplar
     positions are SELECTED without gradient exactly as correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk) selects
     them (that function is called: K41 on the one x-box tensor T where ops.box3_fused_ok and ops.box3_topk_ok(topk) hold, the
@@ -1265,7 +1276,13 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
 
     Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, plain flag set (no warp_patch / warp_bilinear / cycle terms),
     no prepared exemplar: everything else raises ValueError — there is no fall-back route.  CPU tensors raise CocosHipError.  Not built
-    on this route: restrict, search="patchmatch", refine.
+    on this route: search="patchmatch", refine.
+
+    `restrict` (K55; None is the route as it was, launch for launch): "label" or a pair (q_labels [B,h,w], k_labels [B,h,w]) as for
+    correspondence_match_box3 — the k candidates are its restricted top-k (the label mask inside the scan of T), the warp and its
+    gradients are the same K51 on those indices (idx is data).  It needs the grids the fused box route takes and a topk that
+    ops.box3_topk_ok serves (ValueError naming restrict); the result gains match_restricted [B,h,w] bool.  restrict together with
+    transport raises ValueError.
 
     `transport` (K54; None is the route as it was, launch for launch): dict(iters=, tau=) — the candidates are
     correspondence_transport_box3's top-k of z + g and the blend is the softmax over the k pair logits plus g (ops.box3_sparse_softmax_warp
@@ -1273,6 +1290,9 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     K12 statistics only.  It needs the grids the fused box route takes and a topk that ops.box3_topk_ok serves (ValueError); the result
     gains potential_k [B,h,w] and match_mass [B,h,w]."""
     name = "correspondence_sparse_box3"
+    if restrict is not None:      # (first: every scope message of a restricted call names restrict)
+        _topk_arg(name, topk)
+        _restrict_box3_scope(name, cfg, restrict, transport, theta_raw.shape[1])
     k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)
     if transport is not None:
         iters, tau = _transport_dict(name, transport)
@@ -1288,7 +1308,16 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     direct_mask = cfg.warp_mask_losstype == "direct" or cfg.show_warpmask
     extra, g = {}, None
-    if transport is None:
+    if restrict is not None:
+        labels = _restrict_labels(name, restrict, seg_map, ref_seg_map, down, B, (fh, fw), (gh, gw))
+        _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+        th, ph = _raw(theta_raw), _raw(phi_raw)      # projected with autograd first, as _box3_select_and_stats does
+        idx, _, _, restricted = _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, True, labels, k)
+        extra = {"match_restricted": restricted.reshape(B, fh, fw)}
+        idx = idx.to(torch.int64).contiguous()
+        kc = float(C * 9)
+        operands = [th, ph, *_unfold3_stats(th, kc), *_unfold3_stats(ph, kc)]
+    elif transport is None:
         *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature, k)
         with torch.no_grad():
             idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
@@ -1313,6 +1342,93 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     out["match_weight"] = _rank_first(w, (B, fh, fw), k)
     out.update(extra)
     return out
+
+
+# ---- K55: label-restricted candidates on the match_kernel-3 route — the mask inside the scan of T ---------------------------------
+def _restrict_box3_scope(name: str, cfg: HotPathConfig, restrict, transport=None, channels=None, plain_flags: bool = True):
+    """ValueError for a `restrict` that is neither "label" nor a pair of integer tensors (TypeError for another dtype) and for
+    everything outside the box restriction's scope, before any tensor is looked at: no transport, then the flag set (match_kernel 3,
+    PONO_C, with `plain_flags` the plain flags, COCOS_PRECISION=f16x3, ops.MATCH_FUSED), the channels.  Every message names restrict;
+    every route message ends in _ROUTE["restrict_box3"]."""
+    pair = isinstance(restrict, (tuple, list)) and len(restrict) == 2 and all(torch.is_tensor(t) for t in restrict)
+    if not (pair or (isinstance(restrict, str) and restrict == "label")):
+        what = repr(restrict) if isinstance(restrict, str) else type(restrict).__name__
+        raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
+    if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
+        raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
+    if transport is not None:
+        raise ValueError(f"{name}: restrict with transport is out of scope (not built){_ROUTE['restrict_box3']}")
+    _route_scope(f"{name}: restrict", cfg, "restrict_box3", plain_flags=plain_flags, match_fused=True, kernel=3)
+    _route_channels(f"{name}: restrict", "restrict_box3", channels)
+
+
+def _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k):
+    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw) or not ops.box3_topk_ok(k):
+        raise ValueError(f"{name}: restrict: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid at "
+                         f"topk={k} (equal 64- or 128-wide grids, positions a multiple of 256), and there is no materialised fall-back"
+                         f"{_ROUTE['restrict_box3']}")
+
+
+def _restrict_box3_select(theta_raw, phi_raw, inv_t, rows: bool, labels, k):
+    """One _BoxedCorr as correspondence_match's fused match_kernel-3 branch makes it (lazy projections through K25 where allowed), one
+    x-box GEMM and one labelled launch -> (idx int32 [B,N,k], val, lse, restricted bool [B,N]), all without gradient; `labels`
+    (content, exemplar) [B,N] — the side that asks brings its labels, statistics and labels swap together; T is dropped on return"""
+    with torch.no_grad():
+        q_eff, k_eff, restricted = restrict_fallback(*(labels if rows else labels[::-1]), k)
+        if isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:
+            boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
+        else:
+            boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
+        idx, val, lse = boxed.match_labelled(rows, q_eff, k_eff, k)
+        del boxed
+        return idx, val, lse, restricted
+
+
+def correspondence_match_box3(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.01, *, direction="rows", topk=1, restrict=None,
+                              seg_map=None, ref_seg_map=None):
+    """correspondence_match(restrict=) on the reference's default route, match_kernel 3 (K55): the hard readout of the box logits with
+    every position's candidates kept inside its own region.  `restrict` = None calls correspondence_match on the same arguments
+    (its result bit for bit).  "label" takes the majority class of each cell of seg_map / ref_seg_map (cell_labels with cfg.down); a
+    pair (q_labels [B,h,w], k_labels [B,h,w]) of int32 / int64 tensors — content side first, whatever the direction — is taken as
+    given (a negative content label: unrestricted).  The mask is applied inside the scan of the one x-box tensor T
+    (ops.box3_topk_labelled): one x-box GEMM, one labelled launch, T dropped on return; index, logit, prob and lse are over the
+    ALLOWED positions.  A position whose label has fewer than topk positions on the other side falls back to the unrestricted scan
+    (restrict_fallback); `restricted` [B,h,w] bool says which positions were restricted.  Forward only.  Returns a MatchReadout
+    (a TopkMatchReadout for topk > 1).
+
+    Scope: match_kernel 3, PONO_C, COCOS_PRECISION=f16x3, ops.MATCH_FUSED, 256 channels, no prepared exemplar — anything else raises
+    a ValueError naming restrict before any tensor is looked at; then equal grids that ops.box3_fused_ok takes and a topk that
+    ops.box3_topk_ok serves (ValueError: there is no materialised fall-back).  CPU tensors raise CocosHipError.  Not built:
+    restriction together with transport, the flow warp, the match loss or a prepared exemplar."""
+    name = "correspondence_match_box3"
+    if restrict is None:
+        return correspondence_match(theta_raw, phi_raw, cfg, temperature, direction=direction, topk=topk)
+    if direction not in ("rows", "cols"):
+        raise ValueError(f"{name}: direction {direction!r}: expected 'rows' or 'cols'")
+    k = _topk_arg(name, topk)
+    _restrict_box3_scope(name, cfg, restrict, None, theta_raw.shape[1], plain_flags=False)
+    _same_kind(name, theta_raw, phi_raw)
+    B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
+    _fused_width(name, theta_raw, phi_raw)
+    rows = direction == "rows"
+    if k > (Nk if rows else N):
+        raise ValueError(f"{name}: topk={k} exceeds the {Nk if rows else N} positions each row of direction={direction!r} ranges over")
+    labels = _restrict_labels(name, restrict, seg_map, ref_seg_map, cfg.down, B, (fh, fw), (gh, gw))
+    if not _hip_fp32(theta_raw):
+        raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
+    _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+    idx, val, lse, restricted = _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, rows, labels, k)
+    with torch.no_grad():
+        own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
+        shape = (B,) + own
+        if k == 1:
+            m = _readout(idx[..., 0], val[..., 0], lse, shape, other)
+            m.restricted = restricted.reshape(shape)
+            return m
+        lse = lse.reshape(shape)
+        v = _rank_first(val, shape, k)
+        return TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(v - lse.unsqueeze(1)), logit=v, lse=lse,
+                                grid=other, restricted=restricted.reshape(shape))
 
 
 # ---- K54: transport on the match_kernel-3 route — Sinkhorn from one T -------------------------------------------------------------

@@ -3625,6 +3625,39 @@ def _box3_sinkhorn_readout(t, mu, a, nu, b, h, w, k_unfolded, scale, iters, tau)
         return (f, g, *rows(g))
 
 
+# K55  label restriction on the match_kernel-3 route: the readout of T over the keys each query's label allows
+def box3_topk_labelled(t, mu, a, nu, b, q_label, k_label, h, w, k_unfolded, scale, k: int, transposed: bool = False):
+    """box3_topk over the keys each query's label allows (K55; forward only: the inputs are detached and no autograd node is made) ->
+    (idx int32 [B,N,k], val [B,N,k], lse [B,N]).  q_label, k_label [B,N] int32 / int64: key q is allowed for query p when
+    q_label[b,p] < 0 (unrestricted) or q_label[b,p] == k_label[b,q] (corr_topk_labelled's rule; int64 is narrowed after the clamp that
+    keeps a negative label negative).  The mask is applied inside the scan of T, before the candidate list and the sum: lse is over
+    the allowed keys, idx / val their k best in box3_topk's order.  A row with fewer than k allowed keys has val = -inf on the missing
+    ranks (idx stays inside [0, N)); a row with none has lse = -inf; no NaN from finite input.  With nothing restricted the outputs
+    are box3_topk's bit for bit.  `transposed` as for box3_match: the caller exchanges the two label arrays together with (mu, a) and
+    (nu, b).  Refusals in this order: a non-tensor or labels of another dtype (TypeError), labels of another shape, a bad k or one
+    that box3_topk_ok refuses (ValueError); tensors off the device; the shapes box3_topk refuses; COCOS_PRECISION=fp32.  There is no
+    materialised fall-back."""
+    name = "box3_topk_labelled"
+    _box3_readout_tensors(name, t, mu, a, nu, b)
+    B, N = mu.shape
+    q_label = _int_table(name, "q_label", q_label, (B, N))
+    k_label = _int_table(name, "k_label", k_label, (B, N))
+    k = _check_topk(name, k, N)
+    if not box3_topk_ok(k):      # (every LABELS instantiation up to cocos_box3_topk_max_k ships: DESIGN.md 3.41)
+        raise ValueError(f"{name}: k={k}: no instantiation serves it (box3_topk_ok)")
+    _gate(name, ((q_label, "q_label"), (k_label, "k_label")), False)
+    with torch.no_grad():
+        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
+        _gate(name, (), True)
+        idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
+        val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
+        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
+        _call(name, "cocos_box3_topk_labels_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
+              q_label.data_ptr(), k_label.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w),
+              float(k_unfolded), float(scale), k, _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+    return idx, val, lse
+
+
 class _Box3Lse(torch.autograd.Function):
     """K53.  Forward: box3_match's launch, its lse.  Backward: cocos_box3_lse_bwd_f16x3 writes G = g_lse softmax(z) scale a_p b_q
     in _Box3SoftmaxWarp's convention and under its Box3GradSink protocol, so T's node runs one K20 and one pair of GEMMs for every

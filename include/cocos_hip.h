@@ -1089,6 +1089,22 @@ int cocos_box3_topk_f16x3(const float* t_blocked, const float* mu_q, const float
 int cocos_box3_topk_bias_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
                                const float* k_bias, int* idx, float* val, float* lse, int B, int Nq, int Nk, int grid_h, int grid_w,
                                float k_unfolded, float scale, int k, int flags, cocos_stream_t stream);
+/* K55 — the label-restricted readout of these logits (the LABELS instantiations of the same kernel template): cocos_box3_topk_f16x3
+ *     over the allowed pairs only, K47's rule word for word:
+ *         allowed(p, q) = q_label[b,p] < 0  ||  q_label[b,p] == k_label[b,q]
+ *     q_label int32 [B,Nq], k_label int32 [B,Nk], any values, both 4-byte aligned.  idx / val are the k best allowed keys in K41's
+ *     order (tt descending, the lower index first among bitwise-equal tt), lse the log-sum-exp over the allowed keys.  A row with
+ *     fewer than k allowed keys has val = -inf on the missing ranks with idx clamped into [0, Nk); a row with none has lse = -inf;
+ *     finite input never produces a NaN.  The key labels are staged into LDS beside the key statistics as integer bits and compared
+ *     as integers; a disallowed element becomes -inf before the tile maximum, the list and the sum, so with every query label
+ *     negative the three outputs are cocos_box3_topk_f16x3's bit for bit.  With COCOS_BOX3_T_TRANSPOSED the labels belong to the
+ *     problem's queries and keys after the exchange: the caller swaps the two label arrays together with (mu, a) and (nu, b).
+ *     Restriction together with a bias is not built.
+ *     Arguments, supported shapes, flags, k and error codes of cocos_box3_topk_f16x3; a null label pointer or one that is not
+ *     4-byte aligned is COCOS_ERR_INVALID; all checked before any HIP call. */
+int cocos_box3_topk_labels_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k, const float* b_k,
+                                 const int* q_label, const int* k_label, int* idx, float* val, float* lse, int B, int Nq, int Nk,
+                                 int grid_h, int grid_w, float k_unfolded, float scale, int k, int flags, cocos_stream_t stream);
 size_t cocos_box3_softmax_warp_bwd_colpart_bytes(int B, int Nq, int Nk);
 int cocos_box3_softmax_warp_bwd_f16x3(const float* t_blocked, const float* mu_q, const float* a_q, const float* nu_k,
                                       const float* b_k, const void* vph, const void* vpl, const void* gph, const void* gpl,
