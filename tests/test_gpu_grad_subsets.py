@@ -245,6 +245,35 @@ def test_conv2d(layer, flavour, tol, monkeypatch):
             assert ("reflect_pad2d_fwd" in tags) == (not nhwc), (S, sorted(tags))
     b = relmax(tol)
     check_subsets(fn, inputs, ("x", "w", "b"), ref, dict(out=b, x=b, w=b, b=b), op=f"conv2d[{flavour}]", on_tags=on_tags)
+    if flavour != "bf16":
+        return
+    # ... and against the flavour's own operands (tests/conv_bf16_case.py): fp64 of the bf16-rounded x, w, dy, the bound being
+    # factor x the error of the framework's fp32 convolution on the same operands — four decades below the 1.5e-2 above
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import accuracy_case as ac
+    import conv_bf16_case as cb
+    case =cb.Case(layer, xs, Cout, k, stride, pad, 1, reflect, bias, "normal")
+    factor, names, arms = cb.factors(cb.routes(case)), dict(out="y", x="dx", w="dw", b="db"), {}
+
+    def ref_exact(inp, douts, vals32, diff_names):
+        args = (inp["x"], inp["w"], inp["b"], douts[0], stride, pad, 1, reflect)
+        got = dict(zip(cb.TENSORS, cb.reference(*args)))
+        arms.update(zip(cb.TENSORS, cb.fp32_arm(*args)))
+        return [got["y"]], {n: got[names[n]] for n in diff_names}
+
+    def exact(n):
+        t = names[n]
+
+        def f(got, want):
+            as3 = cb._AS3[t]
+            ek, ea = ac.rel_max(as3(got), as3(want)), ac.rel_max(as3(arms[t]), as3(want))
+            limit = ac.bound(ea, factor[(t, "rel_max")])
+            assert limit <= cb.CEILING, (t, limit)
+            return ek / limit, False
+        return f
+    check_subsets(fn, inputs, ("x", "w", "b"), ref_exact, {n: exact(n) for n in names}, op="conv2d[bf16-exact]", on_tags=on_tags)
 
 
 # ---------------------------------------------------------------------------------------------------------------- proj1x1
