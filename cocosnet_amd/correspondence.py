@@ -24,8 +24,8 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_box3_scope, _nll_scope, _refine_scope, _restrict_scope,
-                       _restrict_box3_scope, _sparse_scope, _sparse_search, _topk_arg, _transport_box3_scope, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
+from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope,
+                       _sparse_scope, _sparse_search, _topk_arg, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
                        correspondence_hot_path, correspondence_match, correspondence_match_box3, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
                        correspondence_sparse, correspondence_sparse_box3,
                        correspondence_transport, correspondence_transport_box3)
@@ -472,7 +472,8 @@ class NoVGGCorrespondence(NetworkBase):
         warp_topk).  Scope: match_kernel 3 with PONO_C on the plain flag set, COCOS_PRECISION=f16x3, no prepared exemplar; everything
         else raises a ValueError naming box transport before the network runs.  transport_match() is unaffected."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-        k, iters, tau = _transport_box3_scope("transport_match_box3", cfg, iters, tau, topk, False, self.inter_channels)
+        got = _box3_scope("transport_match_box3", "transport_box3", cfg, False, self.inter_channels, topk=topk, sinkhorn=(iters, tau))
+        k, (iters, tau) = got["topk"], got["sinkhorn"]
         if ref_img is None or ref_seg_map is None:
             raise ValueError("transport_match_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         with torch.no_grad():
@@ -512,7 +513,7 @@ class NoVGGCorrespondence(NetworkBase):
         if hard_warp and direction == "cols":
             raise ValueError("match_box3: hard_warp gathers exemplar patches for the content grid: it needs direction='rows'")
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-        _restrict_box3_scope("match_box3", cfg, restrict, None, self.inter_channels, plain_flags=False)
+        _box3_scope("match_box3", "restrict_box3", cfg, False, self.inter_channels, plain_flags=False, restrict=restrict, transport=None)
         if ref_img is None or ref_seg_map is None:
             raise ValueError("match_box3: restrict: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         with torch.no_grad():
@@ -545,7 +546,7 @@ class NoVGGCorrespondence(NetworkBase):
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
         if restrict is not None:      # (first: every scope message of a restricted call names restrict)
             _topk_arg("sparse_warp_box3", topk)
-            _restrict_box3_scope("sparse_warp_box3", cfg, restrict, transport, self.inter_channels)
+            _box3_scope("sparse_warp_box3", "restrict_box3", cfg, False, self.inter_channels, restrict=restrict, transport=transport)
         _box3_scope("sparse_warp_box3", "sparse_box3", cfg, False, self.inter_channels, topk=topk)      # refused before the network runs
         if transport is not None:
             _transport_dict("sparse_warp_box3", transport)
@@ -634,7 +635,7 @@ class NoVGGCorrespondence(NetworkBase):
         or 128-wide grids, no prepared exemplar; everything else raises ValueError before the network runs (no fall-back).
         match_loss(), match(), forward(), sparse_warp_box3() and flow_warp_box3() are unaffected."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
-        _nll_box3_scope(cfg, symmetric, False, self.inter_channels)      # out-of-scope flags are refused before the network runs
+        _box3_scope("match_loss_box3", "nll_box3", cfg, False, self.inter_channels, symmetric=symmetric)      # out-of-scope flags are refused before the network runs
         if ref_img is None or ref_seg_map is None:
             raise ValueError("match_loss_box3: ref_img and ref_seg_map are required (a prepared exemplar is out of scope)")
         if not torch.is_tensor(target) or target.dtype not in (torch.int32, torch.int64):

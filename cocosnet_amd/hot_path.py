@@ -239,18 +239,29 @@ class _BoxedCorr:
             self._cache[name] = fn()
         return self._cache[name]
 
+    def _t(self):
+        """T = xbox(C_raw) of the row orientation, made once: every pass and every readout reads it (the column direction transposed)"""
+        return self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
+
+    def stats(self):
+        """((mu, a), (nu, b)) of theta and phi, with autograd where the operands carry it"""
+        return self._get("q", lambda: _unfold3_stats(self.th, self.kc)), self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
+
+    def _sides(self, rows: bool):
+        """(the statistics of the side that asks, of the other side, T): theta's first for rows, phi's otherwise — T is then read
+        transposed"""
+        q, k = self.stats()
+        return (q, k, self._t()) if rows else (k, q, self._t())
+
     def rows(self, v):
-        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
-        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        return ops.box3_softmax_warp(t, mu, a, nu, b, v, self.fh, self.fw, self.kc, self.inv_t, sink=self._sink)
+        q, k, t = self._sides(True)
+        return ops.box3_softmax_warp(t, *q, *k, v, self.fh, self.fw, self.kc, self.inv_t, sink=self._sink)
 
     def cols(self, v):   # the same operator with the roles of theta and phi exchanged
-        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
-        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
         if self._sink is not None:
-            t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-            return ops.box3_softmax_warp(t, nu, b, mu, a, v, self.fh, self.fw, self.kc, self.inv_t, transposed=True, sink=self._sink)
+            q, k, t = self._sides(False)
+            return ops.box3_softmax_warp(t, *q, *k, v, self.fh, self.fw, self.kc, self.inv_t, transposed=True, sink=self._sink)
+        (mu, a), (nu, b) = self.stats()
         t = self._get("t_cols", lambda: ops.box3_corr_xbox(self.ph, self.th, None, self._raw_planes))
         return ops.box3_softmax_warp(t, nu, b, mu, a, v, self.fh, self.fw, self.kc, self.inv_t)
 
@@ -258,10 +269,7 @@ class _BoxedCorr:
         """(idx int32, max, lse) [B,N] of the rows of the logits (rows) or of their transpose (not rows): K37 on the row pass's T —
         read transposed for the column direction, with or without a gradient sink (nothing is differentiated).  k > 1: the k best
         per row, (idx [B,N,k], val [B,N,k], lse [B,N]), from K41 on the same T and the same cached statistics."""
-        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
-        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        q, kk, t = self._sides(rows)
         if k == 1:
             return ops.box3_match(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows)
         return ops.box3_topk(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
@@ -269,40 +277,27 @@ class _BoxedCorr:
     def match_biased(self, rows: bool, bias, k: int = 1):
         """match(rows, k) over z + bias[key] (K54, ops.box3_topk_biased) -> (idx [B,N,k], val, lse), on the same T and the same cached
         statistics; `bias` [B,N] fp32 belongs to the keys of the direction read (phi's positions for rows, theta's otherwise)"""
-        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
-        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        q, kk, t = self._sides(rows)
         return ops.box3_topk_biased(t, *q, *kk, bias, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
 
     def match_labelled(self, rows: bool, q_label, k_label, k: int = 1):
         """match(rows, k) over the keys each query's label allows (K55, ops.box3_topk_labelled) -> (idx [B,N,k], val, lse), on the same
         T and the same cached statistics; q_label [B,N] belongs to the positions that ask in the direction read (theta's for rows,
         phi's otherwise), k_label to the other side: the caller passes them in that order, statistics and T's orientation follow"""
-        mu, a = self._get("q", lambda: _unfold3_stats(self.th, self.kc))
-        nu, b = self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        q, kk = ((mu, a), (nu, b)) if rows else ((nu, b), (mu, a))
+        q, kk, t = self._sides(rows)
         return ops.box3_topk_labelled(t, *q, *kk, q_label, k_label, self.fh, self.fw, self.kc, self.inv_t, k, transposed=not rows)
 
     def sinkhorn(self, iters: int, tau: float = 1.0, readout: bool = False):
         """(f, g, row_lse) [B,N] of ops.box3_sinkhorn on the row pass's T and the cached statistics (K54): 2 iters + 1 launches, no
         second correlation GEMM.  `readout`: (f, g, idx [B,N,1], val [B,N,1], row_lse) — the last launch is the k = 1 readout of z + g"""
         iters, tau = ops._sinkhorn_args("box3_sinkhorn", iters, tau)
-        (mu, a), (nu, b) = self.stats()
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        out = ops._box3_sinkhorn_readout(t, mu, a, nu, b, self.fh, self.fw, self.kc, self.inv_t, iters, tau)
+        q, kk, t = self._sides(True)
+        out = ops._box3_sinkhorn_readout(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, iters, tau)
         return out if readout else (out[0], out[1], out[4])
-
-    def stats(self):
-        """((mu, a), (nu, b)) of theta and phi, with autograd where the operands carry it"""
-        return self._get("q", lambda: _unfold3_stats(self.th, self.kc)), self._get("k", lambda: _unfold3_stats(self.ph, self.kc))
 
     def lse(self, rows: bool):
         """match(rows)'s lse [B,N] bit for bit, WITH a gradient (K53, ops.box3_lse): the passes over the one T share its gradient sink"""
-        q, kk = self.stats()
-        t = self._get("t_rows", lambda: ops.box3_corr_xbox(self.th, self.ph, self._sink, self._raw_planes))
-        q, kk = (q, kk) if rows else (kk, q)
+        q, kk, t = self._sides(rows)
         return ops.box3_lse(t, *q, *kk, self.fh, self.fw, self.kc, self.inv_t, transposed=not rows, sink=self._sink)
 
 
@@ -703,6 +698,18 @@ def _route_channels(name: str, member: str, channels):
         raise ValueError(f"{name}: needs {ops.FUSED_K} channels, got {channels}{_ROUTE[member]}")
 
 
+_EXEMPLAR_FWD_ONLY = "a prepared exemplar is out of scope (it is forward-only; the {} differentiates phi)"
+#: the match_kernel-3 members (K51 - K55): what its route messages carry after the name, whether ops.MATCH_FUSED belongs to the scope,
+#: why a prepared exemplar is refused (None: the member takes no such argument), the member's own arguments checked before the flag
+#: set and after the channels (_BOX3_ARG)
+_BOX3_MEMBER = {"sparse_box3": ("", False, _EXEMPLAR_FWD_ONLY.format("sparse warp"), ("topk",), ()),
+                "flow_box3": ("", False, _EXEMPLAR_FWD_ONLY.format("refinement"), (), ("radius", "refine_temperature")),
+                "nll_box3": ("", False, _EXEMPLAR_FWD_ONLY.format("loss"), ("symmetric",), ()),
+                "transport_box3": (": transport", True, "transport with a prepared exemplar is out of scope (not built)"
+                                   + _ROUTE["transport_box3"], ("topk", "sinkhorn"), ()),
+                "restrict_box3": (": restrict", True, None, ("restrict", "transport"), ())}
+
+
 def _topk_arg(name: str, topk):
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= ops.MATCH_TOPK_MAX:
         raise ValueError(f"{name}: topk={topk!r}: expected an integer in 1..{ops.MATCH_TOPK_MAX}")
@@ -713,6 +720,63 @@ def _refine_temperature_arg(name: str, refine_temperature):
     if refine_temperature is not None and not (isinstance(refine_temperature, (int, float)) and not isinstance(refine_temperature, bool)
                                                and refine_temperature > 0):
         raise ValueError(f"{name}: refine_temperature={refine_temperature!r}: expected a positive number (None: the readout's temperature)")
+
+
+def _radius_arg(name: str, radius):
+    top = ops.MATCH_REFINE_MAX_RADIUS
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
+        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
+
+
+def _symmetric_arg(name: str, symmetric):
+    if not isinstance(symmetric, bool):
+        raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
+
+
+def _restrict_arg(name: str, restrict):
+    """ValueError for a `restrict` that is neither "label" nor a pair of tensors, TypeError for a pair of another dtype"""
+    pair = isinstance(restrict, (tuple, list)) and len(restrict) == 2 and all(torch.is_tensor(t) for t in restrict)
+    if not (pair or (isinstance(restrict, str) and restrict == "label")):
+        what = repr(restrict) if isinstance(restrict, str) else type(restrict).__name__
+        raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
+    if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
+        raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
+
+
+def _no_transport_arg(name: str, transport):
+    if transport is not None:
+        raise ValueError(f"{name}: restrict with transport is out of scope (not built){_ROUTE['restrict_box3']}")
+
+
+#: the checks of the members' own arguments: (name, value) -> what the caller goes on with, or None
+_BOX3_ARG = {"topk": _topk_arg, "radius": _radius_arg, "refine_temperature": _refine_temperature_arg, "symmetric": _symmetric_arg,
+             "sinkhorn": lambda name, v: ops._sinkhorn_args(f"{name}: transport", *v), "restrict": _restrict_arg,
+             "transport": _no_transport_arg}
+
+
+def _box3_scope(name: str, member: str, cfg: HotPathConfig, has_exemplar: bool = False, channels=None, *, plain_flags: bool = True, **args):
+    """ValueError (TypeError for labels of another dtype) for everything outside the scope of a match_kernel-3 member, before any
+    tensor is looked at, in _BOX3_MEMBER[member]'s order: the member's own arguments (`args`, by name), the flag set (_route_scope
+    with kernel = 3: match_kernel 3, PONO_C, with `plain_flags` the plain flags, COCOS_PRECISION=f16x3, ops.MATCH_FUSED where it
+    belongs), a prepared exemplar, the channels (`channels` may be a callable: no tensor is looked at before this step), the arguments
+    that come last -> {argument: what its check returned}"""
+    tag, match_fused, no_exemplar, before, after = _BOX3_MEMBER[member]
+    got = {a: _BOX3_ARG[a](name, args[a]) for a in before}
+    _route_scope(name + tag, cfg, member, plain_flags=plain_flags, match_fused=match_fused, kernel=3)
+    if has_exemplar and no_exemplar is not None:
+        raise ValueError(f"{name}: {no_exemplar}")
+    _route_channels(name + tag, member, channels() if callable(channels) else channels)
+    got.update({a: _BOX3_ARG[a](name, args[a]) for a in after})
+    return got
+
+
+def _box3_fused_shapes(name: str, member: str, B, C, fh, fw, gh, gw, k=1):
+    """ValueError unless the grids are equal, ops.box3_fused_ok takes them and ops.box3_topk_ok serves k: the members that read T have
+    no materialised fall-back"""
+    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw) or not ops.box3_topk_ok(k):
+        raise ValueError(f"{name}{_BOX3_MEMBER[member][0]}: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} "
+                         f"exemplar grid at topk={k} (equal 64- or 128-wide grids, positions a multiple of 256), and there is no "
+                         f"materialised fall-back{_ROUTE[member]}")
 
 
 def _raw(t):
@@ -767,6 +831,36 @@ def _rank_first(t, shape, k):
     return t.reshape(tuple(shape) + (k,)).permute(0, 3, 1, 2).contiguous()
 
 
+def _match_result(idx, val, lse, shape, other, restricted=None):
+    """The readout of a kernel's (idx int32 [B,N,k], val [B,N,k], lse [B,N]) on the [B,h,w] `shape` of the side that asks: a MatchReadout
+    for k = 1, a TopkMatchReadout otherwise; `other`: the grid indexed, `restricted` [B,N] bool or None (K47, K55)"""
+    k = idx.shape[-1]
+    restricted = None if restricted is None else restricted.reshape(shape)
+    if k == 1:
+        m = _readout(idx[..., 0], val[..., 0], lse, shape, other)
+        m.restricted = restricted
+        return m
+    lse = lse.reshape(shape)
+    val = _rank_first(val, shape, k)
+    return TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.unsqueeze(1)), logit=val, lse=lse,
+                            grid=other, restricted=restricted)
+
+
+def _boxed(theta_raw, phi_raw, inv_t, *, exemplar=None, grad: bool = False):
+    """The _BoxedCorr of a (theta_raw, phi_raw) pair as correspondence_hot_path makes it: a lazy pair stays lazy where
+    ops.PROJ_BWD_FUSED lets _BoxedCorr take it (K25 / proj_unfold3_stats inside), everything else is projected first (K0).  Forward
+    only — the operands are detached — unless `grad` (K53: autograd stays, and the lse passes share one gradient sink).  `exemplar`: a
+    prepared exemplar in place of phi_raw — the record's planes and (nu, b): the key side is not recomputed."""
+    if exemplar is not None:
+        th = _raw(theta_raw).detach()
+        return _BoxedCorr(th, th.view_as(th), inv_t, prepared_k=exemplar.box_planes(th.shape[0]))
+    if not (isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED):
+        theta_raw, phi_raw = _raw(theta_raw), _raw(phi_raw)
+    if grad:
+        return _BoxedCorr(theta_raw, phi_raw, inv_t, share_sink=True)
+    return _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
+
+
 def _refine_scope(name: str, cfg: HotPathConfig, refine, refine_temperature, topk, has_exemplar: bool, channels=None):
     """ValueError for a `refine` that is no radius, and — with refine > 0 — for everything outside the sub-cell refinement's scope (K44:
     top-1 on the fused match_kernel-1 route, no prepared exemplar); checked before any tensor is looked at.  `channels`: the width of
@@ -803,12 +897,7 @@ def _restrict_scope(name: str, cfg: HotPathConfig, restrict, has_exemplar: bool,
     dense selector); checked before any tensor is looked at.  Every message names `restrict`."""
     if restrict is None:
         return
-    pair = isinstance(restrict, (tuple, list)) and len(restrict) == 2 and all(torch.is_tensor(t) for t in restrict)
-    if not (pair or (isinstance(restrict, str) and restrict == "label")):
-        what = repr(restrict) if isinstance(restrict, str) else type(restrict).__name__
-        raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
-    if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
-        raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
+    _restrict_arg(name, restrict)
     _route_scope(name, cfg, "restrict", plain_flags=False, match_fused=True)
     if has_exemplar:
         raise ValueError(f"{name}: restrict with a prepared exemplar is out of scope (not built)")
@@ -947,8 +1036,6 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
                 asks, other_side = (qn, kn) if rows else (kn, qn)
                 q_eff, k_eff, restricted = restrict_fallback(*(labels if rows else labels[::-1]), k)
                 idx, mx, lse = ops.corr_topk_labelled(asks, other_side, q_eff, k_eff, inv_t, k, planes)
-                if k == 1:
-                    idx, mx = idx[..., 0], mx[..., 0]
             elif k == 1:
                 idx, mx, lse = ops.corr_match(qn, kn, inv_t, planes) if rows else ops.corr_match(kn, qn, inv_t, planes)
                 if refine:      # K44: the window scores come from the operand planes that chose the centre
@@ -961,13 +1048,7 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
               and ops.box3_fused_ok(B, C, fh, fw)):
             # the reference's default on the fused family's shapes: ONE HWxHW tensor (T, from the x-box GEMM's epilogue), read once
             # by K37 (k > 1: K41) — the _BoxedCorr is made as correspondence_hot_path / _attention_with_exemplar make theirs
-            if exemplar is not None:       # the record's planes and (nu, b): the key side is not recomputed
-                th = _raw(theta_raw).detach()
-                boxed = _BoxedCorr(th, th.view_as(th), inv_t, prepared_k=exemplar.box_planes(B))
-            elif isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:      # K25 / proj_unfold3_stats inside _BoxedCorr
-                boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
-            else:
-                boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
+            boxed = _boxed(theta_raw, phi_raw, inv_t, exemplar=exemplar)
             idx, mx, lse = boxed.match(rows, k)
             del boxed
         else:
@@ -981,17 +1062,10 @@ def correspondence_match(theta_raw, phi_raw, cfg: HotPathConfig, temperature=0.0
             del f
         own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
         shape = (B,) + own
-        if k > 1:
-            lse = lse.reshape(shape)
-            val = _rank_first(mx, shape, k)
-            return TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.unsqueeze(1)), logit=val,
-                                    lse=lse, grid=other, restricted=None if restricted is None else restricted.reshape(shape))
-        m = _readout(idx, mx, lse, shape, other)
+        m = _match_result(idx.reshape(B, -1, k), mx.reshape(B, -1, k), lse, shape, other, restricted)
         if refine:
             m.offset = _rank_first(off, shape, 2)
             m.window_prob = torch.exp(lse_win - lse).reshape(shape)
-        if restricted is not None:
-            m.restricted = restricted.reshape(shape)
         return m
 
 
@@ -1227,38 +1301,19 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
 
 
 # ---- K51 / K52: the trainable routes on match_kernel 3 (the k-sparse warp, the sub-cell flow) -----------------------------------------
-def _box3_scope(name: str, member: str, cfg: HotPathConfig, has_exemplar: bool = False, channels=None, *, topk=None, radius=None,
-                refine_temperature=None):
-    """ValueError for everything outside the scope of a trainable match_kernel-3 route (match_kernel 3, PONO_C, the plain flag set,
-    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels), before any tensor is looked at.  "sparse_box3" (K51): `topk` first
-    -> k.  "flow_box3" (K52): `radius` in 1..ops.MATCH_REFINE_MAX_RADIUS and a positive refinement temperature last."""
-    sparse = member == "sparse_box3"
-    k = _topk_arg(name, topk) if sparse else None
-    _route_scope(name, cfg, member, plain_flags=True, match_fused=False, kernel=3)
-    if has_exemplar:
-        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the {'sparse warp' if sparse else 'refinement'} "
-                         "differentiates phi)")
-    _route_channels(name, member, channels)
-    if not sparse:
-        top = ops.MATCH_REFINE_MAX_RADIUS
-        if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
-            raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
-        _refine_temperature_arg(name, refine_temperature)
-    return k
-
-
-def _box3_select_and_stats(theta_raw, phi_raw, cfg: HotPathConfig, temperature, topk=1):
-    """The prologue of both routes -> (th, ph, mu, a, nu, b, readout).  Lazy operands are projected first, with autograd (K0; the
-    handle caches the projection, so this must not happen inside the selection's no_grad block); the selection still gets the
-    operands as they came: its candidates are correspondence_match's on the same arguments bit for bit.  The readout (a few [B,·,h,w]
+def _box3_select_and_stats(theta_raw, phi_raw, select):
+    """The prologue of the trainable routes -> (th, ph, mu, a, nu, b, what `select` returned).  Lazy operands are projected first, with
+    autograd (K0; the handle caches the projection, so this must not happen inside the selection's no_grad block); `select()` — the
+    member's selector: correspondence_match, _restrict_box3_select or _transport_box3_select on the operands as they came, so its
+    candidates are that entry point's bit for bit — runs without gradient and drops its T inside.  What it returns (a few [B,·,h,w]
     tensors) lives across the two statistics launches, which run before the caller's warp_values: the same launches, reordered."""
     th, ph = _raw(theta_raw), _raw(phi_raw)
     with torch.no_grad():
-        m = correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk)      # selection: no gradient; its T is dropped inside
+        picked = select()
     kc = float(th.shape[1] * 9)
     mu, a = _unfold3_stats(th, kc)      # K12 with autograd: the statistics' share of the gradient goes back through its backward
     nu, b = _unfold3_stats(ph, kc)
-    return th, ph, mu, a, nu, b, m
+    return th, ph, mu, a, nu, b, picked
 
 
 def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
@@ -1292,8 +1347,8 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     name = "correspondence_sparse_box3"
     if restrict is not None:      # (first: every scope message of a restricted call names restrict)
         _topk_arg(name, topk)
-        _restrict_box3_scope(name, cfg, restrict, transport, theta_raw.shape[1])
-    k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)
+        _box3_scope(name, "restrict_box3", cfg, False, theta_raw.shape[1], restrict=restrict, transport=transport)
+    k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)["topk"]
     if transport is not None:
         iters, tau = _transport_dict(name, transport)
     _same_kind(name, theta_raw, phi_raw)
@@ -1310,26 +1365,22 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     extra, g = {}, None
     if restrict is not None:
         labels = _restrict_labels(name, restrict, seg_map, ref_seg_map, down, B, (fh, fw), (gh, gw))
-        _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k)
-        th, ph = _raw(theta_raw), _raw(phi_raw)      # projected with autograd first, as _box3_select_and_stats does
-        idx, _, _, restricted = _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, True, labels, k)
+        _box3_fused_shapes(name, "restrict_box3", B, C, fh, fw, gh, gw, k)
+        *operands, (idx, _, _, restricted) = _box3_select_and_stats(
+            theta_raw, phi_raw, lambda: _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, True, labels, k))
         extra = {"match_restricted": restricted.reshape(B, fh, fw)}
         idx = idx.to(torch.int64).contiguous()
-        kc = float(C * 9)
-        operands = [th, ph, *_unfold3_stats(th, kc), *_unfold3_stats(ph, kc)]
     elif transport is None:
-        *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature, k)
+        *operands, m = _box3_select_and_stats(theta_raw, phi_raw, lambda: correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=k))
         with torch.no_grad():
             idx = m.index.reshape(B, k, N).permute(0, 2, 1).contiguous()
             del m
     else:
-        _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k)
-        th, ph = _raw(theta_raw), _raw(phi_raw)      # projected with autograd first, as _box3_select_and_stats does
-        f, g, idx, _, row_lse, _ = _transport_box3_select(theta_raw, phi_raw, 1.0 / temperature, iters, tau, k, key_mass=False)
+        _box3_fused_shapes(name, "transport_box3", B, C, fh, fw, gh, gw, k)
+        *operands, (f, g, idx, _, row_lse, _) = _box3_select_and_stats(
+            theta_raw, phi_raw, lambda: _transport_box3_select(theta_raw, phi_raw, 1.0 / temperature, iters, tau, k, key_mass=False))
         extra = {"potential_k": g.reshape(B, gh, gw), "match_mass": torch.exp(f + row_lse + math.log(N)).reshape(B, fh, fw)}
         idx = idx.to(torch.int64).contiguous()
-        kc = float(C * 9)
-        operands = [th, ph, *_unfold3_stats(th, kc), *_unfold3_stats(ph, kc)]
     with torch.no_grad():
         v = _flat(ops.warp_values(ref_img, ref_seg_map if direct_mask else None, down))
     o, w = ops.box3_sparse_softmax_warp(*operands, v, idx, 1.0 / temperature, return_weights=True, k_bias=g)
@@ -1345,40 +1396,13 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
 
 
 # ---- K55: label-restricted candidates on the match_kernel-3 route — the mask inside the scan of T ---------------------------------
-def _restrict_box3_scope(name: str, cfg: HotPathConfig, restrict, transport=None, channels=None, plain_flags: bool = True):
-    """ValueError for a `restrict` that is neither "label" nor a pair of integer tensors (TypeError for another dtype) and for
-    everything outside the box restriction's scope, before any tensor is looked at: no transport, then the flag set (match_kernel 3,
-    PONO_C, with `plain_flags` the plain flags, COCOS_PRECISION=f16x3, ops.MATCH_FUSED), the channels.  Every message names restrict;
-    every route message ends in _ROUTE["restrict_box3"]."""
-    pair = isinstance(restrict, (tuple, list)) and len(restrict) == 2 and all(torch.is_tensor(t) for t in restrict)
-    if not (pair or (isinstance(restrict, str) and restrict == "label")):
-        what = repr(restrict) if isinstance(restrict, str) else type(restrict).__name__
-        raise ValueError(f"{name}: restrict={what}: expected None, 'label' or a pair (q_labels, k_labels) of integer tensors")
-    if pair and any(t.dtype not in (torch.int32, torch.int64) for t in restrict):
-        raise TypeError(f"{name}: restrict: the labels must be int32 or int64 tensors, got {restrict[0].dtype} and {restrict[1].dtype}")
-    if transport is not None:
-        raise ValueError(f"{name}: restrict with transport is out of scope (not built){_ROUTE['restrict_box3']}")
-    _route_scope(f"{name}: restrict", cfg, "restrict_box3", plain_flags=plain_flags, match_fused=True, kernel=3)
-    _route_channels(f"{name}: restrict", "restrict_box3", channels)
-
-
-def _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k):
-    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw) or not ops.box3_topk_ok(k):
-        raise ValueError(f"{name}: restrict: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid at "
-                         f"topk={k} (equal 64- or 128-wide grids, positions a multiple of 256), and there is no materialised fall-back"
-                         f"{_ROUTE['restrict_box3']}")
-
-
 def _restrict_box3_select(theta_raw, phi_raw, inv_t, rows: bool, labels, k):
     """One _BoxedCorr as correspondence_match's fused match_kernel-3 branch makes it (lazy projections through K25 where allowed), one
     x-box GEMM and one labelled launch -> (idx int32 [B,N,k], val, lse, restricted bool [B,N]), all without gradient; `labels`
     (content, exemplar) [B,N] — the side that asks brings its labels, statistics and labels swap together; T is dropped on return"""
     with torch.no_grad():
         q_eff, k_eff, restricted = restrict_fallback(*(labels if rows else labels[::-1]), k)
-        if isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:
-            boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
-        else:
-            boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
+        boxed = _boxed(theta_raw, phi_raw, inv_t)
         idx, val, lse = boxed.match_labelled(rows, q_eff, k_eff, k)
         del boxed
         return idx, val, lse, restricted
@@ -1406,7 +1430,7 @@ def correspondence_match_box3(theta_raw, phi_raw, cfg: HotPathConfig, temperatur
     if direction not in ("rows", "cols"):
         raise ValueError(f"{name}: direction {direction!r}: expected 'rows' or 'cols'")
     k = _topk_arg(name, topk)
-    _restrict_box3_scope(name, cfg, restrict, None, theta_raw.shape[1], plain_flags=False)
+    _box3_scope(name, "restrict_box3", cfg, False, theta_raw.shape[1], plain_flags=False, restrict=restrict, transport=None)
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     _fused_width(name, theta_raw, phi_raw)
@@ -1416,51 +1440,20 @@ def correspondence_match_box3(theta_raw, phi_raw, cfg: HotPathConfig, temperatur
     labels = _restrict_labels(name, restrict, seg_map, ref_seg_map, cfg.down, B, (fh, fw), (gh, gw))
     if not _hip_fp32(theta_raw):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
-    _restrict_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+    _box3_fused_shapes(name, "restrict_box3", B, C, fh, fw, gh, gw, k)
     idx, val, lse, restricted = _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, rows, labels, k)
     with torch.no_grad():
         own, other = ((fh, fw), (gh, gw)) if rows else ((gh, gw), (fh, fw))
-        shape = (B,) + own
-        if k == 1:
-            m = _readout(idx[..., 0], val[..., 0], lse, shape, other)
-            m.restricted = restricted.reshape(shape)
-            return m
-        lse = lse.reshape(shape)
-        v = _rank_first(val, shape, k)
-        return TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(v - lse.unsqueeze(1)), logit=v, lse=lse,
-                                grid=other, restricted=restricted.reshape(shape))
+        return _match_result(idx, val, lse, (B,) + own, other, restricted)
 
 
 # ---- K54: transport on the match_kernel-3 route — Sinkhorn from one T -------------------------------------------------------------
-def _transport_box3_scope(name: str, cfg: HotPathConfig, iters, tau, topk, has_exemplar: bool = False, channels=None):
-    """ValueError for everything outside box transport's scope, before any tensor is looked at, in §3.33's order: the arguments (topk,
-    iters, tau), then the flag set (match_kernel 3, PONO_C, the plain flags, COCOS_PRECISION=f16x3, ops.MATCH_FUSED), a prepared
-    exemplar, the channels; every route message ends in _ROUTE["transport_box3"] -> (k, iters, tau)"""
-    k = _topk_arg(name, topk)
-    iters, tau = ops._sinkhorn_args(f"{name}: transport", iters, tau)
-    _route_scope(f"{name}: transport", cfg, "transport_box3", plain_flags=True, match_fused=True, kernel=3)
-    if has_exemplar:
-        raise ValueError(f"{name}: transport with a prepared exemplar is out of scope (not built){_ROUTE['transport_box3']}")
-    _route_channels(f"{name}: transport", "transport_box3", channels)
-    return k, iters, tau
-
-
-def _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k):
-    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw) or not ops.box3_topk_ok(k):
-        raise ValueError(f"{name}: transport: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid at "
-                         f"topk={k} (equal 64- or 128-wide grids, positions a multiple of 256), and there is no materialised fall-back"
-                         f"{_ROUTE['transport_box3']}")
-
-
 def _transport_box3_select(theta_raw, phi_raw, inv_t, iters, tau, k, key_mass: bool):
     """One _BoxedCorr as correspondence_match's fused match_kernel-3 branch makes it (lazy projections through K25 where allowed), one
     x-box GEMM, 2 iters + 1 biased launches, one top-k launch when k > 1, one column launch when `key_mass` -> (f, g, idx [B,N,k],
     z [B,N,k], lse [B,N] of z + g, col_lse or None), all without gradient; T is dropped on return"""
     with torch.no_grad():
-        if isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED:
-            boxed = _BoxedCorr(theta_raw.detach(), phi_raw.detach(), inv_t)
-        else:
-            boxed = _BoxedCorr(_raw(theta_raw).detach(), _raw(phi_raw).detach(), inv_t)
+        boxed = _boxed(theta_raw, phi_raw, inv_t)
         f, g, idx, z, lse = boxed.sinkhorn(iters, tau, readout=True)
         if k > 1:
             idx, z, lse = boxed.match_biased(True, g, k)      # (lse is the last launch's bit for bit)
@@ -1484,7 +1477,8 @@ def correspondence_transport_box3(theta_raw, phi_raw, cfg: HotPathConfig, temper
     anything else raises a ValueError naming box transport before any tensor is looked at; then equal grids that ops.box3_fused_ok
     takes and a topk that ops.box3_topk_ok serves (ValueError: there is no materialised fall-back).  CPU tensors raise CocosHipError."""
     name = "correspondence_transport_box3"
-    k, iters, tau = _transport_box3_scope(name, cfg, iters, tau, topk, False, theta_raw.shape[1])
+    got = _box3_scope(name, "transport_box3", cfg, False, theta_raw.shape[1], topk=topk, sinkhorn=(iters, tau))
+    k, (iters, tau) = got["topk"], got["sinkhorn"]
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     _fused_width(name, theta_raw, phi_raw)
@@ -1492,17 +1486,11 @@ def correspondence_transport_box3(theta_raw, phi_raw, cfg: HotPathConfig, temper
         raise ValueError(f"{name}: topk={k} exceeds the {Nk} exemplar positions")
     if not _hip_fp32(theta_raw):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
-    _transport_box3_shapes(name, B, C, fh, fw, gh, gw, k)
+    _box3_fused_shapes(name, "transport_box3", B, C, fh, fw, gh, gw, k)
     f, g, idx, z, lse, col_lse = _transport_box3_select(theta_raw, phi_raw, 1.0 / temperature, iters, tau, k, key_mass=True)
     with torch.no_grad():
         shape = (B, fh, fw)
-        if k == 1:
-            m = _readout(idx[..., 0], z[..., 0], lse, shape, (gh, gw))
-        else:
-            val = _rank_first(z, shape, k)
-            m = TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.reshape(shape).unsqueeze(1)),
-                                 logit=val, lse=lse.reshape(shape), grid=(gh, gw))
-        return {"readout": m, "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
+        return {"readout": _match_result(idx, z, lse, shape, (gh, gw)), "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
                 "match_mass": torch.exp(f + lse + math.log(N)).reshape(shape),
                 "key_mass": torch.exp(g + col_lse + math.log(Nk)).reshape(B, gh, gw)}
 
@@ -1571,13 +1559,7 @@ def correspondence_transport(theta_raw, phi_raw, cfg: HotPathConfig, temperature
         idx, z, lse = ops.corr_topk_biased(qn, kn, g, inv_t, k, planes)       # (k = 1: lse is row_lse bit for bit)
         _, _, col_lse = ops.corr_topk_biased(kn, qn, f, inv_t, 1, planes)
         shape = (B, fh, fw)
-        if k == 1:
-            m = _readout(idx[..., 0], z[..., 0], lse, shape, (gh, gw))
-        else:
-            val = _rank_first(z, shape, k)
-            m = TopkMatchReadout(index=_rank_first(idx.to(torch.int64), shape, k), prob=torch.exp(val - lse.reshape(shape).unsqueeze(1)),
-                                 logit=val, lse=lse.reshape(shape), grid=(gh, gw))
-        return {"readout": m, "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
+        return {"readout": _match_result(idx, z, lse, shape, (gh, gw)), "potential_q": f.reshape(shape), "potential_k": g.reshape(B, gh, gw),
                 "match_mass": torch.exp(f + row_lse + math.log(N)).reshape(shape),
                 "key_mass": torch.exp(g + col_lse + math.log(Nk)).reshape(B, gh, gw)}
 
@@ -1587,10 +1569,8 @@ def _flow_scope(cfg: HotPathConfig, radius, refine_temperature):
     """ValueError for everything outside correspondence_flow's scope: correspondence_sparse's flag checks (_sparse_scope, in its words),
     then the window radius and the refinement temperature; checked before any tensor is looked at"""
     _sparse_scope(cfg, 1)
-    name, top = "correspondence_flow", ops.MATCH_REFINE_MAX_RADIUS
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= top:
-        raise ValueError(f"{name}: radius={radius!r}: expected an integer in 1..{top}")
-    _refine_temperature_arg(name, refine_temperature)
+    _radius_arg("correspondence_flow", radius)
+    _refine_temperature_arg("correspondence_flow", refine_temperature)
 
 
 def _flow_result(ref_img, idx, off, lse_win, lse, grid, kgrid, down):
@@ -1686,7 +1666,7 @@ def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, te
     if not (_hip_fp32(theta_raw) and _hip_fp32(ref_img)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP fp32 tensors; the correspondence hot path has no CPU fallback")
     inv_rt = 1.0 / (temperature if refine_temperature is None else refine_temperature)
-    *operands, m = _box3_select_and_stats(theta_raw, phi_raw, cfg, temperature)
+    *operands, m = _box3_select_and_stats(theta_raw, phi_raw, lambda: correspondence_match(theta_raw, phi_raw, cfg, temperature))
     idx, lse = m.index.reshape(B, N), m.lse.reshape(B, N)
     del m
     off, lse_win = ops.box3_soft_match_offset(*operands, idx, (fh, fw), (gh, gw), inv_rt, radius)
@@ -1697,10 +1677,8 @@ def correspondence_flow_box3(theta_raw, phi_raw, ref_img, cfg: HotPathConfig, te
 def _nll_scope(cfg: HotPathConfig, symmetric=True):
     """ValueError for every flag outside correspondence_nll's scope — correspondence_sparse's, in messages that name match_loss;
     checked before any tensor is looked at"""
-    name = "match_loss"
-    if not isinstance(symmetric, bool):
-        raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
-    _route_scope(name, cfg, "nll", plain_flags=True, match_fused=False)
+    _symmetric_arg("match_loss", symmetric)
+    _route_scope("match_loss", cfg, "nll", plain_flags=True, match_fused=False)
 
 
 def _nll_targets(target, weight, B, fh, fw, Nk, name="match_loss"):
@@ -1771,19 +1749,6 @@ def correspondence_nll(theta_raw, phi_raw, target, cfg: HotPathConfig, temperatu
 
 
 # ---- K53: the supervised match loss on the match_kernel-3 route ----------------------------------------------------------------------
-def _nll_box3_scope(cfg: HotPathConfig, symmetric=True, has_exemplar: bool = False, channels=None):
-    """ValueError for everything outside correspondence_nll_box3's scope (match_kernel 3, PONO_C, the plain flag set,
-    COCOS_PRECISION=f16x3, no prepared exemplar, 256 channels), in messages that name match_loss_box3; checked before any tensor is
-    looked at"""
-    name = "match_loss_box3"
-    if not isinstance(symmetric, bool):
-        raise ValueError(f"{name}: symmetric={symmetric!r}: expected True or False")
-    _route_scope(name, cfg, "nll_box3", plain_flags=True, match_fused=False, kernel=3)
-    if has_exemplar:
-        raise ValueError(f"{name}: a prepared exemplar is out of scope (it is forward-only; the loss differentiates phi)")
-    _route_channels(name, "nll_box3", channels)
-
-
 def correspondence_nll_box3(theta_raw, phi_raw, target, cfg: HotPathConfig, temperature=0.01, *, weight=None, symmetric=True, exemplar=None):
     """correspondence_nll on the reference's default route, match_kernel 3 (K53): with z[p,q] the box logit of the 3x3-unfolded,
     centred, normalised vectors over the temperature, match_nll = lse_q z[p,.] - z[p,t_p] and back_nll = lse_p z[.,t_p] - z[p,t_p].
@@ -1805,22 +1770,18 @@ def correspondence_nll_box3(theta_raw, phi_raw, target, cfg: HotPathConfig, temp
     128-wide grids that ops.box3_fused_ok takes: everything else raises ValueError in a message that names match_loss_box3 — there is
     no fall-back to the materialised chain.  CPU tensors raise CocosHipError."""
     name = "match_loss_box3"
-    _nll_box3_scope(cfg, symmetric, exemplar is not None)      # before any tensor is looked at
-    _route_channels(name, "nll_box3", theta_raw.shape[1])
+    _box3_scope(name, "nll_box3", cfg, exemplar is not None, lambda: theta_raw.shape[1], symmetric=symmetric)
     _same_kind(name, theta_raw, phi_raw)
     B, C, fh, fw, gh, gw, N, Nk = _grids(theta_raw, phi_raw)
     _fused_width(name, theta_raw, phi_raw)
     _nll_targets(target, weight, B, fh, fw, Nk, name)
     if not (_hip_fp32(theta_raw) and _hip_fp32(phi_raw) and target.is_cuda and (weight is None or weight.is_cuda)):
         raise ops._lib.CocosHipError(f"{name}: expected CUDA/HIP tensors (fp32 features); the correspondence hot path has no CPU fallback")
-    if (gh, gw) != (fh, fw) or not ops.box3_fused_ok(B, C, fh, fw):
-        raise ValueError(f"{name}: the fused box route does not take a {fh}x{fw} content grid with a {gh}x{gw} exemplar grid (equal 64- or "
-                         "128-wide grids, positions a multiple of 256)")
+    _box3_fused_shapes(name, "nll_box3", B, C, fh, fw, gh, gw)
     inv_t = 1.0 / temperature
     th, ph = _raw(theta_raw), _raw(phi_raw)      # the fp32 projections the pair unit reads (K0 with autograd; cached by the handle)
     # T and the statistics as correspondence_match makes them (the lse vectors are its readout's bit for bit), with autograd
-    lazy = isinstance(theta_raw, ops.LazyProj1x1) and ops.PROJ_BWD_FUSED
-    boxed = _BoxedCorr(theta_raw if lazy else th, phi_raw if lazy else ph, inv_t, share_sink=True)      # the lse passes share one G
+    boxed = _boxed(theta_raw, phi_raw, inv_t, grad=True)      # the lse passes share one G
     (mu, a), (nu, b) = boxed.stats()
     tgt = target.reshape(B, N)
     row_lse = boxed.lse(True)

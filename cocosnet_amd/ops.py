@@ -3375,6 +3375,37 @@ class Box3GradSink:
         self.gmax = None
         self.t_dead = None
 
+    @staticmethod
+    def begin(sink, needs_t: bool, numel: int, device, flags: int):
+        """Before a pass's backward kernel (_Box3SoftmaxWarp's, _Box3Lse's) -> (g, g_ret, gmax, flags): the buffer the kernel writes G
+        into, what the node returns for T (None on an accumulating pass and when T needs no gradient), a fresh zero max|G| cell and
+        the flag word, with COCOS_BOX3_G_ACCUMULATE on a pass that adds.  `sink`: the pass's Box3GradSink or None."""
+        if not needs_t:
+            sink = None          # nobody differentiates T through this pass (autograd.grad(..., inputs=[v])): its G is scratch and must
+                                 # not become — or be added into — the shared buffer (ADVICE r4)
+        gmax = _zero_cell(device)
+        if sink is not None and sink.buf is not None:      # another pass over this T has written its G: add ours to it
+            sink.gmax = gmax                               # ... and max|G| becomes that of the sum (a fresh zero cell)
+            return sink.buf, None, gmax, flags | _C["COCOS_BOX3_G_ACCUMULATE"]
+        g = torch.empty(numel, device=device, dtype=torch.float32)
+        if sink is not None:
+            sink.buf, sink.gmax = g, gmax
+            # the buffer belongs to THIS backward: whatever happens to T's node (not reached, an exception on the way), the
+            # engine drops it when the pass ends, so a later backward over a retained graph starts a new G
+            torch.autograd.Variable._execution_engine.queue_callback(sink.reset)
+        return g, (g if needs_t else None), gmax, flags
+
+    @staticmethod
+    def end(sink, needs_t: bool, t, g, gmax, flags: int):
+        """After that kernel: what autograd and the max|x| cache cannot see of a write through raw pointers"""
+        if flags & _C["COCOS_BOX3_G_ACCUMULATE"]:
+            # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand, so that whatever
+            # was derived from the buffer as it was (the first pass's max|G| cell among them) is void
+            torch.autograd.graph.increment_version(g)
+        _remember_amax(g, gmax)      # (an accumulating pass replaces the cell remembered for the shared buffer)
+        if sink is not None and needs_t and t.numel() * 4 >= BOX3_ALIAS_T_BYTES:
+            sink.t_dead = t          # (only when T's node will take the storage over: the reference keeps T alive until then)
+
 
 def box3_corr_xbox(q_raw, k_raw, sink: Box3GradSink | None = None, raw_planes: Box3RawPlanes | None = None):
     """x-direction diagonal box filter of the K = 256 correlation of two raw [B,256,h,w] feature maps (64- or 128-wide grid),
@@ -3422,22 +3453,8 @@ class _Box3SoftmaxWarp(torch.autograd.Function):
         d_pre = _rowdot_cached(dout, out) if BWD_D_PRECOMPUTED else None
         (gph, gpl, gs), (vph, vpl, v_scale) = _split_pair_transposed(dout, g_amax, v, ctx.v_amax, cvp)
         f32 = dict(device=v.device, dtype=torch.float32)
-        sink, flags = ctx.sink, (_C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
-        if not ctx.needs_input_grad[0]:
-            sink = None          # nobody differentiates T through this pass (autograd.grad(..., inputs=[v])): its G is scratch and must
-                                 # not become — or be added into — the shared buffer
-        if sink is not None and sink.buf is not None:      # another pass over this T has written its G: add ours to it
-            g, g_ret = sink.buf, None
-            gmax = sink.gmax = _zero_cell(v.device)        # ... and max|G| becomes that of the sum (a fresh zero cell)
-            flags |= _C["COCOS_BOX3_G_ACCUMULATE"]
-        else:
-            g = g_ret = torch.empty(B * N * N, **f32)
-            gmax = _zero_cell(v.device)
-            if sink is not None:
-                sink.buf, sink.gmax = g, gmax
-                # the buffer belongs to THIS backward: whatever happens to T's node (not reached, an exception on the way), the
-                # engine drops it when the pass ends, so a later backward over a retained graph starts a new G
-                torch.autograd.Variable._execution_engine.queue_callback(sink.reset)
+        needs_t = ctx.needs_input_grad[0]
+        g, g_ret, gmax, flags = Box3GradSink.begin(ctx.sink, needs_t, B * N * N, v.device, _C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
         dmu, da, dnu, db = (torch.empty((B, N), **f32) for _ in range(4))
         colpart = torch.empty(_lib.load().cocos_box3_softmax_warp_bwd_colpart_bytes(B, N, N) // 4, **f32)
         need_v = ctx.needs_input_grad[5]
@@ -3450,13 +3467,7 @@ class _Box3SoftmaxWarp(torch.autograd.Function):
               v_scale.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), g.data_ptr(), dmu.data_ptr(),
               da.data_ptr(), dnu.data_ptr(), db.data_ptr(), colpart.data_ptr(), gmax.data_ptr(), _ptr(psh), _ptr(psl),
               _ptr(ctx.v_lomask), B, N, N, Cv, cvp, h, w, kc, scale, _ptr(d_pre), flags, _stream())
-        if flags & _C["COCOS_BOX3_G_ACCUMULATE"]:
-            # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand, so that whatever
-            # was derived from the buffer as it was (the first pass's max|G| cell among them) is void
-            torch.autograd.graph.increment_version(g)
-        _remember_amax(g, gmax)      # (an accumulating pass replaces the cell remembered for the shared buffer)
-        if sink is not None and t.numel() * 4 >= BOX3_ALIAS_T_BYTES:
-            sink.t_dead = t          # (only when T's node will take the storage over: the reference keeps T alive until then)
+        Box3GradSink.end(ctx.sink, needs_t, t, g, gmax, flags)
         dv = None
         if need_v:
             gch, gcl, _ = split_f16(dout, False, amax=g_amax)
@@ -3483,23 +3494,60 @@ def box3_match(t, mu, a, nu, b, h, w, k_unfolded, scale, transposed: bool = Fals
     z[p,q] = scale * a_p b_q (ybox(T)[p,q] - k mu_p nu_q), with T from box3_corr_xbox — that pass without its value tensor (K37;
     forward only: the inputs are detached and no autograd node is made).  `transposed` as for box3_softmax_warp.  Shapes outside
     cocos_box3_fused_supported raise: materialise the logits and use row_argmax_lse."""
-    for x, name in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
-        if not x.is_cuda:
-            raise _lib.CocosHipError(f"box3_match: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
     with torch.no_grad():
-        t, mu, a, nu, b = (_chk(x.detach(), f"box3_match: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
+        operands, _ = _box3_readout_gate("box3_match", t, mu, a, nu, b, h, w)
+        return _box3_readout_launch("box3_match", "cocos_box3_match_f16x3", operands, (), h, w, k_unfolded, scale, 0, transposed)
+
+
+def _box3_readout_gate(name, t, mu, a, nu, b, h, w, *, typed=None, own=None, detach: bool = True, f16x3: bool = False):
+    """The one gate of the operands of a T readout (box3_match, box3_topk, box3_topk_biased, box3_topk_labelled, box3_sinkhorn,
+    box3_lse) -> ((t, mu, a, nu, b) contiguous fp32, detached unless `detach` is False; what `own` returned).  Refusals in this order;
+    what the ops differ in is an argument:
+      `typed` "tensor" (K54, K55): TypeError for a non-tensor, then ValueError unless mu is [B,N];
+              "float32" (K53): TypeError unless the five are float32 tensors, then mu and the shapes (h, w integers) at once;
+      `own(B, N)`: the op's own argument errors (a bias, labels, k, a scale), which come before any device is looked at -> the
+              tensors the launch takes besides the five, checked (the bias; the two label tables);
+      CocosHipError for a tensor off the device, TypeError for another dtype, ValueError for mu and the shapes;
+      `f16x3`: CocosHipError under COCOS_PRECISION=fp32."""
+    operands = ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b"))
+
+    def shapes():
         if mu.dim() != 2:
-            raise ValueError("box3_match: mu is [B,N]")
+            raise ValueError(f"{name}: mu is [B,N]")
         B, N = mu.shape
         if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
-            raise ValueError("box3_match: shape mismatch")
-        idx = torch.empty((B, N), device=t.device, dtype=torch.int32)
-        mx = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        _call("box3_match", "cocos_box3_match_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
-              idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale),
-              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
-    return idx, mx, lse
+            raise ValueError(f"{name}: shape mismatch")
+
+    if typed is not None:
+        for x, what in operands:
+            if not torch.is_tensor(x):
+                raise TypeError(f"{name}: {what}: expected a tensor, got {type(x).__name__}")
+            if typed == "float32" and x.dtype != torch.float32:
+                raise TypeError(f"{name}: {what}: expected float32, got {x.dtype}")
+        if mu.dim() != 2:
+            raise ValueError(f"{name}: mu is [B,N]")
+        if typed == "float32":
+            if not (_is_int(h) and _is_int(w)):
+                raise ValueError(f"{name}: shape mismatch")
+            shapes()
+    extra = own(*mu.shape) if own is not None else ()
+    _gate(name, operands, False)
+    t, mu, a, nu, b = (_chk(x.detach() if detach else x, f"{name}: {what}") for x, what in operands)
+    if typed != "float32":
+        shapes()
+    _gate(name, (), f16x3)
+    return (t, mu, a, nu, b), extra
+
+
+def _box3_readout_launch(tag, entry, operands, extra, h, w, k_unfolded, scale, k: int, transposed: bool):
+    """One launch of a readout entry point of T — cocos_box3_match_f16x3 (k = 0: outputs [B,N], no k argument), cocos_box3_topk_f16x3,
+    cocos_box3_topk_bias_f16x3 or cocos_box3_topk_labels_f16x3 (`extra`: the bias, or the two label tables) — on `operands` = (t, mu, a, nu, b),
+    checked, contiguous fp32 tensors -> (idx int32 [B,N,k], val [B,N,k], lse [B,N]).  `tag`: the KernelTimer label."""
+    B, N = operands[1].shape
+    idx, val, lse = _readout_outputs((B, N), k, operands[0].device)
+    _call(tag, entry, *(x.data_ptr() for x in operands), *(x.data_ptr() for x in extra), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale), *((k,) if k else ()),
+          _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+    return idx, val, lse
 
 
 def box3_topk_ok(k: int) -> bool:
@@ -3515,61 +3563,13 @@ def box3_topk(t, mu, a, nu, b, h, w, k_unfolded, scale, k: int, transposed: bool
     non-increasing, and two unequal tt that round to the same val keep their tt order.  Rank 0 and lse are box3_match's outputs bit
     for bit.  1 <= k <= MATCH_TOPK_MAX, k <= N (ValueError); a k that box3_topk_ok refuses and the shapes box3_match refuses
     raise: materialise the logits and use row_topk_lse."""
-    for x, name in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
-        if not x.is_cuda:
-            raise _lib.CocosHipError(f"box3_topk: {name}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
     with torch.no_grad():
-        t, mu, a, nu, b = (_chk(x.detach(), f"box3_topk: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
-        if mu.dim() != 2:
-            raise ValueError("box3_topk: mu is [B,N]")
-        B, N = mu.shape
-        if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
-            raise ValueError("box3_topk: shape mismatch")
-        k = _check_topk("box3_topk", k, N)
-        idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
-        val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
-        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        _call("box3_topk", "cocos_box3_topk_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
-              idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale), k,
-              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
-    return idx, val, lse
+        operands, _ = _box3_readout_gate("box3_topk", t, mu, a, nu, b, h, w)
+        k = _check_topk("box3_topk", k, mu.shape[1])
+        return _box3_readout_launch("box3_topk", "cocos_box3_topk_f16x3", operands, (), h, w, k_unfolded, scale, k, transposed)
 
 
 # K54  transport on the match_kernel-3 route: the biased readout of T and the Sinkhorn iteration on top of it
-def _box3_topk_bias_launch(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k: int, transposed: bool, name: str = "box3_topk_biased"):
-    """One launch of cocos_box3_topk_bias_f16x3 on contiguous fp32 device tensors (already checked) -> (idx [B,N,k], val, lse)"""
-    B, N = mu.shape
-    idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
-    val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
-    lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
-    _call(name, "cocos_box3_topk_bias_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(), k_bias.data_ptr(),
-          idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(k_unfolded), float(scale), k,
-          _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
-    return idx, val, lse
-
-
-def _box3_readout_tensors(name, t, mu, a, nu, b):
-    """TypeError unless the five operands are tensors, ValueError unless mu is [B,N]: the first refusal of both K54 ops"""
-    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
-        if not torch.is_tensor(x):
-            raise TypeError(f"{name}: {what}: expected a tensor, got {type(x).__name__}")
-    if mu.dim() != 2:
-        raise ValueError(f"{name}: mu is [B,N]")
-
-
-def _box3_readout_args(name, t, mu, a, nu, b, h, w):
-    """The refusals box3_topk_biased and box3_sinkhorn share, after their own argument errors: device, then shapes -> the five tensors
-    detached, contiguous fp32"""
-    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
-        if not x.is_cuda:
-            raise _lib.CocosHipError(f"{name}: {what}: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
-    t, mu, a, nu, b = (_chk(x.detach(), f"{name}: {n}") for x, n in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")))
-    B, N = mu.shape
-    if N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
-        raise ValueError(f"{name}: shape mismatch")
-    return t, mu, a, nu, b
-
-
 def box3_topk_biased(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k: int, transposed: bool = False):
     """box3_topk over z'[p,q] = z[p,q] + k_bias[b,q] (K54; forward only: the inputs are detached and no autograd node is made) ->
     (idx int32 [B,N,k], val [B,N,k] = z', lse [B,N] = log sum_q exp z'[p,q]).  k_bias [B,N] float32: finite values of any sign, or -inf
@@ -3579,17 +3579,22 @@ def box3_topk_biased(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k: int, t
     a bias of another dtype (TypeError), of another shape or one that requires a gradient, a bad k (ValueError); tensors off the
     device; the shapes box3_topk refuses."""
     name = "box3_topk_biased"
-    _box3_readout_tensors(name, t, mu, a, nu, b)
-    B, N = mu.shape
-    k_bias = _bias_table(name, k_bias, (B, N))
-    k = _check_topk(name, k, N)
-    if not box3_topk_ok(k):      # (cocos_box3_topk_max_k owns the limit of both entries: every BIAS instantiation ships)
-        raise ValueError(f"{name}: k={k}: no instantiation serves it (box3_topk_ok)")
-    if not k_bias.is_cuda:
-        raise _lib.CocosHipError(f"{name}: k_bias: expected a CUDA/HIP tensor; the correspondence hot path has no CPU fallback")
+
+    def own(B, N):
+        bias = _bias_table(name, k_bias, (B, N))
+        _box3_served_k(name, k, N)
+        _gate(name, ((bias, "k_bias"),), False)
+        return (bias,)
     with torch.no_grad():
-        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
-        return _box3_topk_bias_launch(t, mu, a, nu, b, k_bias, h, w, k_unfolded, scale, k, transposed)
+        operands, bias = _box3_readout_gate(name, t, mu, a, nu, b, h, w, typed="tensor", own=own)
+        return _box3_readout_launch(name, "cocos_box3_topk_bias_f16x3", operands, bias, h, w, k_unfolded, scale, k, transposed)
+
+
+def _box3_served_k(name, k, N):
+    """ValueError unless k is a candidate count (_check_topk) that an instantiation serves: cocos_box3_topk_max_k owns the limit of all
+    three top-k entries, and every BIAS and LABELS instantiation up to it ships"""
+    if not box3_topk_ok(_check_topk(name, k, N)):
+        raise ValueError(f"{name}: k={k}: no instantiation serves it (box3_topk_ok)")
 
 
 def box3_sinkhorn(t, mu, a, nu, b, h, w, k_unfolded, scale, iters: int, tau: float = 1.0):
@@ -3601,7 +3606,6 @@ def box3_sinkhorn(t, mu, a, nu, b, h, w, k_unfolded, scale, iters: int, tau: flo
     (nu, b) exchanged and f as the key bias; the affine update runs in torch on [B,N] vectors.  2 iters + 1 launches, no second
     correlation GEMM and nothing N x N besides T.  iters an integer in 1..SINKHORN_MAX_ITERS, 0 < tau <= 1 (ValueError); then the
     refusals of box3_match."""
-    name = "box3_sinkhorn"
     f, g, _, _, row_lse = _box3_sinkhorn_readout(t, mu, a, nu, b, h, w, k_unfolded, scale, iters, tau)
     return f, g, row_lse
 
@@ -3611,13 +3615,14 @@ def _box3_sinkhorn_readout(t, mu, a, nu, b, h, w, k_unfolded, scale, iters, tau)
     z + g is that launch, so a caller that wants the best match per row pays nothing for it"""
     name = "box3_sinkhorn"
     iters, tau = _sinkhorn_args(name, iters, tau)
-    _box3_readout_tensors(name, t, mu, a, nu, b)
     with torch.no_grad():
-        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
+        (t, mu, a, nu, b), _ = _box3_readout_gate(name, t, mu, a, nu, b, h, w, typed="tensor")
         B, N = mu.shape
         log_m = -math.log(N)
-        rows = lambda g: _box3_topk_bias_launch(t, mu, a, nu, b, g, h, w, k_unfolded, scale, 1, False, name)
-        cols = lambda f: _box3_topk_bias_launch(t, nu, b, mu, a, f, h, w, k_unfolded, scale, 1, True, name)[2]
+        launch = lambda operands, bias, transposed: _box3_readout_launch(name, "cocos_box3_topk_bias_f16x3", operands, (bias,), h, w,
+                                                                         k_unfolded, scale, 1, transposed)
+        rows = lambda g: launch((t, mu, a, nu, b), g, False)
+        cols = lambda f: launch((t, nu, b, mu, a), f, True)[2]
         g = torch.zeros((B, N), device=t.device, dtype=torch.float32)
         for _ in range(iters):
             f = tau * (log_m - rows(g)[2])
@@ -3638,24 +3643,15 @@ def box3_topk_labelled(t, mu, a, nu, b, q_label, k_label, h, w, k_unfolded, scal
     that box3_topk_ok refuses (ValueError); tensors off the device; the shapes box3_topk refuses; COCOS_PRECISION=fp32.  There is no
     materialised fall-back."""
     name = "box3_topk_labelled"
-    _box3_readout_tensors(name, t, mu, a, nu, b)
-    B, N = mu.shape
-    q_label = _int_table(name, "q_label", q_label, (B, N))
-    k_label = _int_table(name, "k_label", k_label, (B, N))
-    k = _check_topk(name, k, N)
-    if not box3_topk_ok(k):      # (every LABELS instantiation up to cocos_box3_topk_max_k ships: DESIGN.md 3.41)
-        raise ValueError(f"{name}: k={k}: no instantiation serves it (box3_topk_ok)")
-    _gate(name, ((q_label, "q_label"), (k_label, "k_label")), False)
+
+    def own(B, N):
+        labels = _int_table(name, "q_label", q_label, (B, N)), _int_table(name, "k_label", k_label, (B, N))
+        _box3_served_k(name, k, N)
+        _gate(name, ((labels[0], "q_label"), (labels[1], "k_label")), False)
+        return labels
     with torch.no_grad():
-        t, mu, a, nu, b = _box3_readout_args(name, t, mu, a, nu, b, h, w)
-        _gate(name, (), True)
-        idx = torch.empty((B, N, k), device=t.device, dtype=torch.int32)
-        val = torch.empty((B, N, k), device=t.device, dtype=torch.float32)
-        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        _call(name, "cocos_box3_topk_labels_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
-              q_label.data_ptr(), k_label.data_ptr(), idx.data_ptr(), val.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w),
-              float(k_unfolded), float(scale), k, _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
-    return idx, val, lse
+        operands, labels = _box3_readout_gate(name, t, mu, a, nu, b, h, w, typed="tensor", own=own, f16x3=True)
+        return _box3_readout_launch(name, "cocos_box3_topk_labels_f16x3", operands, labels, h, w, k_unfolded, scale, k, transposed)
 
 
 class _Box3Lse(torch.autograd.Function):
@@ -3666,13 +3662,7 @@ class _Box3Lse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, mu, a, nu, b, h: int, w: int, kc: float, scale: float, transposed: bool = False, sink=None):
         ctx.transposed, ctx.sink = bool(transposed), sink
-        B, N = mu.shape
-        idx = torch.empty((B, N), device=t.device, dtype=torch.int32)
-        mx = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        lse = torch.empty((B, N), device=t.device, dtype=torch.float32)
-        _call("box3_match", "cocos_box3_match_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
-              idx.data_ptr(), mx.data_ptr(), lse.data_ptr(), B, N, N, int(h), int(w), float(kc), float(scale),
-              _C["COCOS_BOX3_T_TRANSPOSED"] if transposed else 0, _stream())
+        lse = _box3_readout_launch("box3_match", "cocos_box3_match_f16x3", (t, mu, a, nu, b), (), h, w, kc, scale, 0, transposed)[2]
         ctx.save_for_backward(t, mu, a, nu, b, lse)
         ctx.cfg = (int(h), int(w), float(kc), float(scale))
         return lse
@@ -3684,34 +3674,14 @@ class _Box3Lse(torch.autograd.Function):
         g_lse = _chk(g_lse, "box3_lse: g_lse")
         B, N = mu.shape
         f32 = dict(device=t.device, dtype=torch.float32)
-        sink, flags = ctx.sink, (_C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
-        if not ctx.needs_input_grad[0]:
-            sink = None          # nobody differentiates T through this pass: its G is scratch and must not become — or be added
-                                 # into — the shared buffer (as _Box3SoftmaxWarp)
-        if sink is not None and sink.buf is not None:      # another pass over this T has written its G: add ours to it
-            g, g_ret = sink.buf, None
-            gmax = sink.gmax = _zero_cell(t.device)        # ... and max|G| becomes that of the sum (a fresh cell)
-            flags |= _C["COCOS_BOX3_G_ACCUMULATE"]
-        else:
-            g = g_ret = torch.empty(B * N * N, **f32)
-            gmax = _zero_cell(t.device)
-            if sink is not None:
-                sink.buf, sink.gmax = g, gmax
-                # the buffer belongs to THIS backward (see _Box3SoftmaxWarp): a later backward over a retained graph starts a new G
-                torch.autograd.Variable._execution_engine.queue_callback(sink.reset)
+        needs_t = ctx.needs_input_grad[0]
+        g, g_ret, gmax, flags = Box3GradSink.begin(ctx.sink, needs_t, B * N * N, t.device, _C["COCOS_BOX3_T_TRANSPOSED"] if ctx.transposed else 0)
         dmu, da, dnu, db = (torch.empty((B, N), **f32) for _ in range(4))
         colpart = torch.empty(_lib.load().cocos_box3_lse_bwd_colpart_bytes(B, N, N) // 4, **f32)
         _call("box3_lse_bwd", "cocos_box3_lse_bwd_f16x3", t.data_ptr(), mu.data_ptr(), a.data_ptr(), nu.data_ptr(), b.data_ptr(),
               lse.data_ptr(), g_lse.data_ptr(), g.data_ptr(), dmu.data_ptr(), da.data_ptr(), dnu.data_ptr(), db.data_ptr(),
               colpart.data_ptr(), gmax.data_ptr(), B, N, N, h, w, kc, scale, flags, _stream())
-        if flags & _C["COCOS_BOX3_G_ACCUMULATE"]:
-            # the kernel added into another pass's buffer through raw pointers: the version counter follows by hand
-            torch.autograd.graph.increment_version(g)
-        _remember_amax(g, gmax)      # (an accumulating pass replaces the cell remembered for the shared buffer)
-        if sink is not None and t.numel() * 4 >= BOX3_ALIAS_T_BYTES:
-            sink.t_dead = t          # (only when T's node will take the storage over)
-        if not ctx.needs_input_grad[0]:
-            g_ret = None
+        Box3GradSink.end(ctx.sink, needs_t, t, g, gmax, flags)
         return g_ret, dmu, da, dnu, db, None, None, None, None, None, None
 
 
@@ -3723,21 +3693,15 @@ def box3_lse(t, mu, a, nu, b, h, w, k_unfolded, scale, transposed: bool = False,
     box adjoint and one pair of GEMMs.  T is saved for the backward and G is allocated in it: two HWxHW tensors, the dense route's
     budget.  CPU tensors raise CocosHipError, the fp32 flavour too; shapes outside cocos_box3_fused_supported raise ValueError."""
     name = "box3_lse"
-    for x, what in ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")):
-        if not torch.is_tensor(x) or x.dtype != torch.float32:
-            raise TypeError(f"{name}: {what} must be a float32 tensor")
-    if mu.dim() != 2:
-        raise ValueError(f"{name}: mu is [B,N]")
-    B, N = mu.shape
-    if not (_is_int(h) and _is_int(w)) or N != h * w or t.numel() != B * N * N or any(x.shape != (B, N) for x in (a, nu, b)):
-        raise ValueError(f"{name}: shape mismatch")
-    if not scale > 0:
-        raise ValueError(f"{name}: scale={scale!r}: expected a positive number")
-    _gate(name, ((t, "t"), (mu, "mu"), (a, "a"), (nu, "nu"), (b, "b")), True)
-    if not _lib.load().cocos_box3_fused_supported(N, N, 1, h, w):
+
+    def own(B, N):
+        if not scale > 0:
+            raise ValueError(f"{name}: scale={scale!r}: expected a positive number")
+        return ()
+    operands, _ = _box3_readout_gate(name, t, mu, a, nu, b, h, w, typed="float32", own=own, detach=False, f16x3=True)
+    if not _lib.load().cocos_box3_fused_supported(h * w, h * w, 1, h, w):
         raise ValueError(f"{name}: the fused box route does not take a {h}x{w} grid (64- or 128-wide, positions a multiple of 256)")
-    return _Box3Lse.apply(t.contiguous(), mu.contiguous(), a.contiguous(), nu.contiguous(), b.contiguous(), h, w, float(k_unfolded),
-                          float(scale), transposed, sink)
+    return _Box3Lse.apply(*operands, h, w, float(k_unfolded), float(scale), transposed, sink)
 
 
 # ------------------------------------------------------------------------------------------
