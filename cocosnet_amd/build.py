@@ -70,6 +70,7 @@ HIP_SOURCES = [
     "row_topk_lse.hip",
     "plane_pair.hip",
     "patchmatch_f16x3.hip",
+    "patchmatch_box3.hip",
     "corr_match_mutual_f16x3.hip",
     "corr_lse_bwd_f16x3.hip",
     "corr_topk_bias_f16x3.hip",

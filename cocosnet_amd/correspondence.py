@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from torch.nn import init
 
 from . import inference, ops
-from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_scope, _refine_scope, _restrict_scope,
+from .hot_path import (HotPathConfig, _box3_scope, _flow_scope, _max_dist, _nll_scope, _no_patchmatch_with, _refine_scope, _restrict_scope,
                        _sparse_scope, _sparse_search, _topk_arg, _transport_dict, _transport_scope, _upsample, correspondence_flow, correspondence_flow_box3,
                        correspondence_hot_path, correspondence_match, correspondence_match_box3, correspondence_mutual, correspondence_nll, correspondence_nll_box3,
                        correspondence_sparse, correspondence_sparse_box3,
@@ -531,7 +531,8 @@ class NoVGGCorrespondence(NetworkBase):
                 out["warp_topk"] = ops.gather_blend_patches(ref_img, m.index, weights, fh, fw, self.opt.down)
         return out
 
-    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, transport=None, restrict=None):
+    def sparse_warp_box3(self, ref_img, real_img, seg_map, ref_seg_map, temperature=0.01, *, topk=4, transport=None, restrict=None,
+                         search="dense", search_opts=None):
         """sparse_warp on the reference's default route, match_kernel 3 (K51, hot_path.correspondence_sparse_box3): per content position
         the `topk` best exemplar positions are selected without gradient, as match(topk=topk) selects them, and a softmax over those k
         box logits alone blends the pooled exemplar (and, under --warp_mask_losstype direct, the exemplar's labels), with gradients to
@@ -542,12 +543,16 @@ class NoVGGCorrespondence(NetworkBase):
         dict(iters=, tau=) — the candidates are the top-k of the box transport plan's rows and the blend is the biased softmax over
         them, with the Sinkhorn potentials detached; the result gains potential_k and match_mass.  `restrict` (K55; None changes nothing):
         "label" or a pair of integer label tensors as for match_box3 — the candidates are the restricted top-k; the result gains
-        match_restricted; restrict together with transport raises ValueError."""
+        match_restricted; restrict together with transport raises ValueError.  `search` / `search_opts` (K57; "dense" changes nothing):
+        "patchmatch" selects the candidates with ops.patchmatch_topk_box3 — no HWxHW tensor of the full grid, any grid sizes — as
+        hot_path.correspondence_sparse_box3 takes them; together with restrict or transport it raises a ValueError naming search."""
         cfg = HotPathConfig.from_opt(self.opt, down=self.opt.down)
+        _no_patchmatch_with("sparse_warp_box3", search, restrict, transport)
         if restrict is not None:      # (first: every scope message of a restricted call names restrict)
             _topk_arg("sparse_warp_box3", topk)
             _box3_scope("sparse_warp_box3", "restrict_box3", cfg, False, self.inter_channels, restrict=restrict, transport=transport)
         _box3_scope("sparse_warp_box3", "sparse_box3", cfg, False, self.inter_channels, topk=topk)      # refused before the network runs
+        _sparse_search(search, search_opts, "sparse_warp_box3")
         if transport is not None:
             _transport_dict("sparse_warp_box3", transport)
         if ref_img is None or ref_seg_map is None:
@@ -557,6 +562,8 @@ class NoVGGCorrespondence(NetworkBase):
         kw = {} if transport is None else {"transport": transport}
         if restrict is not None:
             kw["restrict"] = restrict
+        if search != "dense":
+            kw.update(search=search, search_opts=search_opts)
         coor_out.update(correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg, temperature, topk, **kw))
         return coor_out
 

@@ -8,99 +8,17 @@
 //                 rho = max(1, R >> s)
 // One launch is one JACOBI iteration: idx_in is read, idx_out (another buffer) is written, no atomics, no communication between
 // workgroups — the result is a pure function of the arguments.  Everything that chooses a candidate is 32-bit integer arithmetic
-// (pm_hash below), so a host restatement reproduces every pool exactly (tests/patchmatch_case.py).
+// (patchmatch_pool.h, shared with the box-logit step of patchmatch_box3.hip), so a host restatement reproduces every pool exactly
+// (tests/patchmatch_case.py).
 //
 // A score is K42's logit of the pair, bit for bit (sparse_row.h): one wave per query, 512-byte row loads, four FMAs per lane, the xor
 // butterfly, one multiply by inv_temperature / operand_scale^2.  The candidates of one source (the own list, one neighbour's list, one
 // radius of the search) are scored together: their K row loads are issued before the first butterfly.  Every lane holds the same
 // score bits, so the candidate list is wave-uniform; it is kept in the order of topk_list.h (score descending, equal bits: lower key
 // first) by a general insert that first tests membership — the same key may reach the pool from several sources.
-#include "sparse_row.h"
-#include "topk_list.h"
+#include "patchmatch_pool.h"
 
 namespace cocos {
-
-constexpr int PM_WAVES = 4;              // queries per workgroup, one per wave
-constexpr int PM_THREADS = PM_WAVES * kWave;
-
-__host__ __device__ __forceinline__ unsigned pm_fmix32(unsigned h) {      // the 32-bit murmur3 finaliser
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-// the hash of (seed, iteration, query row b Nq + i, word): word = (r << 8) | (s << 1) | axis for the search, (r << 8) | 0xff for
-// the random initialisation
-__host__ __device__ __forceinline__ unsigned pm_hash(int seed, int iteration, int row, unsigned word) {
-    unsigned h = pm_fmix32((unsigned)seed ^ 0x9e3779b9u);
-    h = pm_fmix32(h ^ (unsigned)iteration);
-    h = pm_fmix32(h ^ (unsigned)row);
-    return pm_fmix32(h ^ word);
-}
-
-// The candidate list of K43: K (score, key) pairs in the order of topk_before, empty slots (-inf, -1).  Unlike TopkList::push_ascending
-// the keys arrive in ANY order and may repeat: a key already in the list is refused, the place of a new one is found by topk_before
-// itself.  A NaN score never enters.  All loops are unrolled: the arrays stay in registers.
-template <int K>
-struct PoolList {
-    float v[K];
-    int i[K];
-
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int p = 0; p < K; ++p) { v[p] = -INFINITY; i[p] = -1; }
-    }
-
-    __device__ __forceinline__ void insert(float x, int j) {      // j >= 0
-        bool fresh = true;
-#pragma unroll
-        for (int p = 0; p < K; ++p) fresh = fresh && i[p] != j;
-#pragma unroll
-        for (int p = K - 1; p >= 1; --p) {
-            const bool up = fresh && topk_before(x, j, v[p - 1], i[p - 1]), here = fresh && topk_before(x, j, v[p], i[p]);
-            v[p] = up ? v[p - 1] : (here ? x : v[p]);
-            i[p] = up ? i[p - 1] : (here ? j : i[p]);
-        }
-        const bool first = fresh && topk_before(x, j, v[0], i[0]);
-        v[0] = first ? x : v[0];
-        i[0] = first ? j : i[0];
-    }
-};
-
-// the k own candidates of query row `row` when there is no idx_in: hashed key positions, made pairwise distinct by linear probing
-// (k <= Nk: the probe ends)
-template <int K>
-__device__ __forceinline__ void pm_init_list(int (&own)[K], int row, int k, int Nk, int seed, int iteration) {
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-        own[r] = 0;
-        if (r < k) {
-            int p = (int)(pm_hash(seed, iteration, row, ((unsigned)r << 8) | 0xffu) % (unsigned)Nk);
-            for (int tries = 0; tries < K; ++tries) {      // at most r earlier entries can collide, each at most once
-                bool taken = false;
-#pragma unroll
-                for (int e = 0; e < K; ++e) taken = taken || (e < r && own[e] == p);
-                if (!taken) break;
-                p = p + 1 == Nk ? 0 : p + 1;
-            }
-            own[r] = p;
-        }
-    }
-}
-
-// the list of query row `row`: idx_in clamped into the key grid, or the random initialisation
-template <int K>
-__device__ __forceinline__ void pm_list(int (&out)[K], const int* __restrict__ idx_in, int row, int k, int Nk, int seed, int iteration) {
-    if (idx_in) {
-#pragma unroll
-        for (int r = 0; r < K; ++r) out[r] = r < k ? clamp_key(idx_in[(long long)row * k + r], Nk) : 0;
-    } else {
-        pm_init_list<K>(out, row, k, Nk, seed, iteration);
-    }
-}
 
 template <int K>
 __global__ __launch_bounds__(PM_THREADS) void patchmatch_step_kernel(const _Float16* __restrict__ qh, const _Float16* __restrict__ ql,
@@ -124,42 +42,10 @@ __global__ __launch_bounds__(PM_THREADS) void patchmatch_step_kernel(const _Floa
     PoolList<K> best;
     best.clear();
 
-    // sources: 0 the own list, 1 .. 4 the neighbours (y - d, x), (y + d, x), (y, x - d), (y, x + d), 5 + s the search at radius s
-    for (int src = 0; src < 5 + S; ++src) {
+    const PmStep step{hq, wq, hk, wk, Nq, Nk, k, stride, S, R, seed, iteration};
+    for (int src = 0; src < pm_sources(step); ++src) {
         int cand[K];      // key index, or -1: no candidate
-        if (src == 0) {
-#pragma unroll
-            for (int r = 0; r < K; ++r) cand[r] = r < k ? own[r] : -1;
-        } else if (src < 5) {
-            const int dy = src == 1 ? -stride : (src == 2 ? stride : 0), dx = src == 3 ? -stride : (src == 4 ? stride : 0);
-            const int ny = y + dy, nx = x + dx;
-#pragma unroll
-            for (int r = 0; r < K; ++r) cand[r] = -1;
-            if (ny >= 0 && ny < hq && nx >= 0 && nx < wq) {
-                int theirs[K];
-                pm_list<K>(theirs, idx_in, b * Nq + ny * wq + nx, k, Nk, seed, iteration);
-#pragma unroll
-                for (int r = 0; r < K; ++r) {
-                    const int ky = theirs[r] / wk - dy, kx = theirs[r] % wk - dx;
-                    if (r < k && ky >= 0 && ky < hk && kx >= 0 && kx < wk) cand[r] = ky * wk + kx;
-                }
-            }
-        } else {
-            const int s = src - 5;
-            const int rho = max(1, R >> s);
-            const unsigned span = 2u * (unsigned)rho + 1u;
-#pragma unroll
-            for (int r = 0; r < K; ++r) {
-                cand[r] = -1;
-                if (r < k) {
-                    const unsigned word = ((unsigned)r << 8) | ((unsigned)s << 1);
-                    const int oy = (int)(pm_hash(seed, iteration, row, word) % span) - rho;
-                    const int ox = (int)(pm_hash(seed, iteration, row, word | 1u) % span) - rho;
-                    const int ky = min(max(own[r] / wk + oy, 0), hk - 1), kx = min(max(own[r] % wk + ox, 0), wk - 1);
-                    cand[r] = ky * wk + kx;
-                }
-            }
-        }
+        pm_source<K>(cand, src, own, idx_in, row, b, y, x, step);
         // the K rows of this source first, then their reductions: K loads in flight instead of one load -> butterfly chain per key
         f32x4 kv[K];
 #pragma unroll
@@ -218,14 +104,8 @@ extern "C" int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const
     COCOS_REQUIRE(B >= 1 && hq >= 1 && wq >= 1 && hk >= 1 && wk >= 1, COCOS_ERR_UNSUPPORTED, "%s: empty grid: B=%d query %dx%d key %dx%d",
                   name, B, hq, wq, hk, wk);
     const long long Nq = (long long)hq * wq, Nk = (long long)hk * wk;
-    COCOS_REQUIRE(k >= 1 && k <= COCOS_MATCH_TOPK_MAX && k <= Nk, COCOS_ERR_UNSUPPORTED, "%s: k=%d: expected 1 <= k <= min(%d, Nk=%lld)",
-                  name, k, COCOS_MATCH_TOPK_MAX, Nk);
-    COCOS_REQUIRE(stride >= 1 && stride <= (1 << 20), COCOS_ERR_UNSUPPORTED, "%s: stride=%d: expected 1 .. 2^20", name, stride);
-    COCOS_REQUIRE(radii >= 0 && radii <= COCOS_PATCHMATCH_MAX_RADII, COCOS_ERR_UNSUPPORTED, "%s: radii=%d: expected 0 .. %d", name, radii,
-                  COCOS_PATCHMATCH_MAX_RADII);
-    COCOS_REQUIRE(radius0 >= 0 && radius0 <= (1 << 20), COCOS_ERR_UNSUPPORTED, "%s: radius0=%d: expected 0 .. 2^20", name, radius0);
-    COCOS_REQUIRE(B * Nq < 0x7ffffff0ll && B * Nq * k < 0x7fffffffll && B * Nk < 0x7fffffffll, COCOS_ERR_UNSUPPORTED,
-                  "%s: B Nq k = %lld entries / B Nk = %lld keys exceed the 32-bit tables", name, B * Nq * k, B * Nk);
+    if (const int rc = pm_check_schedule(name, k, Nk, stride, radii, radius0)) return rc;
+    if (const int rc = pm_check_tables(name, B, Nq, Nk, k)) return rc;
     for (const void* p : {qh, ql, kh, kl})
         COCOS_REQUIRE(aligned16(p), COCOS_ERR_INVALID, "%s: q/k planes must be 16-byte aligned", name);
     const int rows = (int)(B * Nq);

@@ -1154,10 +1154,9 @@ def _sparse_scope(cfg: HotPathConfig, topk):
     return k
 
 
-def _sparse_search(search, search_opts):
-    """ValueError for a selector correspondence_sparse does not have, or options it does not know -> the PatchMatch schedule (None for
-    the dense scan); checked after _sparse_scope, before any tensor is looked at"""
-    name = "correspondence_sparse"
+def _sparse_search(search, search_opts, name="correspondence_sparse"):
+    """ValueError for a selector correspondence_sparse (`name`: correspondence_sparse_box3) does not have, or options it does not know
+    -> the PatchMatch schedule (None for the dense scan); checked after the route's scope, before any tensor is looked at"""
     if search not in ("dense", "patchmatch"):
         raise ValueError(f"{name}: search={search!r}: expected 'dense' or 'patchmatch'")
     opts = dict(search_opts or {})
@@ -1189,7 +1188,13 @@ def _patchmatch_coarse_init(theta_raw, phi_raw, inv_t, k):
     qc = ops.center_l2norm_planes(pool(theta_raw), 1, planes, want_chan=False)
     kc = ops.center_l2norm_planes(pool(phi_raw), 1, planes, want_chan=False)
     coarse, _, _ = ops.corr_topk(qc, kc, inv_t, k, planes)                          # [B,Nc,k] int32
-    coarse = coarse.to(torch.int64).reshape(B, fh // 2, fw // 2, k)
+    return _patchmatch_expand(coarse.to(torch.int64).reshape(B, fh // 2, fw // 2, k), fh, fw, gw)
+
+
+def _patchmatch_expand(coarse, fh, fw, gw):
+    """coarse [B,fh/2,fw/2,k] int64, keys of the half exemplar grid (width gw / 2) -> [B,fh*fw,k] int64 on the full grids: every
+    coarse candidate (ky, kx) of coarse query (y / 2, x / 2) moved to the fine key (2 ky + y % 2, 2 kx + x % 2)"""
+    B, k = coarse.shape[0], coarse.shape[3]
     coarse = coarse.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)         # the coarse query of every fine query
     dev = coarse.device
     py = (torch.arange(fh, device=dev) % 2).view(1, fh, 1, 1)
@@ -1301,6 +1306,15 @@ def correspondence_sparse(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg
 
 
 # ---- K51 / K52: the trainable routes on match_kernel 3 (the k-sparse warp, the sub-cell flow) -----------------------------------------
+def _no_patchmatch_with(name: str, search, restrict, transport):
+    """ValueError naming search: on the match_kernel-3 route the label mask and the transport bias live in the scan of T, which
+    search="patchmatch" does not make"""
+    if search == "patchmatch" and (restrict is not None or transport is not None):
+        what = "restrict" if restrict is not None else "transport"
+        raise ValueError(f"{name}: search='patchmatch' with {what} is out of scope (not built): {what} selects inside the dense scan of T"
+                         f"{_ROUTE['sparse_box3']}")
+
+
 def _box3_select_and_stats(theta_raw, phi_raw, select):
     """The prologue of the trainable routes -> (th, ph, mu, a, nu, b, what `select` returned).  Lazy operands are projected first, with
     autograd (K0; the handle caches the projection, so this must not happen inside the selection's no_grad block); `select()` — the
@@ -1316,8 +1330,50 @@ def _box3_select_and_stats(theta_raw, phi_raw, select):
     return th, ph, mu, a, nu, b, picked
 
 
+#: the largest materialised matrix the coarse start of search="patchmatch" may build at the half grid, per matrix (the chain builds
+#: two): a condition on the shapes, not a measurement
+PATCHMATCH_BOX3_COARSE_CAP = 256 << 20
+
+
+def _patchmatch_coarse_route_box3(B, C, fh, fw, gh, gw, k):
+    """How search="patchmatch" starts on the match_kernel-3 route, as a pure function of the shapes -> "fused", "materialised" or
+    "random".  The start is correspondence_match(topk=k) on the 2 x 2 average-pooled features, so it needs even sides and k half-grid
+    keys.  "fused": the half grids are equal and pass ops.box3_fused_ok and ops.box3_topk_ok(k) (with ops.MATCH_FUSED) — the readout
+    from one T of the half grid (256x256 -> 128x128, 128x128 -> 64x64).  "materialised": the chain at the half grid stays small,
+    B * Nc * Nkc * 4 bytes <= PATCHMATCH_BOX3_COARSE_CAP (256 MiB) per matrix.  "random" for everything else: an odd side, k above the
+    number of half-grid keys, a half grid that is too large, and unequal grids (the dense box readout, fused or materialised, is
+    built for equal grids: ops.box3_logits filters a square matrix)."""
+    if fh % 2 or fw % 2 or gh % 2 or gw % 2 or (gh, gw) != (fh, fw):
+        return "random"
+    ch, cw = fh // 2, fw // 2
+    Nc = ch * cw
+    if k > Nc:
+        return "random"
+    if ops.MATCH_FUSED and ops.box3_fused_ok(B, C, ch, cw) and ops.box3_topk_ok(k):
+        return "fused"
+    return "materialised" if B * Nc * Nc * 4 <= PATCHMATCH_BOX3_COARSE_CAP else "random"
+
+
+def _patchmatch_coarse_init_box3(theta_raw, phi_raw, cfg, temperature, k):
+    """The starting candidates of the PatchMatch selector on the match_kernel-3 route, [B,N,k] int64, or "random"
+    (_patchmatch_coarse_route_box3 decides from the shapes alone): theta / phi averaged over 2 x 2 cells (torch glue),
+    correspondence_match(topk=k) on the pooled features — K41 on the half grid's T where the fused family takes it, the materialised
+    chain where that stays below 256 MiB per matrix — and every coarse candidate expanded as _patchmatch_coarse_init does.  Runs
+    without gradient; whatever HWxHW tensor of the HALF grid the readout made is gone on return."""
+    B, C, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    if _patchmatch_coarse_route_box3(B, C, fh, fw, gh, gw, k) == "random":
+        return "random"
+    with torch.no_grad():
+        pool = lambda t: F.avg_pool2d(t.detach(), 2)
+        m = correspondence_match(pool(theta_raw), pool(phi_raw), cfg, temperature, topk=k)
+        coarse = m.index.reshape(B, k, fh // 2, fw // 2).permute(0, 2, 3, 1)
+        del m
+        return _patchmatch_expand(coarse, fh, fw, gw)
+
+
 def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map, cfg: HotPathConfig, temperature=0.01, topk=4, *,
-                               exemplar=None, transport=None, restrict=None):
+                               exemplar=None, transport=None, restrict=None, search="dense", search_opts=None):
     """correspondence_sparse on the reference's default route, match_kernel 3 (K51): per content position the `topk` best exemplar
     positions are SELECTED without gradient exactly as correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=topk) selects
     them (that function is called: K41 on the one x-box tensor T where ops.box3_fused_ok and ops.box3_topk_ok(topk) hold, the
@@ -1331,7 +1387,15 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
 
     Scope: match_kernel 3, PONO_C, 256 channels, COCOS_PRECISION=f16x3, plain flag set (no warp_patch / warp_bilinear / cycle terms),
     no prepared exemplar: everything else raises ValueError — there is no fall-back route.  CPU tensors raise CocosHipError.  Not built
-    on this route: search="patchmatch", refine.
+    on this route: refine.
+
+    `search` (K57; "dense", the default, is the route as it was, launch for launch): "patchmatch" finds the k candidates without any
+    HWxHW tensor of the full grid — the K12 statistics are made once (with autograd; the selector reads their detached values, the
+    warp the same tensors), the start is _patchmatch_coarse_init_box3 (the dense readout of the 2 x 2 pooled features, or a random
+    start), then ops.patchmatch_topk_box3 runs the schedule on the box logit of single pairs; the warp and its gradients are the same
+    K51 on those indices.  The 64- / 128-wide grid requirement of the dense selector is dropped: any grids, equal or not.  Its
+    candidates are the best of what it looked at, not of all keys.  `search_opts` overrides entries of
+    ops.PATCHMATCH_DEFAULTS.  search="patchmatch" together with restrict or transport raises a ValueError that names search.
 
     `restrict` (K55; None is the route as it was, launch for launch): "label" or a pair (q_labels [B,h,w], k_labels [B,h,w]) as for
     correspondence_match_box3 — the k candidates are its restricted top-k (the label mask inside the scan of T), the warp and its
@@ -1345,10 +1409,12 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
     K12 statistics only.  It needs the grids the fused box route takes and a topk that ops.box3_topk_ok serves (ValueError); the result
     gains potential_k [B,h,w] and match_mass [B,h,w]."""
     name = "correspondence_sparse_box3"
+    _no_patchmatch_with(name, search, restrict, transport)
     if restrict is not None:      # (first: every scope message of a restricted call names restrict)
         _topk_arg(name, topk)
         _box3_scope(name, "restrict_box3", cfg, False, theta_raw.shape[1], restrict=restrict, transport=transport)
     k = _box3_scope(name, "sparse_box3", cfg, exemplar is not None, theta_raw.shape[1], topk=topk)["topk"]
+    pm = _sparse_search(search, search_opts, name)
     if transport is not None:
         iters, tau = _transport_dict(name, transport)
     _same_kind(name, theta_raw, phi_raw)
@@ -1370,6 +1436,14 @@ def correspondence_sparse_box3(theta_raw, phi_raw, ref_img, seg_map, ref_seg_map
             theta_raw, phi_raw, lambda: _restrict_box3_select(theta_raw, phi_raw, 1.0 / temperature, True, labels, k))
         extra = {"match_restricted": restricted.reshape(B, fh, fw)}
         idx = idx.to(torch.int64).contiguous()
+    elif pm is not None:      # K57: the statistics first (once, with autograd), the selection on their detached values
+        th, ph = _raw(theta_raw), _raw(phi_raw)
+        kc = float(C * 9)
+        operands = [th, ph, *_unfold3_stats(th, kc), *_unfold3_stats(ph, kc)]
+        with torch.no_grad():
+            idx, _ = ops.patchmatch_topk_box3(*operands, 1.0 / temperature, k, _patchmatch_coarse_init_box3(th, ph, cfg, temperature, k),
+                                              pm["strides"], (pm["radii"], pm["radius0"]), pm["seed"])
+            idx = idx.to(torch.int64)
     elif transport is None:
         *operands, m = _box3_select_and_stats(theta_raw, phi_raw, lambda: correspondence_match(theta_raw, phi_raw, cfg, temperature, topk=k))
         with torch.no_grad():

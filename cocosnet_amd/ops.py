@@ -4041,6 +4041,103 @@ def box3_pair_logits(theta_raw, phi_raw, mu, a, nu, b, idx, inv_temperature: flo
     return _Box3PairLogits.apply(*floats, idx.reshape(B, Nq), float(inv_temperature))
 
 
+# K57  PatchMatch candidate search on the match_kernel-3 route: K43's step with K51's box logit as the score
+def _patchmatch_box3_operands(name: str, theta_raw, phi_raw, mu, a, nu, b, k):
+    """the shape checks patchmatch_step_box3 / patchmatch_topk_box3 share -> (B, fh, fw, gh, gw, stats); ValueError before the library
+    is called"""
+    if not (torch.is_tensor(theta_raw) and torch.is_tensor(phi_raw)) or theta_raw.dim() != 4 or phi_raw.dim() != 4:
+        got = tuple(tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in (theta_raw, phi_raw))
+        raise ValueError(f"{name}: expected theta_raw [B,256,fh,fw] and phi_raw [B,256,gh,gw]; got {got[0]}, {got[1]}")
+    B, K, fh, fw = theta_raw.shape
+    gh, gw = phi_raw.shape[2:]
+    if phi_raw.shape[:2] != (B, K) or B < 1 or fh * fw < 1 or gh * gw < 1:
+        raise ValueError(f"{name}: shape mismatch theta_raw{tuple(theta_raw.shape)} phi_raw{tuple(phi_raw.shape)}")
+    if K != FUSED_K:
+        raise ValueError(f"{name}: needs {FUSED_K} channels, got {K}")
+    _check_topk(name, k, gh * gw)
+    return B, fh, fw, gh, gw, _box3_stats(name, B, fh * fw, gh * gw, mu, a, nu, b)
+
+
+def _patchmatch_box3_temperature(name: str, inv_t):
+    if isinstance(inv_t, bool) or not isinstance(inv_t, (int, float)) or not inv_t > 0:
+        raise ValueError(f"{name}: inv_t={inv_t!r}: expected a positive number")
+
+
+def _patchmatch_box3_rows(name: str, theta_raw, phi_raw, stats):
+    """_gate, then the detached float operands -> (th_t [B,Nq,256], ph_t [B,Nk,256], mu, a, nu, b): the position-major rows are made
+    here, ONCE per call of the op (cocos_transpose_f32), not per iteration"""
+    _gate(name, ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + stats, False)
+    th, ph, *st = (_chk(t.detach(), f"{name}: {what}") for t, what in ((theta_raw, "theta_raw"), (phi_raw, "phi_raw")) + stats)
+    B, K = th.shape[:2]
+    return (_transpose(th.reshape(B, K, -1)), _transpose(ph.reshape(B, K, -1)), *st)
+
+
+def _patchmatch_box3_launch(rows6, idx, fh, fw, gh, gw, inv_t, k, stride, radii, radius0, seed, iteration):
+    """one K57 launch on ready rows; idx int32 [B,Nq,k] contiguous or None -> (idx_out, val_out), fresh buffers"""
+    th_t, ph_t, mu, a, nu, b = rows6
+    B, Nq, K = th_t.shape
+    idx_out = torch.empty((B, Nq, k), device=th_t.device, dtype=torch.int32)
+    val_out = torch.empty((B, Nq, k), device=th_t.device, dtype=torch.float32)
+    _call("patchmatch_step_box3", "cocos_patchmatch_step_box3", th_t.data_ptr(), ph_t.data_ptr(), mu.data_ptr(), a.data_ptr(),
+          nu.data_ptr(), b.data_ptr(), _ptr(idx), idx_out.data_ptr(), val_out.data_ptr(), B, K, fh, fw, gh, gw, k, stride, radii, radius0,
+          seed, iteration, float(inv_t), _stream())
+    return idx_out, val_out
+
+
+def patchmatch_step_box3(theta_raw, phi_raw, mu, a, nu, b, idx, inv_t: float, k: int, stride: int, radii: int, radius0: int, seed: int,
+                         iteration: int):
+    """One PatchMatch iteration on the match_kernel-3 route (K57; forward only: the inputs are detached and no autograd node is made)
+    -> (idx int32 [B,Nq,k], val [B,Nq,k]).  The pool, the draw, the order and the short-pool rule are patchmatch_step's, with the
+    content grid fh x fw of theta_raw [B,256,fh,fw] as the query grid and the exemplar grid gh x gw of phi_raw [B,256,gh,gw] as the key
+    grid (any sizes, equal or not); (mu, a) [B,fh*fw] and (nu, b) [B,gh*gw] as unfold3_stats returns them for theta_raw and phi_raw.
+    idx [B,Nq,k] int32 / int64 (values outside the key grid are clamped into it) or None: the hashed initialisation.  val holds the
+    logits box3_sparse_softmax_warp forms for the same pairs, z = inv_t a_p b_q (R[p,q] - 9*256 mu_p nu_q).  Nothing Nq x Nk is
+    allocated.  Bad shapes, k, inv_t, stride, radii: ValueError before the library is called."""
+    name = "patchmatch_step_box3"
+    B, fh, fw, gh, gw, stats = _patchmatch_box3_operands(name, theta_raw, phi_raw, mu, a, nu, b, k)
+    _patchmatch_box3_temperature(name, inv_t)
+    _patchmatch_search(name, stride, radii, radius0, seed, iteration)
+    if idx is not None:
+        idx = _int_table(name, "the index table", idx, (B, fh * fw, k))
+    with torch.no_grad():
+        rows6 = _patchmatch_box3_rows(name, theta_raw, phi_raw, stats)
+        if idx is not None:
+            _gate(name, ((idx, "idx"),), False)
+        return _patchmatch_box3_launch(rows6, idx, fh, fw, gh, gw, inv_t, k, stride, radii, radius0, seed, iteration)
+
+
+def patchmatch_topk_box3(theta_raw, phi_raw, mu, a, nu, b, inv_t: float, k: int, init="random", strides=PATCHMATCH_DEFAULTS["strides"],
+                         radii=PATCHMATCH_DEFAULTS["radii"], seed: int = 0):
+    """PatchMatch top-k selection on the match_kernel-3 route (K57; forward only) -> (idx int32 [B,Nq,k], val [B,Nq,k]) for
+    box3_sparse_softmax_warp: one patchmatch_step_box3 launch per entry of `strides` (iteration t = 0, 1, ...: launch t reads the table
+    launch t - 1 wrote, two buffers alive at a time) on position-major rows made once.  `init`, `strides`, `radii` (a number, starting
+    at half the longer side of the exemplar grid, or a pair (radii, radius0)) and `seed` as patchmatch_topk takes them; operands and
+    errors as patchmatch_step_box3; an empty `strides` is a ValueError (a selection needs scores)."""
+    name = "patchmatch_topk_box3"
+    B, fh, fw, gh, gw, stats = _patchmatch_box3_operands(name, theta_raw, phi_raw, mu, a, nu, b, k)
+    _patchmatch_box3_temperature(name, inv_t)
+    if isinstance(init, str) and init != "random" or not (isinstance(init, str) or torch.is_tensor(init)):
+        raise ValueError(f"{name}: init={init!r}: expected 'random' or an integer tensor [B,Nq,k]")
+    try:
+        strides = tuple(strides)
+    except TypeError:
+        raise ValueError(f"{name}: strides={strides!r}: expected a non-empty sequence of integers >= 1") from None
+    if not strides:
+        raise ValueError(f"{name}: strides is empty: expected a non-empty sequence of integers >= 1")
+    n_radii, radius0 = radii if isinstance(radii, (tuple, list)) and len(radii) == 2 else (radii, max(gh, gw) // 2)
+    for t, stride in enumerate(strides):
+        _patchmatch_search(name, stride, n_radii, radius0, seed, t)
+    idx = None if isinstance(init, str) else _int_table(name, "the index table", init, (B, fh * fw, k))
+    with torch.no_grad():
+        rows6 = _patchmatch_box3_rows(name, theta_raw, phi_raw, stats)
+        if idx is not None:
+            _gate(name, ((idx, "idx"),), False)
+        val = None
+        for t, stride in enumerate(strides):
+            idx, val = _patchmatch_box3_launch(rows6, idx, fh, fw, gh, gw, inv_t, k, stride, n_radii, radius0, seed, t)
+        return idx, val
+
+
 class _GatherKeys(torch.autograd.Function):
     """x[b, idx[b,p]] with a backward that is a GATHER in a fixed order: the key kernel of the pair unit at one channel — its dv output
     sums w over the inverse table's list of every key, with w the upstream gradient and dout = 1 (exact products)."""

@@ -1528,6 +1528,25 @@ int cocos_patchmatch_step_f16x3(const void* qh, const void* ql, const void* kh, 
                                 int radius0, int seed, int iteration, float inv_temperature, float operand_scale, cocos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K57 PatchMatch candidate search on the match_kernel-3 route (patchmatch_box3.hip): ONE Jacobi iteration per call, K43's step with
+ *     the box logit of K51 as the score — the selector of cocos_box3_sparse_softmax_warp_fwd that needs no HW x HW tensor.
+ *     Content (query) grid fh x fw, exemplar (key) grid gh x gw, any sizes, equal or not.  The pool of a query, the hash, the random
+ *     initialisation with idx_in null, the order of idx_out / val_out [B,Nq,k] (the k best DISTINCT keys, score descending, equal bits:
+ *     lower key first), the repeat of the last pair in a short pool and the instantiations (1, 2, 4, 8; a k between two runs the next
+ *     larger one, truncated) are cocos_patchmatch_step_f16x3's, word for word (patchmatch_pool.h is shared).
+ *     val is the logit z = inv_temperature a_p b_q (R[p,q] - 9*256 mu_p nu_q) of cocos_box3_sparse_softmax_warp_fwd for the same pair,
+ *     formed in the same expressions: th_t [B,Nq,256], ph_t [B,Nk,256] fp32 position-major rows, (mu, a) [B,Nq], (nu, b) [B,Nk] the
+ *     K12 statistics.  A tap is inside a grid by its 2-D coordinates.
+ *     Null rows / statistics / outputs, idx_in == idx_out, non-positive inv_temperature, misaligned rows: COCOS_ERR_INVALID; K != 256,
+ *     an empty grid or batch, k outside 1..COCOS_MATCH_TOPK_MAX or above Nk, stride < 1, radii outside 0..COCOS_PATCHMATCH_MAX_RADII,
+ *     radius0 outside 0..2^20, B Nq k or B Nk at or above 2^31: COCOS_ERR_UNSUPPORTED — in this order, all before any HIP call.
+ * ------------------------------------------------------------------------------------- */
+int cocos_patchmatch_step_box3(const float* th_t, const float* ph_t, const float* mu, const float* a, const float* nu, const float* b,
+                               const int* idx_in /* nullable */, int* idx_out, float* val_out, int B, int K, int fh, int fw, int gh, int gw,
+                               int k, int stride, int radii, int radius0, int seed, int iteration, float inv_temperature,
+                               cocos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * K44 Sub-cell match refinement (plane_pair.hip, gather_warp.hip): a soft-argmax over the window of keys around a hard
  *     match, and the full-resolution warp sampled at the refined position.
  *   cocos_match_refine_f16x3: qh, ql [B,Nq,256], kh, kl [B,Nk,256] operand planes and score arithmetic as K42 / K43 (the logit
